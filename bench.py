@@ -11,11 +11,20 @@ start iterate and the cost grid, ~45 MB at L=9, are handed over per solve).
 The direct solve does not shard ("replicas only"), so at N > 1 every rank
 solves its own replica of the workload and `value` is the aggregate rate (weak scaling).
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` is
+the wall-clock of one timed step).  `--dump-outputs DIR` writes what the last timed step
+returned (the solution z and the t-ramp arrays of mgb_driver) as DIR/<name>.npy; the inputs
+are a function of the arguments alone, so two builds can be compared output for output.
+
+`--full` adds these objects to the JSON line:
   roofline     -- the fused element Hessian kernel (the largest HBM stream of the path,
-                  SURVEY.md section 8d) timed live with hipEvents on the library's stream;
+                  SURVEY.md section 8d) timed live with hipEvents on the library's stream,
+                  with rocprofv3 kernel-trace and PMC child passes at N = 1 (unless --no-traffic);
+  roofline_solver -- what bounds the sparse LDL' (same child passes);
+  north_star_p15, reference_anchor_L7_p1 -- the p = 1.5 line and the L = 7 anchor, N = 1 only
+                  (unless --no-p15);
   cpu_baseline -- the NumPy/SciPy oracle (+ host multifrontal Cholesky) on a bounded
-                  sample of the same workload, rank 0 / N = 1 only.
+                  sample of the same workload, N = 1 only (unless --no-cpu-baseline).
 """
 import argparse
 import json
@@ -271,6 +280,89 @@ def timed_solves(mgb_driver, D, steps):
     return its_total, solve_s, core_s, last
 
 
+def roofline_measurements(mgb_driver, D, n, stats, kstats, traffic, traffic_note):
+    """--full: the `roofline` and `roofline_solver` objects of the result line."""
+    main = D.main
+    fine = len(main.level_sizes) - 1
+    # ---- roofline of the dominant HBM kernel: fused element Hessian (f2), fine level ----
+    # One more solve of the same workload, outside the timed region, with the library's hipEvent
+    # stage timers switched on (events recorded on the library's own stream around every stage):
+    # the fine-level launches are timed exactly as they occur in the Newton loop.
+    main.reset_stage_timers(True)
+    mgb_driver(D)
+    st = {k: main.stage_ms(k) for k in ("f2", "assemble", "f0", "f1", "f01", "restrict", "prolong", "factor", "trisolve")}
+    main.reset_stage_timers(False)
+    avg_us = {k: (1e3 * ms / cnt if cnt else 0.0) for k, (ms, cnt) in st.items()}
+    gbs = lambda nbytes, us: (nbytes / (us * 1e-6) / 1e9) if us > 0 else 0.0
+    # the roofline's launch duration: rocprofv3's kernel-trace average of the condensing f2 instantiation (child pass);
+    # the hipEvent stage timer of the live solve is kept beside it (it brackets the launch, a few us more)
+    f2_hipevent_us = avg_us["f2"]
+    f2_rocprof = [(c, a) for name, (c, a, t) in (kstats or {}).items()
+                  if "elem_f2_fast" in name and ("true" in name or "(bool)1" in name)]
+    f2_us = (sum(c * a for c, a in f2_rocprof) / sum(c for c, a in f2_rocprof) / 1e3) if f2_rocprof else f2_hipevent_us
+    achieved = gbs(BYTES["f2"] * n, f2_us)
+    # aggregate of SURVEY 8(d): one fine Newton iteration = f2 + assembly + f0 + f1 (prolongation and the
+    # R' gather are part of those stages' stage timers) against 1285 B / node.  The line search evaluates
+    # f0 and f1 of a trial in ONE pass over the operators (stage "f01"); the separate f0 / f1 stages only
+    # run once per Newton solve (the start point) and are not part of an iteration.
+    trial_us = avg_us["f01"] if st["f01"][1] else avg_us["f0"] + avg_us["f1"]
+    agg_us = avg_us["f2"] + avg_us["assemble"] + trial_us + avg_us["restrict"]
+    roofline = dict(
+        bound="hbm",
+        kernel="elem_f2_fast<4,7,SigDefault,CONDENSE>: fused Dz + cone Hessian + element blocks + static condensation of "
+               "the element's slack and bubble unknowns (writes the leaf fronts of the factorization), fine level -- the f2 "
+               "stage of the Newton loop; it replaces round 2's f2 + assembly + leaf-level factorization kernels",
+        achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
+        numerator="SURVEY 8(d) algorithmic bytes of f2 alone: 347 B/node x n (the kernel also does the assembly's and the leaf "
+                  "level's work, which 8(d) prices at 488 B/node more; not claimed here)",
+        traffic=traffic, traffic_source=traffic_note,
+        bytes_per_launch=BYTES["f2"] * n, avg_launch_us=f2_us,
+        avg_launch_source=("rocprofv3 --kernel-trace --stats child pass" if f2_rocprof else "hipEvent stage timers (no kernel trace)"),
+        avg_launch_us_hipevents=f2_hipevent_us, launches=int(st["f2"][1]),
+        moved_bytes_model=F2_MOVED_BYTES_PER_NODE * n,
+        moved_gbs=gbs(F2_MOVED_BYTES_PER_NODE * n, f2_us),
+        moved_frac=gbs(F2_MOVED_BYTES_PER_NODE * n, f2_us) / HBM_PEAK_GBS,
+        measured_gbs=(gbs(traffic, f2_us) if traffic else None),
+        measured_frac=(gbs(traffic, f2_us) / HBM_PEAK_GBS if traffic else None),
+        aggregate=dict(stages_us={"f0+f1 (one pass)": trial_us, "restrict": avg_us["restrict"], "f2": avg_us["f2"],
+                                  "assemble": avg_us["assemble"]}, total_us=agg_us,
+                       note=("bytes are SURVEY 8(d)'s algorithmic 1285 B/node; the device moves fewer: the trial reads the operators "
+                             "once for f0 and f1, and the fine level never forms H as a CSR value array (the factorization reads "
+                             "single-contribution entries from the element-block slab, 'assemble' sums only the shared ones)"),
+                       bytes=sum(BYTES.values()) * n, gbs=gbs(sum(BYTES.values()) * n, agg_us),
+                       frac=gbs(sum(BYTES.values()) * n, agg_us) / HBM_PEAK_GBS),
+        factor_avg_us=avg_us["factor"], trisolve_avg_us=avg_us["trisolve"],
+        solver_note="factor carries the forward substitution (bordered LDL'); trisolve is the backward sweep only")
+    roofline_solver = solver_roofline(kstats, main.solver_chain(fine), stats, avg_us["factor"], avg_us["trisolve"])
+    return roofline, roofline_solver
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, z, SOL):
+    """What the last timed mgb_driver call returned: z (nodes x components) and the per-t-step arrays of each phase
+    (Newton iterations per level, t, kappa, c.Dz; not the wall-clock `times`).  All float64.  If z would take the
+    total over DUMP_LIMIT_BYTES, a fixed seeded sample of its rows is written instead, with the row indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for phase, key in (("main", "SOL_main"), ("feasibility", "SOL_feasibility")):
+        if SOL[key] is not None:
+            for name in ("its", "ts", "kappas", "c_dot_Dz"):
+                arrays[f"{phase}_{name}"] = np.asarray(SOL[key][name], dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values()) - 4096        # 4 KiB: the .npy headers
+    if z.nbytes <= room:
+        arrays["z"] = z
+    else:
+        k = room // (z.shape[1] * 8 + 8)
+        rows = np.sort(np.random.default_rng(0).choice(z.shape[0], size=k, replace=False))
+        arrays["z_sample"] = z[rows]
+        arrays["z_sample_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -285,6 +377,9 @@ def main():
     ap.add_argument("--sharded", action="store_true",
                     help="N > 1: ONE workload domain-decomposed over the ranks (strong scaling) instead of N replicas")
     ap.add_argument("--device-pointers", action="store_true", help="--sharded: pass device pointers to RCCL (no host staging)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the p = 1.5 and L = 7 lines and the CPU baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -292,7 +387,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # PMC passes first: child processes, before this process initialises the GPU (rank 0, N = 1 only)
     traffic, traffic_note, kstats = None, "not measured", None
-    if world == 1 and rank == 0 and not args.no_traffic and os.environ.get("MGB_BENCH_TRAFFIC", "1") == "1":
+    if args.full and world == 1 and rank == 0 and not args.no_traffic and os.environ.get("MGB_BENCH_TRAFFIC", "1") == "1":
         traffic, traffic_note, kstats = profile_children(args.L, args.p, hierarchies(args.p, args.L)[0])
 
     import torch
@@ -340,6 +435,11 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed_max = float(tmax.item())
+        if args.dump_outputs and args.steps > 0:
+            parts = [None] * world                   # ranks hold consecutive node ranges (ShardedSolver.solve)
+            dist.all_gather_object(parts, SOL["z"])
+            if rank == 0:
+                dump_outputs(args.dump_outputs, np.concatenate(parts, axis=0), SOL)
         iface = [int(sh.iface.size) for sh in S.shards[0]]
         local = [int(sh.cols.size) for sh in S.shards[0]]
         S.close()
@@ -380,60 +480,14 @@ def main():
     from mgb_amd.replicas import aggregate
     elapsed_max, its_all = aggregate(elapsed, its_total, dist, device="cpu" if rehearsal else "cuda")
 
-    # ---- roofline of the dominant HBM kernel: fused element Hessian (f2), fine level ----
-    # One more solve of the same workload, outside the timed region, with the library's hipEvent
-    # stage timers switched on (events recorded on the library's own stream around every stage):
-    # the fine-level launches are timed exactly as they occur in the Newton loop.
     main = D.main
     fine = len(main.level_sizes) - 1
     n = prob.M[0].w.size
-    main.reset_stage_timers(True)
-    mgb_driver(D)
-    st = {k: main.stage_ms(k) for k in ("f2", "assemble", "f0", "f1", "f01", "restrict", "prolong", "factor", "trisolve")}
-    main.reset_stage_timers(False)
-    avg_us = {k: (1e3 * ms / cnt if cnt else 0.0) for k, (ms, cnt) in st.items()}
-    gbs = lambda nbytes, us: (nbytes / (us * 1e-6) / 1e9) if us > 0 else 0.0
-    # the roofline's launch duration: rocprofv3's kernel-trace average of the condensing f2 instantiation (child pass);
-    # the hipEvent stage timer of the live solve is kept beside it (it brackets the launch, a few us more)
-    f2_hipevent_us = avg_us["f2"]
-    f2_rocprof = [(c, a) for name, (c, a, t) in (kstats or {}).items()
-                  if "elem_f2_fast" in name and ("true" in name or "(bool)1" in name)]
-    f2_us = (sum(c * a for c, a in f2_rocprof) / sum(c for c, a in f2_rocprof) / 1e3) if f2_rocprof else f2_hipevent_us
-    achieved = gbs(BYTES["f2"] * n, f2_us)
-    # aggregate of SURVEY 8(d): one fine Newton iteration = f2 + assembly + f0 + f1 (prolongation and the
-    # R' gather are part of those stages' stage timers) against 1285 B / node.  The line search evaluates
-    # f0 and f1 of a trial in ONE pass over the operators (stage "f01"); the separate f0 / f1 stages only
-    # run once per Newton solve (the start point) and are not part of an iteration.
-    trial_us = avg_us["f01"] if st["f01"][1] else avg_us["f0"] + avg_us["f1"]
-    agg_us = avg_us["f2"] + avg_us["assemble"] + trial_us + avg_us["restrict"]
-    roofline = dict(
-        bound="hbm",
-        kernel="elem_f2_fast<4,7,SigDefault,CONDENSE>: fused Dz + cone Hessian + element blocks + static condensation of "
-               "the element's slack and bubble unknowns (writes the leaf fronts of the factorization), fine level -- the f2 "
-               "stage of the Newton loop; it replaces round 2's f2 + assembly + leaf-level factorization kernels",
-        achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
-        numerator="SURVEY 8(d) algorithmic bytes of f2 alone: 347 B/node x n (the kernel also does the assembly's and the leaf "
-                  "level's work, which 8(d) prices at 488 B/node more; not claimed here)",
-        traffic=traffic, traffic_source=traffic_note,
-        bytes_per_launch=BYTES["f2"] * n, avg_launch_us=f2_us,
-        avg_launch_source=("rocprofv3 --kernel-trace --stats child pass" if f2_rocprof else "hipEvent stage timers (no kernel trace)"),
-        avg_launch_us_hipevents=f2_hipevent_us, launches=int(st["f2"][1]),
-        moved_bytes_model=F2_MOVED_BYTES_PER_NODE * n,
-        moved_gbs=gbs(F2_MOVED_BYTES_PER_NODE * n, f2_us),
-        moved_frac=gbs(F2_MOVED_BYTES_PER_NODE * n, f2_us) / HBM_PEAK_GBS,
-        measured_gbs=(gbs(traffic, f2_us) if traffic else None),
-        measured_frac=(gbs(traffic, f2_us) / HBM_PEAK_GBS if traffic else None),
-        aggregate=dict(stages_us={"f0+f1 (one pass)": trial_us, "restrict": avg_us["restrict"], "f2": avg_us["f2"],
-                                  "assemble": avg_us["assemble"]}, total_us=agg_us,
-                       note=("bytes are SURVEY 8(d)'s algorithmic 1285 B/node; the device moves fewer: the trial reads the operators "
-                             "once for f0 and f1, and the fine level never forms H as a CSR value array (the factorization reads "
-                             "single-contribution entries from the element-block slab, 'assemble' sums only the shared ones)"),
-                       bytes=sum(BYTES.values()) * n, gbs=gbs(sum(BYTES.values()) * n, agg_us),
-                       frac=gbs(sum(BYTES.values()) * n, agg_us) / HBM_PEAK_GBS),
-        factor_avg_us=avg_us["factor"], trisolve_avg_us=avg_us["trisolve"],
-        solver_note="factor carries the forward substitution (bordered LDL'); trisolve is the backward sweep only")
     stats = main.solver_stats(fine)
-    roofline_solver = solver_roofline(kstats, main.solver_chain(fine), stats, avg_us["factor"], avg_us["trisolve"])
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last["z"], last)
+    if args.full:
+        roofline, roofline_solver = roofline_measurements(mgb_driver, D, n, stats, kstats, traffic, traffic_note)
 
     out = None
     if rank == 0:
@@ -467,12 +521,12 @@ def main():
             "t_steps": int(sm["k"]),
             "setup_s": setup,
             "factorization": {k: stats[k] for k in ("fronts", "max_front", "factor_flops", "tree_levels", "nnz", "unknowns")},
-            "roofline": roofline,
-            "roofline_solver": roofline_solver,
         }
+        if args.full:
+            out.update(roofline=roofline, roofline_solver=roofline_solver)
     D.close()
     # ---- north_star target line: fem2d_P2 p = 1.5 at the same L (BASELINE.json north_star), rank 0 / N = 1 ----
-    if rank == 0 and world == 1 and not args.no_p15 and args.p != 1.5:
+    if args.full and rank == 0 and world == 1 and not args.no_p15 and args.p != 1.5:
         prob15, D15, used15, setup15 = run_workload(m, DeviceMGBProblem, mgb_driver, MGBConvergenceFailure, args.L, 1.5,
                                                     dev_index, 1, rank)
         torch.cuda.synchronize()
@@ -507,11 +561,11 @@ def main():
                 wall_clock_to_converge_s=el7 / max(args.steps, 1), value=its7 / el7, unit="newton_iters/s",
                 newton_iterations_per_solve=its7 / max(args.steps, 1),
                 hierarchy=f"amg_ruge_stuben({used7 if used7 else 'max_coarse=2: the reference default'})",
-                published=dict(source="/root/reference/bench.md:21", cpu_s=66.509, gpu_s=5.122,
+                published=dict(source="MultiGridBarrier.jl bench.md:21", cpu_s=66.509, gpu_s=5.122,
                                hardware="DMOG cluster CPU (unspecified) / 1x NVIDIA A40 + cuDSS, Julia 1.11.6",
                                note="different hardware and a different Ruge-Stueben implementation (iteration counts differ): an anchor, not a like-for-like ratio"))
             D7.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(prob, args.cpu_budget, its_per_level=its_levels)
         if out["cpu_baseline"]["value"] > 0:
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]

@@ -3,8 +3,8 @@ hierarchy the reference specifies completely in-repo, hence the place where prol
 checked bit-exactly (BASELINE north_star).  The expected integer structure is derived here independently
 of the package's sparse products: per fine element, follow the parent chain and multiply the boolean
 patterns of the child-interpolation table."""
+import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -34,13 +34,13 @@ def test_refine_table_is_the_reference_literal_and_nearly_the_exact_interpolant(
     rounded = np.flatnonzero(diff > 1e-12)
     assert rounded.size == 6 and diff.max() < 4e-3             # the six rows with integer-rounded numerators
     assert np.allclose(T[np.setdiff1d(np.arange(28), rounded)], E[np.setdiff1d(np.arange(28), rounded)], atol=1e-15)
-    src = "/root/reference/src/fem2d_P2.jl"
-    if os.path.exists(src):                                     # this container only: the literal itself
-        mm = re.search(r"refine = sparse\(\[([^\]]*)\], \[([^\]]*)\], T\[([^\]]*)\]\./648, 28, 7\)", open(src).read())
-        Tr = np.zeros((28, 7))
-        for r, c, v in zip(*(x.split(",") for x in mm.groups())):
-            Tr[int(r) - 1, int(c) - 1] = float(v) / 648
-        assert np.array_equal(Tr, T)
+    # the literal itself, transcribed as numbers from the reference's src/fem2d_P2.jl (tests/golden/refine_p2.json)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refine_p2.json")) as fh:
+        lit = json.load(fh)
+    Tr = np.zeros(lit["shape"])
+    for r, c, v in zip(lit["rows"], lit["cols"], lit["numerators"]):
+        Tr[r - 1, c - 1] = float(v) / lit["denominator"]
+    assert np.array_equal(Tr, T)
     P = fp.refine_table(False)
     assert P.shape == (24, 6) and np.allclose(P.sum(axis=1), 1.0)
 

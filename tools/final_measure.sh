@@ -3,15 +3,15 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final
 mkdir -p $O
 cd $R
-python bench.py > $O/bench_L9.json 2> $O/bench_L9.err
+python bench.py --full > $O/bench_L9.json 2> $O/bench_L9.err
 echo bench done >> $O/progress
-python bench.py --L 7 --p 1.5 --no-traffic --no-p15 --cpu-budget 10 > $O/bench_L7.json 2> $O/bench_L7.err
+python bench.py --full --L 7 --p 1.5 --no-traffic --no-p15 --cpu-budget 10 > $O/bench_L7.json 2> $O/bench_L7.err
 echo bench7 done >> $O/progress
 MGBHIP_DEBUG=2 python tools/gpu_solver_levels.py 9 1.0 10 "{}" > $O/solver_levels.txt 2>&1
 python tools/setup_timing.py 9 1.0 > $O/setup_timing.json 2>$O/setup_timing.err
 echo levels done >> $O/progress
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 $R/bench.py --no-cpu-baseline --no-traffic --no-p15 --steps 2 > $O/prof_bench.out 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 $R/bench.py --full --no-cpu-baseline --no-traffic --no-p15 --steps 2 > $O/prof_bench.out 2>&1
 cp $(find /tmp/p1 -name "*kernel_stats.csv" | head -1) $O/bench_L9_kernel_stats.csv
 echo prof1 done >> $O/progress
 REPS=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p4 -- python3 $R/tools/gpu_fem3d.py 6 4.0 '{"max_coarse":300}' > $O/prof_c4.out 2>&1
