@@ -40,8 +40,9 @@ extern "C" {
 #define MGBHIP_ERR_CONVERGENCE 5  /* MGBConvergenceFailure (src/utils.jl:178-184); code in diagnostics */
 
 #define MGBHIP_MAX_PIECES 4
-#define MGBHIP_MAX_IDX 4
-#define MGBHIP_MAX_ND 10   /* 3-D parabolic phase I: (dim + 3) + 1 + 3 rows */
+#define MGBHIP_MAX_IDX 10  /* Euclidean-power piece width nz (3-D p_harmonic / norton_hoff: d^2 + 1)      */
+#define MGBHIP_MAX_LIN 4   /* linear pieces: at most 4 constraint rows (nc) on at most 4 indexed rows (ni)  */
+#define MGBHIP_MAX_ND 13   /* 3-D vector problems: d (1 + d) + 1 rows                                      */
 #define MGBHIP_MAX_NU 4
 #define MGBHIP_MAX_OPS 8
 

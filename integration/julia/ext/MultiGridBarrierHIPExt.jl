@@ -27,7 +27,8 @@ import MultiGridBarrier: Device, HIPDevice, native_to_device, device_to_native, 
 const libmgbhip = get(ENV, "MGBHIP_LIB", "libmgbhip.so")
 
 # ---- mirrors of the C structs (include/mgbhip.h); field order and types are the header's -------------
-const MAX_PIECES, MAX_IDX, MAX_ND, MAX_NU, MAX_OPS = 4, 4, 10, 4, 8
+const MAX_PIECES, MAX_IDX, MAX_ND, MAX_NU, MAX_OPS = 4, 10, 13, 4, 8
+const MAX_LIN = 4     # linear pieces: rows and indexed rows (MGBHIP_MAX_LIN)
 const KIND_EP, KIND_LINEAR = Int32(1), Int32(2)          # MGBHIP_KIND_EP / MGBHIP_KIND_LINEAR
 
 struct CPiece
@@ -125,7 +126,11 @@ function build_desc(M::AMG, Q::Convex; feasibility::Bool, NC::Int, keep::Vector{
     cp = ntuple(MAX_PIECES) do k
         k > length(pcs) && return NOPIECE
         q = pcs[k]
-        length(q.idx) <= MAX_IDX && q.nc <= MAX_IDX || error("HIPDevice: functor family size exceeds MGBHIP_MAX_IDX")
+        if q.kind == KIND_LINEAR
+            length(q.idx) <= MAX_LIN && q.nc <= MAX_LIN || error("HIPDevice: linear piece exceeds MGBHIP_MAX_LIN ($MAX_LIN rows on $MAX_LIN indexed rows)")
+        else
+            length(q.idx) <= MAX_IDX || error("HIPDevice: Euclidean-power piece wider than MGBHIP_MAX_IDX ($MAX_IDX)")
+        end
         idx = ntuple(j -> j <= length(q.idx) ? Int32(q.idx[j] - 1) : Int32(0), MAX_IDX)
         constp = q.p !== nothing && allequal(q.p) && allequal(q.mu)
         CPiece(q.kind, length(q.idx), q.nc, idx, col(q.A), col(q.b),

@@ -17,6 +17,7 @@ from .spectral import spectral1d, spectral2d, SPECTRAL1D, SPECTRAL2D
 from .amg_prolongators import amg_ruge_stuben, amg_smoothed_aggregation
 from .convex import Convex, Piece, convex_Euclidian_power, convex_linear, convex_piecewise, intersect
 from .parabolic import parabolic_solve, ParabolicSOL
+from . import zoo as Zoo
 from .problem import (MGBProblem, assemble, amg, subdivide, geometric_mg, find_boundary, default_f, default_g,
                       default_D, default_idx)
 

@@ -179,6 +179,101 @@ void launch_node_ny(const ElemParams& P, int mode, hipStream_t st) {
     MGB_HIP_CHECK(hipGetLastError());
 }
 
+// Wide path (cone.hpp: cone_eval_wide): the node Hessian triangle goes straight to dn_Y entry by entry, each thread
+// accumulating into its own node's column of the n x nD(nD+1)/2 workspace.
+template <int MODE>
+__global__ __launch_bounds__(256) void dense_node_wide_kernel(const ElemParams P) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const int64_t n = P.n;
+    const int nD = P.nD;
+    const int64_t node = (int64_t)blockIdx.x * 256 + tid;
+    const bool active = node < n;
+    double y[WIDE_NY];
+#pragma unroll
+    for (int k = 0; k < WIDE_NY; ++k) y[k] = (active && k < nD) ? P.dn_Dz[node + n * k] : 0.0;
+    double F = 0.0;
+    double g[WIDE_NY];
+    if (MODE == MODE_NODE_F) {
+        if (active) {
+            cone_eval_wide<0>(P.cone, node, n, nD, y, F, g, nullptr, 0);
+            P.out_F[node] = F;
+            if (P.out_Dz != nullptr)
+                for (int k = 0; k < nD; ++k) P.out_Dz[node + n * k] = y[k];
+        }
+        return;
+    }
+    if (MODE == MODE_NODE_SLACK) {
+        if (active) P.out_F[node] = cone_slack<WIDE_NY, WIDE_W>(P.cone, node, n, y);
+        return;
+    }
+    if (MODE == MODE_F0) {
+        double val = 0.0;
+        if (active) {
+            cone_eval_wide<0>(P.cone, node, n, nD, y, F, g, nullptr, 0);
+            double bar;
+            if (P.bw != nullptr) {
+                const double bwv = P.bw[node];
+                bar = (bwv == 0.0) ? 0.0 : bwv * F;
+            } else {
+                bar = (P.invn == 0.0) ? 0.0 : P.invn * F;
+            }
+            double lin = 0.0;
+            for (int k = 0; k < nD; ++k) lin += P.c[node + n * k] * y[k];
+            val = bar + P.w[node] * lin;
+        }
+        red[tid] = val;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if (tid < off) red[tid] += red[tid + off];
+            __syncthreads();
+        }
+        if (tid == 0) P.out_partial[blockIdx.x] = red[0];
+        return;
+    }
+    if (MODE == MODE_F1) {
+        if (active) {
+            cone_eval_wide<1>(P.cone, node, n, nD, y, F, g, nullptr, 0);
+            const double wv = P.w[node];
+            const double bwv = P.bw ? P.bw[node] : 0.0;
+#pragma unroll
+            for (int k = 0; k < WIDE_NY; ++k) {
+                if (k >= nD) continue;
+                const double sc = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * g[k]) : P.invn * g[k];
+                P.dn_Y[node + n * k] = sc + wv * P.c[node + n * k];
+            }
+        }
+        return;
+    }
+    if (MODE == MODE_F2) {
+        if (active) {
+            const int NT = nD * (nD + 1) / 2;
+            double* Tn = P.dn_Y + node;
+            for (int t = 0; t < NT; ++t) Tn[n * t] = 0.0;
+            cone_eval_wide<2>(P.cone, node, n, nD, y, F, g, Tn, (int)n);
+            const double bwv = P.bw ? P.bw[node] : 0.0;
+            for (int t = 0; t < NT; ++t) {
+                const double h = Tn[n * t];
+                Tn[n * t] = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * h) : P.invn * h;
+            }
+        }
+        return;
+    }
+}
+
+static void launch_node_wide(const ElemParams& P, int mode, hipStream_t st) {
+    const dim3 grid((unsigned)dense_grid(P.n)), blk(256);
+    switch (mode) {
+        case MODE_F0: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_F0>), grid, blk, 0, st, P); break;
+        case MODE_F1: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_F1>), grid, blk, 0, st, P); break;
+        case MODE_F2: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_F2>), grid, blk, 0, st, P); break;
+        case MODE_NODE_F: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_NODE_F>), grid, blk, 0, st, P); break;
+        case MODE_NODE_SLACK: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_NODE_SLACK>), grid, blk, 0, st, P); break;
+        default: throw InvalidArgument("launch_dense_eval: bad mode");
+    }
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------------------------
 // W = Ybar * DR: thread per (node, column)
 // ---------------------------------------------------------------------------------------------
@@ -481,6 +576,7 @@ void launch_dense_weight(int NY, int klo, int khi, int64_t n, int64_t m, int64_t
 #define MGB_CASE(X) \
     case X: hipLaunchKernelGGL((dense_weight_kernel<X>), grid, blk, 0, st, klo, khi, n, ld, DR, Yh, W); break;
         MGB_CASE(1) MGB_CASE(2) MGB_CASE(3) MGB_CASE(4) MGB_CASE(5) MGB_CASE(6) MGB_CASE(7) MGB_CASE(8) MGB_CASE(9) MGB_CASE(10)
+        MGB_CASE(11) MGB_CASE(12) MGB_CASE(13)
 #undef MGB_CASE
         default: throw InvalidArgument("dense_weight: nD out of range");
     }
@@ -498,7 +594,9 @@ void launch_dense_eval(const ElemParams& P, int mode, hipStream_t st) {
         if (op == nullptr) MGB_HIP_CHECK(hipMemcpyAsync(P.dn_Dz + (int64_t)k * n, za, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
         else launch_dense_gemv_n(n, n, op, n, za, P.dn_Dz + (int64_t)k * n, st);
     }
-    switch (P.nD) {
+    if (P.wide) {
+        launch_node_wide(P, mode, st);
+    } else switch (P.nD) {
 #define MGB_CASE(X) case X: launch_node_ny<X>(P, mode, st); break;
         MGB_CASE(1) MGB_CASE(2) MGB_CASE(3) MGB_CASE(4) MGB_CASE(5) MGB_CASE(6) MGB_CASE(7) MGB_CASE(8) MGB_CASE(9) MGB_CASE(10)
 #undef MGB_CASE

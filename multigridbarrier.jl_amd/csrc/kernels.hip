@@ -297,6 +297,201 @@ __global__ __launch_bounds__(256) void elem_kernel(const ElemParams P, const int
     }
 }
 
+// Wide path (problems with more than 10 D rows or a power cone wider than NARROW_W; cone.hpp: cone_eval_wide): the same
+// contract as elem_kernel -- z_at with the selection map, the on-the-fly trial point, barrier weights / invn, diag_mask
+// and blk_off of the slab, the phase-I cobarrier and box terms -- for a runtime nD <= WIDE_NY.  y and the gradient live
+// in registers (WIDE_NY doubles each); the node Hessian is written entry by entry into its LDS triangle [EPB][tri][G]
+// and never held in registers, and the block products run as runtime loops over the D rows.  MODE_F2 runs
+// WIDE_F2_THREADS threads per workgroup (the triangle of 128 lanes at nD = 13 is 93 KB), every other mode 256.
+template <int MODE>
+__global__ __launch_bounds__(256) void elem_wide_kernel(const ElemParams P, const int lgG) {
+    extern __shared__ double sh[];
+    const int tid = threadIdx.x;
+    const int NT_ = blockDim.x;
+    const int G = 1 << lgG;
+    const int EPB = NT_ >> lgG;
+    const int el = tid >> lgG;
+    const int r = tid & (G - 1);
+    const int p = P.p;
+    const int pp = p * p;
+    const int nu = P.nu;
+    const int nD = P.nD;
+    const int64_t e = (int64_t)blockIdx.x * EPB + el;
+    const bool active = (e < P.N) && (r < p);
+    const int64_t n = P.n;
+    const int64_t node = e * p + r;
+
+    double* zl = sh;                                    // [EPB][nu][G]
+    double* opL = zl + (size_t)NT_ * nu;                // [nstage][EPB][pp]
+    double* YL = opL + (size_t)P.nstage * EPB * pp;     // MODE_F1 / F01: [EPB][nD][G]; MODE_F2: [EPB][tri][G]
+    {
+        const int64_t e0 = (int64_t)blockIdx.x * EPB;
+        int64_t lim = (P.N - e0) * pp;
+        if (lim > (int64_t)EPB * pp) lim = (int64_t)EPB * pp;
+        for (int o = 0; o < P.nstage; ++o) {
+            const double* src = P.stage_ptr[o] + e0 * pp;
+            double* dst = opL + (size_t)o * EPB * pp;
+            for (int i = tid; i < lim; i += NT_) dst[i] = src[i];
+        }
+    }
+    if (active) {
+        for (int a = 0; a < nu; ++a) zl[(el * nu + a) * G + r] = z_at(P, (int64_t)a * n + node);
+    }
+    __syncthreads();
+
+    auto OP = [&](int k, int rr, int cc) -> double {
+        const int so = P.D_stage[k];
+        if (so >= 0) return opL[((size_t)so * EPB + el) * pp + cc * p + rr];
+        return P.ops[P.D_op[k]][e * pp + cc * p + rr];
+    };
+
+    double y[WIDE_NY];
+#pragma unroll
+    for (int k = 0; k < WIDE_NY; ++k) {
+        double v = 0.0;
+        if (active && k < nD) {
+            const int a = P.D_state[k];
+            if (P.D_stage[k] == -1) {
+                v = zl[(el * nu + a) * G + r];
+            } else {
+                for (int cc = 0; cc < p; ++cc) v += OP(k, r, cc) * zl[(el * nu + a) * G + cc];
+            }
+        }
+        y[k] = v;
+    }
+    double F = 0.0;
+    double g[WIDE_NY];
+
+    if (MODE == MODE_F0 || MODE == MODE_NODE_F) {
+        if (active) cone_eval_wide<0>(P.cone, node, n, nD, y, F, g, nullptr, 0);
+        if (MODE == MODE_NODE_F) {
+            if (active) {
+                P.out_F[node] = F;
+                if (P.out_Dz != nullptr)
+                    for (int k = 0; k < nD; ++k) P.out_Dz[node + n * k] = y[k];
+            }
+            return;
+        }
+        double val = 0.0;
+        if (active) {
+            double bar;
+            if (P.bw != nullptr) {
+                const double bwv = P.bw[node];
+                bar = (bwv == 0.0) ? 0.0 : bwv * F;
+            } else {
+                bar = (P.invn == 0.0) ? 0.0 : P.invn * F;
+            }
+            double lin = 0.0;
+#pragma unroll
+            for (int k = 0; k < WIDE_NY; ++k) lin += (k < nD) ? P.c[node + n * k] * y[k] : 0.0;
+            val = bar + P.w[node] * lin;
+        }
+        __syncthreads();
+        const double tot = block_sum_256(val, sh);
+        if (tid == 0) P.out_partial[blockIdx.x] = tot;
+        return;
+    }
+    if (MODE == MODE_NODE_SLACK) {
+        if (active) P.out_F[node] = cone_slack<WIDE_NY, WIDE_W>(P.cone, node, n, y);
+        return;
+    }
+    if (MODE == MODE_F1 || MODE == MODE_F01) {
+        double val = 0.0;
+        if (active) {
+            double F0v = 0.0;
+            if (MODE == MODE_F01) cone_eval_wide<0>(P.cone, node, n, nD, y, F0v, g, nullptr, 0);
+            cone_eval_wide<1>(P.cone, node, n, nD, y, F, g, nullptr, 0);
+            const double wv = P.w[node];
+            const double bwv = P.bw ? P.bw[node] : 0.0;
+            double lin = 0.0;
+#pragma unroll
+            for (int k = 0; k < WIDE_NY; ++k) {
+                if (k >= nD) continue;
+                const double ck = P.c[node + n * k];
+                lin += ck * y[k];
+                const double sc = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * g[k]) : P.invn * g[k];
+                YL[(el * nD + k) * G + r] = sc + wv * ck;
+            }
+            if (MODE == MODE_F01) {
+                const double bar = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * F0v) : P.invn * F0v;
+                val = bar + wv * lin;
+            }
+        }
+        __syncthreads();
+        if (active) {
+            const int i = r;
+            for (int a = 0; a < nu; ++a) {
+                double acc = 0.0;
+                for (int k = 0; k < nD; ++k) {
+                    if (P.D_state[k] != a) continue;
+                    const double* Yk = YL + (el * nD + k) * G;
+                    if (P.D_stage[k] == -1) {
+                        acc += Yk[i];
+                    } else {
+                        for (int rr = 0; rr < p; ++rr) acc += OP(k, rr, i) * Yk[rr];
+                    }
+                }
+                P.out_ret[(int64_t)a * n + node] = acc;
+            }
+        }
+        if (MODE == MODE_F01) {
+            __syncthreads();
+            const double tot = block_sum_256(val, sh);
+            if (tid == 0) P.out_partial[blockIdx.x] = tot;
+        }
+        return;
+    }
+    if (MODE == MODE_F2) {
+        const int NT = nD * (nD + 1) / 2;
+        double* Tn = YL + (size_t)el * NT * G + r;      // this node's triangle, stride G
+        for (int t = 0; t < NT; ++t) Tn[(size_t)t * G] = 0.0;
+        if (active) {
+            cone_eval_wide<2>(P.cone, node, n, nD, y, F, g, Tn, G);
+            const double bwv = P.bw ? P.bw[node] : 0.0;
+            for (int t = 0; t < NT; ++t) {
+                const double h = Tn[(size_t)t * G];
+                Tn[(size_t)t * G] = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * h) : P.invn * h;
+            }
+        }
+        __syncthreads();
+        if (active) {
+            const int j = r;
+            for (int a = 0; a < nu; ++a)
+                for (int b = a; b < nu; ++b) {
+                    const int blk = a * nu - (a * (a - 1)) / 2 + (b - a);
+                    const bool dblk = (P.diag_mask >> blk) & 1;
+                    double* out = P.out_hel + P.blk_off[blk] + (dblk ? (e * p + j) - j : (e * p + j) * (int64_t)p);
+                    for (int i = dblk ? j : 0; i < (dblk ? j + 1 : p); ++i) {
+                        double val = 0.0;
+                        for (int k = 0; k < nD; ++k) {
+                            if (P.D_state[k] != a) continue;
+                            const bool idk = P.D_stage[k] == -1;
+                            for (int k2 = 0; k2 < nD; ++k2) {
+                                if (P.D_state[k2] != b) continue;
+                                const bool idk2 = P.D_stage[k2] == -1;
+                                const int t = (k <= k2) ? tri_index(k, k2, nD) : tri_index(k2, k, nD);
+                                const double* Yt = YL + ((size_t)el * NT + t) * G;
+                                if (idk && idk2) {
+                                    val += (i == j) ? Yt[i] : 0.0;
+                                } else if (idk) {
+                                    val += Yt[i] * OP(k2, i, j);
+                                } else if (idk2) {
+                                    val += OP(k, j, i) * Yt[j];
+                                } else {
+                                    double acc = 0.0;
+                                    for (int rr = 0; rr < p; ++rr) acc += OP(k, rr, i) * Yt[rr] * OP(k2, rr, j);
+                                    val += acc;
+                                }
+                            }
+                        }
+                        out[i] = val;
+                    }
+                }
+        }
+        return;
+    }
+}
+
 // Specialised element Hessian kernel for compile-time (NY, P): same arithmetic as MODE_F2 of the
 // generic kernel, restructured so that lane j first forms C_k[r] = sum_k' Y_r[k,k'] D_k'[r,j] in
 // registers and then out[i] = sum_k sum_r D_k[r,i] C_k[r]  (|K_a| * P * (|K_b| + P) multiply-adds
@@ -1692,7 +1887,7 @@ static bool try_f2_fast(const ElemParams& P, hipStream_t st) {
 bool launch_elem_f2_condense(const ElemParams& P, hipStream_t st) {
     // fem2d_P2 with bubble, default D table: 7 nodes per element, node 6 interior (the only family specialised so far)
     constexpr int NY = 4, PN = 7;
-    if (P.nD != NY || P.p != PN || P.nu != 2 || P.nstage != 2 || !is_default_signature<NY>(P)) return false;
+    if (P.wide || P.nD != NY || P.p != PN || P.nu != 2 || P.nstage != 2 || !is_default_signature<NY>(P)) return false;
     for (int k = 0; k < NY; ++k)
         if (P.D_stage[k] == -2) return false;
     MGB_REQUIRE(P.leaf_desc && P.leaf_arena && P.leaf_g && P.leaf_status, "condensing f2: leaf arguments missing");
@@ -1734,6 +1929,49 @@ static bool try_f01_fast(const ElemParams& P, hipStream_t st) {
     return true;
 }
 
+size_t wide_lds_bytes(int p, int nu, int nD, int nstage, int mode) {
+    const int G = elem_group(p);
+    const int threads = (mode == MODE_F2) ? WIDE_F2_THREADS : 256;
+    const int EPB = threads / G;
+    size_t d = (size_t)threads * nu + (size_t)nstage * EPB * p * p;
+    if (mode == MODE_F1 || mode == MODE_F01) d += (size_t)threads * nD;
+    if (mode == MODE_F2) d += (size_t)threads * (nD * (nD + 1) / 2);
+    if (d < 256) d = 256;
+    return d * sizeof(double);
+}
+
+static void launch_elem_wide(const ElemParams& P, int mode, hipStream_t st) {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const int big = 160 * 1024;
+        (void)hipFuncSetAttribute((const void*)elem_wide_kernel<MODE_F0>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)elem_wide_kernel<MODE_F1>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)elem_wide_kernel<MODE_F2>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)elem_wide_kernel<MODE_NODE_F>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)elem_wide_kernel<MODE_NODE_SLACK>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)elem_wide_kernel<MODE_F01>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipGetLastError();
+    });
+    const int G = elem_group(P.p);
+    int lgG = 0;
+    while ((1 << lgG) < G) ++lgG;
+    const int threads = (mode == MODE_F2) ? WIDE_F2_THREADS : 256;
+    const int EPB = threads / G;
+    const dim3 grid((unsigned)((P.N + EPB - 1) / EPB)), blk((unsigned)threads);
+    const size_t lds = wide_lds_bytes(P.p, P.nu, P.nD, P.nstage, mode);
+    MGB_REQUIRE(lds <= 160 * 1024, "wide element kernel LDS budget exceeded");
+    switch (mode) {
+        case MODE_F0: hipLaunchKernelGGL((elem_wide_kernel<MODE_F0>), grid, blk, lds, st, P, lgG); break;
+        case MODE_F1: hipLaunchKernelGGL((elem_wide_kernel<MODE_F1>), grid, blk, lds, st, P, lgG); break;
+        case MODE_F2: hipLaunchKernelGGL((elem_wide_kernel<MODE_F2>), grid, blk, lds, st, P, lgG); break;
+        case MODE_NODE_F: hipLaunchKernelGGL((elem_wide_kernel<MODE_NODE_F>), grid, blk, lds, st, P, lgG); break;
+        case MODE_NODE_SLACK: hipLaunchKernelGGL((elem_wide_kernel<MODE_NODE_SLACK>), grid, blk, lds, st, P, lgG); break;
+        case MODE_F01: hipLaunchKernelGGL((elem_wide_kernel<MODE_F01>), grid, blk, lds, st, P, lgG); break;
+        default: throw InvalidArgument("launch_elem: bad mode");
+    }
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
 void launch_elem(const ElemParams& P, int mode, hipStream_t st) {
     if (P.p > 64) {      // one dense spectral element: GEMV + node kernel path (dense.hip)
         launch_dense_eval(P, mode, st);
@@ -1741,6 +1979,11 @@ void launch_elem(const ElemParams& P, int mode, hipStream_t st) {
     }
     MGB_REQUIRE(P.p >= 1 && P.p <= 64, "element kernels support 1 <= p <= 64 nodes per element");
     MGB_REQUIRE(P.nD >= 1 && P.nD <= MGBHIP_MAX_ND, "nD out of range");
+    if (P.wide) {
+        launch_elem_wide(P, mode, st);
+        return;
+    }
+    MGB_REQUIRE(P.nD <= 10, "narrow element kernels: nD out of range");
     if (mode == MODE_F2) {
         // compile-time specialisations for the discretisations of the BASELINE configs
         // (fem1d, fem2d_P2 with/without bubble, fem3d Q1) and their phase-I images

@@ -55,7 +55,11 @@ struct ElemParams {
     // that materialises it runs BEHIND this evaluation instead of in front of it, off the host round trip's critical path)
     const double* zx;
     double zalpha;
+    // wide path (mgbhip_problem::wide, chosen once at upload): more than 10 D rows or a Euclidean-power piece wider than
+    // NARROW_W -- launch_elem and launch_dense_eval run the wide kernels (elem_wide_kernel, dense_node_wide_kernel)
+    int32_t wide;
 };
+static_assert(sizeof(ElemParams) <= 4096 - 64, "ElemParams must stay well inside the kernel argument limit");
 
 // Fine-level Newton systems: H of the default problem couples the p broken slack unknowns of an element (diagonal
 // H_ss because D_s = id) and its interior u unknown (the bubble) to the element's own nodes only -- the leaf fronts of
@@ -82,6 +86,10 @@ inline int64_t hel_layout(int nu, int64_t N, int p, int diag_mask, int64_t* off)
 }
 
 int elem_group(int p);                                   // lanes per element (power of two >= p)
+// wide path: threads per workgroup of the element Hessian kernel (the other modes run 256, like the narrow kernels, so
+// that f0's workgroup partials keep their count elem_grid(p, N)) and the LDS it needs
+constexpr int WIDE_F2_THREADS = 128;
+size_t wide_lds_bytes(int p, int nu, int nD, int nstage, int mode);
 int64_t elem_grid(int p, int64_t N);                     // workgroups
 size_t elem_lds_bytes(const ElemParams& P, int mode);
 void launch_elem(const ElemParams& P, int mode, hipStream_t st);

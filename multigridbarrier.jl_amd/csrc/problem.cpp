@@ -141,6 +141,10 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         }
         P->store->w.upload(d->w, (size_t)P->n, st);
     }
+    // wide path (kernels.hip: elem_wide_kernel): chosen once here, from the D rows and the piece widths
+    P->wide = d->nD > 10;
+    for (int k = 0; k < d->cone.npieces && k < MGBHIP_MAX_PIECES; ++k)
+        if (d->cone.pieces[k].kind == MGBHIP_KIND_EP && d->cone.pieces[k].ni > NARROW_W) P->wide = true;
     // D table + LDS staging decision
     P->nstage = 0;
     int slot_of_op[MGBHIP_MAX_OPS];
@@ -159,7 +163,9 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
             // ... and the whole f2 working set (operators + broken values + nD(nD+1)/2 node weights
             // per lane) fits the 160 KB of a CU
             size_t bytes = (size_t)(P->nstage + 1) * EPB * P->p * P->p * sizeof(double);
-            const size_t f2_total = bytes + 256 * sizeof(double) * (size_t)(d->nu + d->nD * (d->nD + 1) / 2);
+            size_t f2_total = bytes + 256 * sizeof(double) * (size_t)(d->nu + d->nD * (d->nD + 1) / 2);
+            if (P->wide)    // the wide Hessian kernel runs WIDE_F2_THREADS lanes per workgroup
+                f2_total = wide_lds_bytes(P->p, d->nu, d->nD, P->nstage + 1, MODE_F2);
             if (!P->dense && bytes <= 64 * 1024 && f2_total <= 150 * 1024) {
                 slot_of_op[o] = P->nstage;
                 P->stage_ptr[P->nstage++] = P->store->ops[o].p;
@@ -198,11 +204,14 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         const mgbhip_piece& s = C.pieces[k];
         PieceDev& t = P->cone.pc[k];
         MGB_REQUIRE(s.kind == MGBHIP_KIND_EP || s.kind == MGBHIP_KIND_LINEAR, "unknown functor family");
-        MGB_REQUIRE(s.ni >= 1 && s.ni <= MGBHIP_MAX_IDX, "functor index list too long for this build");
+        MGB_REQUIRE(s.ni >= 1 && s.ni <= MGBHIP_MAX_IDX, "functor index list too long for this build (MGBHIP_MAX_IDX)");
         t.kind = s.kind;
         t.ni = s.ni;
         t.nc = (s.kind == MGBHIP_KIND_EP) ? s.ni : s.nc;
-        MGB_REQUIRE(t.nc >= 1 && t.nc <= MGBHIP_MAX_IDX, "functor constraint count too large for this build");
+        MGB_REQUIRE(t.nc >= 1, "functor constraint count must be positive");
+        if (s.kind == MGBHIP_KIND_LINEAR)
+            MGB_REQUIRE(s.ni <= MGBHIP_MAX_LIN && t.nc <= MGBHIP_MAX_LIN,
+                        "linear piece exceeds MGBHIP_MAX_LIN (4 constraint rows on 4 indexed rows)");
         if (s.kind == MGBHIP_KIND_EP) MGB_REQUIRE(s.ni >= 2, "Euclidean power cone needs nz >= 2");
         for (int c = 0; c < MGBHIP_MAX_IDX; ++c) {
             t.idx[c] = c < s.ni ? s.idx[c] : 0;
@@ -719,6 +728,7 @@ ElemParams mgbhip_problem::base_params(int level, const double* d_s, const doubl
     ElemParams E;
     std::memset(&E, 0, sizeof(E));
     E.p = p; E.nu = nu; E.nD = nD; E.nstage = nstage; E.N = N; E.n = n;
+    E.wide = wide ? 1 : 0;
     E.ymask = 0;
     for (int k = 0; k < cone.npieces; ++k)
         for (int c = 0; c < cone.pc[k].ni; ++c) E.ymask |= 1 << cone.pc[k].idx[c];

@@ -100,6 +100,7 @@ struct mgbhip_problem {
     int64_t N = 0, n = 0;
     int32_t diag_mask_sel = 0;             // element blocks that are diagonal (identity-only states), compact on selection levels
     bool dense = false;                    // one dense spectral element (p > 64): dense.hip path
+    bool wide = false;                     // wide path (nD > 10 or a power cone wider than NARROW_W): chosen at upload
     std::shared_ptr<mgbhip::OpStore> store;
     int32_t D_state[MGBHIP_MAX_ND], D_op[MGBHIP_MAX_ND], D_stage[MGBHIP_MAX_ND];
     int32_t nstage = 0;

@@ -24,7 +24,8 @@ from .convex import KIND_EP, KIND_LINEAR, Convex
 from .multigrid import AMG
 from .problem import MGBProblem
 
-MAX_PIECES, MAX_IDX, MAX_ND, MAX_NU, MAX_OPS = 4, 4, 10, 4, 8
+MAX_PIECES, MAX_IDX, MAX_ND, MAX_NU, MAX_OPS = 4, 10, 13, 4, 8
+MAX_LIN = 4        # linear pieces: constraint rows and indexed rows (include/mgbhip.h MGBHIP_MAX_LIN)
 OK, ERR_INVALID, ERR_HIP, ERR_NOT_SPD, ERR_NONFINITE, ERR_CONVERGENCE = range(6)
 
 
@@ -326,8 +327,12 @@ class DeviceProblem:
         self.p, self.N, self.n = p, N, p * N
         self.nu = first.nu
         self.nD = len(M.D_fine)
-        if self.nD > MAX_ND or self.nu > MAX_NU:
-            raise ValueError("problem exceeds the compiled MAX_ND / MAX_NU")
+        if self.nu > MAX_NU:
+            what = "the phase-I (feasibility) problem" if feasibility else "the problem"
+            raise ValueError(f"{what} has {self.nu} state components; this build supports at most MAX_NU = {MAX_NU} "
+                             "(a 3-D vector problem needs a feasible start: phase I would need one state more)")
+        if self.nD > MAX_ND:
+            raise ValueError(f"problem has {self.nD} D rows; this build supports at most MAX_ND = {MAX_ND}")
         keep: List[np.ndarray] = []
         d = _Desc()
         d.p, d.N, d.nu, d.nD = p, N, self.nu, self.nD
@@ -383,8 +388,11 @@ class DeviceProblem:
             P.kind = pc.kind
             P.ni = pc.ni
             P.nc = pc.nc
-            if pc.ni > MAX_IDX or pc.nc > MAX_IDX:
-                raise ValueError("functor family size exceeds this build (MAX_IDX)")
+            if pc.kind == KIND_EP and pc.ni > MAX_IDX:
+                raise ValueError(f"Euclidean-power piece of width {pc.ni} exceeds this build (MAX_IDX = {MAX_IDX})")
+            if pc.kind == KIND_LINEAR and (pc.ni > MAX_LIN or pc.nc > MAX_LIN):
+                raise ValueError(f"linear piece with {pc.nc} row(s) on {pc.ni} indexed row(s) exceeds this build "
+                                 f"(MAX_LIN = {MAX_LIN} of each)")
             for c, i in enumerate(pc.idx):
                 P.idx[c] = int(i)
 
