@@ -274,6 +274,30 @@ int mgbhip_solver_stats(mgbhip_problem* prob, int32_t level, double* out8);
  * opaque (cuDSS FACTORIZATION + SOLVE per Newton iteration, ext/MultiGridBarrierCUDAExt/cudss_solver.jl:279-288). */
 int mgbhip_solver_chain(mgbhip_problem* prob, int32_t level, double* out8);
 
+/* ---- point evaluation (reference: `interpolate`, src/utils.jl:16-58) ---------------------------------------------
+ * out[q, c] = the element-space function with broken-basis values z[:, c] at point q, for M points pts (M x d,
+ * row-major); out is M x ncomp row-major, z is (p*N) x ncomp row-major (row e*p + i: local node i of element e).
+ *  - FEM1D       d = 1, k = degree, p = k + 1; x = the p*N node coordinates, table = the k + 1 reference nodes.
+ *                The reference's algorithm (src/TensorFEM.jl:967-1014): clamped outside [x[0], x[p*N-1]].
+ *  - QK          d = 2 or 3, p = (k + 1)^d, x (p*N) x d, table = the k + 1 reference nodes; Newton from xi = 0.
+ *  - P1 / P2     d = 2, p = 3 / 6 / 7, x (p*N) x 2, table = p x 10 coefficients of the basis over the monomials
+ *                1, l1, l2, l1^2, l1 l2, l2^2, l1^3, l1^2 l2, l1 l2^2, l2^3 (l1 = 1 at corner slot 0, l2 = 1 at the
+ *                next corner slot, the third corner is the origin).
+ *  - SPECTRAL1D  d = 1, k = n - 1, p = n, N = 1, z = Chebyshev coefficients (n x ncomp), x and table unused.
+ *  - SPECTRAL2D  d = 2, k = n - 1, p = n*n, N = 1, z row i*n + j = C[i, j] (value = bx' C by), x and table unused.
+ * 2-D / 3-D FEM: a point outside every element (or with a non-finite coordinate) gives NaN and elem -1; a point in
+ * several elements takes the lowest element index.  elem (M, may be NULL) receives the element used.  M = 0 is a
+ * no-op; N = 0 is MGBHIP_ERR_INVALID.  Host pointers; the work runs on ctx's stream and is complete on return.   */
+#define MGBHIP_INTERP_FEM1D 1
+#define MGBHIP_INTERP_QK 2
+#define MGBHIP_INTERP_P1 3
+#define MGBHIP_INTERP_P2 4
+#define MGBHIP_INTERP_SPECTRAL1D 5
+#define MGBHIP_INTERP_SPECTRAL2D 6
+int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                       const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
+                       const double* pts, double* out, int32_t* elem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
 #include <memory>
 #include <string>
 
+#include "interpolate.hpp"
 #include "problem.hpp"
 
 using namespace mgbhip;
@@ -634,6 +635,60 @@ int mgbhip_reset_stage_timers(mgbhip_problem* P, int enable) {
     MGB_API_BEGIN_ON(P)
     MGB_REQUIRE(P, "null argument");
     P->ctx->timers.reset(enable != 0);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                       const double* table, int32_t ncomp, const double* z, int64_t M, const double* pts, double* out,
+                       int32_t* elem) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(N > 0, "interpolate: no elements (N = 0)");
+    MGB_REQUIRE(M >= 0 && ncomp >= 1 && p >= 1, "interpolate: bad sizes");
+    MGB_REQUIRE(z != nullptr && (M == 0 || (pts != nullptr && out != nullptr)), "null argument");
+    InterpIn in;
+    in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.ncomp = ncomp; in.M = M;
+    in.x = x; in.table = table; in.z = z; in.pts = pts; in.out = out; in.elem = elem;
+    const bool fem = family >= MGBHIP_INTERP_FEM1D && family <= MGBHIP_INTERP_P2;
+    if (fem) {
+        MGB_REQUIRE(x != nullptr && table != nullptr, "interpolate: FEM families need node coordinates and a table");
+        MGB_REQUIRE(k >= 1 && k <= INTERP_MAX_DEGREE, "interpolate: element degree out of range");
+    }
+    switch (family) {
+        case MGBHIP_INTERP_FEM1D:
+            MGB_REQUIRE(d == 1 && p == k + 1, "interpolate: fem1d needs d = 1, p = k + 1");
+            in.table_len = k + 1;
+            for (int64_t e = 1; e < N && in.sorted; ++e) in.sorted = x[e * p] >= x[(e - 1) * p];
+            break;
+        case MGBHIP_INTERP_QK: {
+            MGB_REQUIRE(d == 2 || d == 3, "interpolate: Q_k needs d = 2 or 3");
+            int64_t s = 1;
+            for (int a = 0; a < d; ++a) s *= k + 1;
+            MGB_REQUIRE(p == s, "interpolate: Q_k needs p = (k + 1)^d");
+            in.table_len = k + 1;
+            break;
+        }
+        case MGBHIP_INTERP_P1:
+        case MGBHIP_INTERP_P2:
+            MGB_REQUIRE(d == 2, "interpolate: triangles need d = 2");
+            MGB_REQUIRE(family == MGBHIP_INTERP_P1 ? p == 3 : (p == 6 || p == 7), "interpolate: bad nodes per triangle");
+            in.table_len = (int64_t)p * 10;
+            break;
+        case MGBHIP_INTERP_SPECTRAL1D:
+            MGB_REQUIRE(d == 1 && N == 1 && k >= 0 && p == k + 1, "interpolate: spectral1d needs d = 1, N = 1, p = n");
+            in.table = nullptr;
+            break;
+        case MGBHIP_INTERP_SPECTRAL2D:
+            MGB_REQUIRE(d == 2 && N == 1 && k >= 0 && (int64_t)p == (int64_t)(k + 1) * (k + 1),
+                        "interpolate: spectral2d needs d = 2, N = 1, p = n^2");
+            in.table = nullptr;
+            break;
+        default:
+            throw InvalidArgument("interpolate: unknown family");
+    }
+    MGB_REQUIRE((int64_t)p * N < (int64_t)INT32_MAX && M < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
+    interpolate_run(in, ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }

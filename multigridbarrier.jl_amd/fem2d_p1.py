@@ -44,6 +44,16 @@ def refine_table() -> np.ndarray:
     return _REFINE.copy()
 
 
+def basis_coefficient_table() -> np.ndarray:
+    """(3, 10): the nodal basis over the monomials of `fem2d_p2.MONOMIALS` in (l1, l2), where l1 = 1 at corner slot 0,
+    l2 = 1 at corner slot 1 and corner slot 2 is the origin: phi_0 = l1, phi_1 = l2, phi_2 = 1 - l1 - l2."""
+    T = np.zeros((3, 10))
+    T[0, 1] = 1.0
+    T[1, 2] = 1.0
+    T[2, :3] = (1.0, -1.0, -1.0)
+    return T
+
+
 def _operators(X: np.ndarray):
     """Element blocks of d/dx, d/dy and the quadrature weights (reference: src/fem2d_P1.jl:266-297): on a triangle with
     corners 1, 2, 3 and det = (x2 - x1)(y3 - y1) - (x3 - x1)(y2 - y1), every row of the 3 x 3 block is (b_j / det) resp.

@@ -96,13 +96,17 @@ def _solve_exact(A, B):
 
 
 _REF_CACHE: Dict[bool, dict] = {}
+_BASIS_CACHE: Dict[bool, list] = {}
+
+# the monomials l1^i l2^j of degree <= 3 over which `basis_coefficient_table` expands the basis
+MONOMIALS = ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3))
 
 
-def reference_triangle(bubble: bool = True) -> dict:
-    """K (V x 3), w (V), dx, dy (V x V) of the reference element, as float64 arrays
-    (reference: src/fem2d_P2.jl:74-96 and :109-128 tabulate the same quantities)."""
-    if bubble in _REF_CACHE:
-        return _REF_CACHE[bubble]
+def _nodal_basis(bubble: bool) -> list:
+    """The nodal basis of span{P2} (+) span{l1 l2 l3} on the 7 (or 6) nodes in exact rational arithmetic: one
+    polynomial {(i, j): coefficient of x^i y^j} per node, with reference coordinates x = l1, y = l2."""
+    if bubble in _BASIS_CACHE:
+        return _BASIS_CACHE[bubble]
     nodes = _bary_nodes(bubble)
     V = len(nodes)
     one = Fraction(1)
@@ -123,12 +127,31 @@ def reference_triangle(bubble: bool = True) -> dict:
             for key, c in mons[m].items():
                 pj[key] = pj.get(key, 0) + coef[m][j] * c
         basis.append(pj)
+    _BASIS_CACHE[bubble] = basis
+    return basis
+
+
+def reference_triangle(bubble: bool = True) -> dict:
+    """K (V x 3), w (V), dx, dy (V x V) of the reference element, as float64 arrays
+    (reference: src/fem2d_P2.jl:74-96 and :109-128 tabulate the same quantities)."""
+    if bubble in _REF_CACHE:
+        return _REF_CACHE[bubble]
+    nodes = _bary_nodes(bubble)
+    V = len(nodes)
+    basis = _nodal_basis(bubble)
     dx = np.array([[float(_poly_eval(_poly_diff(basis[j], 0), nd[0], nd[1])) for j in range(V)] for nd in nodes])
     dy = np.array([[float(_poly_eval(_poly_diff(basis[j], 1), nd[0], nd[1])) for j in range(V)] for nd in nodes])
     w = np.array([float(2 * _poly_int(basis[j])) for j in range(V)])
     K = np.array([[float(v) for v in nd] for nd in nodes])
     _REF_CACHE[bubble] = dict(K=K, w=w, dx=dx, dy=dy)
     return _REF_CACHE[bubble]
+
+
+def basis_coefficient_table(bubble: bool = True) -> np.ndarray:
+    """(V, 10): row j holds the coefficients of phi_j over `MONOMIALS` in (l1, l2), where l1 = 1 at corner slot 0,
+    l2 = 1 at corner slot 2 and corner slot 4 is the origin (the table `interpolate` hands the device)."""
+    basis = _nodal_basis(bubble)
+    return np.array([[float(pj.get(mono, 0)) for mono in MONOMIALS] for pj in basis])
 
 
 # child corner slots of the four red-refinement children, as parent local slots

@@ -1,0 +1,162 @@
+"""Point evaluation of a solution: `interpolate(geom, z, t)` (reference: src/utils.jl:16-58).
+
+The reference covers 1-D Q_k FEM (src/TensorFEM.jl:957-1014), `spectral1d` (src/spectral1d.jl:140-170) and `spectral2d`
+(src/spectral2d.jl:85-125); this module also covers the 2-D and 3-D element families (Q_k, P1, P2), which the reference
+does not.  Every evaluation runs on the device in one call of `mgbhip_interpolate` (csrc/interpolate.hip); the host
+only checks arguments, builds the small basis tables and, for the spectral families, forms the Chebyshev coefficients
+exactly as the reference does (`evaluation(x, n) \\ z`).  Arguments are checked before any device work.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import fem2d_p1, fem2d_p2
+from .fem2d_p1 import FEM2D_P1
+from .fem2d_p2 import FEM2D_P2
+from .multigrid import Geometry
+from .spectral import SPECTRAL1D, SPECTRAL2D, evaluation
+from .tensorfem import TensorFEM, _tf_nodes
+
+# include/mgbhip.h MGBHIP_INTERP_*
+FEM1D, QK, P1, P2, SPECTRAL_1D, SPECTRAL_2D = range(1, 7)
+MAX_DEGREE = 8          # csrc/interpolate.hpp INTERP_MAX_DEGREE
+
+
+def _c_f64(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _spectral1d_coefficients(geom: Geometry, Z: np.ndarray) -> np.ndarray:
+    """c = evaluation(x, n) \\ z, column by column (src/spectral1d.jl:140-150)."""
+    x = geom.xflat[:, 0]
+    V = evaluation(x, len(x))
+    return np.stack([np.linalg.solve(V, Z[:, j]) for j in range(Z.shape[1])], axis=1)
+
+
+def _spectral2d_coefficients(geom: Geometry, Z: np.ndarray) -> np.ndarray:
+    """C = V \\ reshape(z, n, n) / V', column by column (src/spectral2d.jl:85-92); row i*n + j of the result is C[i, j]."""
+    n = geom.discretization.n
+    V = evaluation(geom.xflat[:n, 0], n)
+    cols = []
+    for j in range(Z.shape[1]):
+        Y = np.linalg.solve(V, Z[:, j].reshape(n, n, order="F"))
+        Cm = np.linalg.solve(V, Y.T).T                 # Y / V'  =  (V \\ Y')'
+        cols.append(Cm.reshape(-1))
+    return np.stack(cols, axis=1)
+
+
+def _check_p2_straight(x: np.ndarray, bubble: bool) -> None:
+    RK = fem2d_p2.reference_triangle(bubble)["K"]
+    straight = np.einsum("vc,ced->ved", RK, x[[0, 2, 4], :, :])
+    tol = 1e-12 * max(1.0, float(np.abs(x).max()))
+    if not np.all(np.abs(straight - x) <= tol):
+        raise ValueError("fem2d_P2 interpolation needs straight elements: every edge node at its edge's midpoint"
+                         + (" and the bubble node at the centroid" if bubble else ""))
+
+
+def _plan(geom: Geometry):
+    """(family, name, d, k, p, N, node coordinates or None, table or None) of a geometry; ValueError if unsupported."""
+    disc = geom.discretization
+    if isinstance(disc, TensorFEM):
+        if disc.e != disc.d:
+            raise ValueError(f"interpolate: embedded manifolds (TensorFEM with d = {disc.d} < e = {disc.e}) are not "
+                             "supported")
+        if not 1 <= disc.k <= MAX_DEGREE:
+            raise ValueError(f"interpolate: element degree k = {disc.k} is outside 1..{MAX_DEGREE}")
+        p, N, d = geom.x.shape
+        return (FEM1D if d == 1 else QK), f"fem{d}d", d, disc.k, p, N, geom.xflat, _tf_nodes(disc.k)
+    if isinstance(disc, FEM2D_P1):
+        p, N, _ = geom.x.shape
+        return P1, "fem2d_P1", 2, 1, p, N, geom.xflat, fem2d_p1.basis_coefficient_table()
+    if isinstance(disc, FEM2D_P2):
+        p, N, _ = geom.x.shape
+        _check_p2_straight(geom.x, p == 7)
+        return P2, "fem2d_P2", 2, 2, p, N, geom.xflat, fem2d_p2.basis_coefficient_table(p == 7)
+    if isinstance(disc, SPECTRAL1D):
+        n = len(geom.w)
+        return SPECTRAL_1D, "spectral1d", 1, n - 1, n, 1, None, None
+    if isinstance(disc, SPECTRAL2D):
+        n = disc.n
+        return SPECTRAL_2D, "spectral2d", 2, n - 1, n * n, 1, None, None
+    raise ValueError(f"interpolate: no method for {type(disc).__name__} geometries")
+
+
+def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool = False):
+    """Evaluate the element-space function with broken-basis values `z` at the points `t`.
+
+    `z` is `(p*N,)` in `geom.xflat` row order (a column of `sol.z`), or `(p*N, k)`: the result then has a trailing axis
+    of `k`, each column bitwise what a 1-column call returns.  1-D geometries take a scalar `t` (scalar result) or an
+    array (result of the same shape); 2-D and 3-D ones take `(M, d)` points (result `(M,)`) or one point `(d,)`
+    (scalar).
+
+    - fem1d: the reference's algorithm (src/TensorFEM.jl:967-1014), clamped outside the mesh: `t <= x[0]` gives the
+      first value, `t >= x[-1]` the last (also for +-Inf); NaN gives NaN.
+    - fem2d / fem3d (Q_k), fem2d_P1, fem2d_P2 (straight elements): the element map of the lowest-index element that
+      contains the point (within a 1e-11 tolerance in reference coordinates) is inverted and the element's basis
+      evaluated; a point outside the mesh, or with a NaN or Inf coordinate, gives NaN.
+    - spectral1d / spectral2d: the Chebyshev interpolant of the reference, not clamped; a non-finite point gives NaN.
+
+    With `return_element=True` the result is `(values, elements)`: the int32 element used per point (-1: none; the
+    spectral families report 0).
+    """
+    family, name, d, k, p, N, xnodes, table = _plan(geom)
+    Z = np.asarray(z, dtype=np.float64)
+    if Z.ndim not in (1, 2):
+        raise ValueError(f"interpolate: z must be a vector or a matrix (got {Z.ndim} dimensions)")
+    single = Z.ndim == 1
+    Z = Z.reshape(Z.shape[0], -1)
+    if Z.shape[0] != p * N:
+        raise ValueError(f"{name} interpolation needs {p * N} values (got {Z.shape[0]})")
+    if Z.shape[1] < 1:
+        raise ValueError("interpolate: z has no columns")
+    if N == 0:
+        raise ValueError(f"{name} interpolation needs at least one element")
+    T = np.asarray(t, dtype=np.float64)
+    if d == 1:
+        scalar = T.ndim == 0
+        shape = T.shape
+        pts = T.reshape(-1, 1)
+    else:
+        if T.ndim == 1 and T.shape[0] == d:
+            scalar, shape = True, ()
+            pts = T.reshape(1, d)
+        elif T.ndim == 2 and T.shape[1] == d:
+            scalar, shape = False, (T.shape[0],)
+            pts = T
+        else:
+            raise ValueError(f"{name} interpolation points must form an M-by-{d} array (got shape {T.shape})")
+    if xnodes is not None and not np.all(np.isfinite(xnodes)):
+        raise ValueError(f"{name} interpolation: the mesh has non-finite node coordinates")
+    if family == SPECTRAL_1D:
+        Zd = _spectral1d_coefficients(geom, Z)
+    elif family == SPECTRAL_2D:
+        Zd = _spectral2d_coefficients(geom, Z)
+    else:
+        Zd = Z
+    M, ncomp = pts.shape[0], Z.shape[1]
+    out = np.empty((M, ncomp))
+    elem = np.empty(M, dtype=np.int32)
+    if M:
+        from .device import HipContext, _check, _ptr
+        Zd, pts = _c_f64(Zd), _c_f64(pts)
+        xnodes = None if xnodes is None else _c_f64(xnodes)
+        table = None if table is None else _c_f64(table)
+        ctx = HipContext(device_id)
+        try:
+            _check(ctx.lib, ctx.lib.mgbhip_interpolate(
+                ctx.handle, family, d, k, p, N, _ptr(xnodes), _ptr(table), ncomp, _ptr(Zd), M, _ptr(pts),
+                _ptr(out), elem.ctypes.data_as(C.POINTER(C.c_int32))))
+        finally:
+            ctx.close()
+    vals = out[:, 0] if single else out
+    if scalar:
+        vals = vals[0] if single else vals[0].copy()
+        if single:
+            vals = float(vals)
+        elem_out = int(elem[0])
+    else:
+        vals = vals.reshape(shape + (() if single else (ncomp,)))
+        elem_out = elem.reshape(shape)
+    return (vals, elem_out) if return_element else vals
