@@ -297,6 +297,22 @@ int mgbhip_solver_chain(mgbhip_problem* prob, int32_t level, double* out8);
 int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
                        const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
                        const double* pts, double* out, int32_t* elem);
+/* The same evaluation with the gradient with respect to x: grad[q, c, a] = d/dx_a of component c at point q (M x ncomp
+ * x d, row-major; d = 1: M x ncomp).  Arguments, layouts and checks are those of mgbhip_interpolate; out (M x ncomp)
+ * may be NULL, and where given it is bitwise what mgbhip_interpolate returns; grad == NULL is MGBHIP_ERR_INVALID.
+ *  - QK          grad = J^{-T} sum_i grad_xi phi_i(xi) z_i at the located xi, J the Jacobian of the element map there
+ *                (curved elements included).
+ *  - P1 / P2     the monomial table differentiated in (l1, l2), mapped by the inverse transpose of the two edge vectors.
+ *  - FEM1D       the derivative of the element's Lagrange interpolant over dx/dxi.  Values are clamped outside
+ *                [x[0], x[p*N-1]], so the derivative there is 0.0 (also at +-Inf); at the two end points it is the
+ *                one-sided derivative of the end element; NaN gives NaN.
+ *  - SPECTRAL*   the derivative of the Chebyshev sums by the recurrence for T_n' (finite at +-1); 2-D: both partials.
+ * A point that gets NaN for its value gets NaN in every gradient entry.  The gradient is discontinuous across element
+ * faces: a point on a shared face reports the gradient of the lowest-index element, the one its value comes from. */
+int mgbhip_interpolate_grad(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                            const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
+                            const double* pts, double* out /* M x ncomp, may be NULL */,
+                            double* grad /* M x ncomp x d */, int32_t* elem /* M or NULL */);
 
 #ifdef __cplusplus
 }

@@ -463,6 +463,29 @@ function hip_mgb_driver(img::HIPImage{T}, f::Matrix{T}, g::Matrix{T}, Q::Convex{
 end
 # `mgb_solve` calls mgb_driver(prob.M, prob.f, prob.g, prob.Q; …) (src/mgb.jl:831): prob.M is the HIPImage.
 
+# Values and gradients of an element-space function at points (mgbhip_interpolate_grad; include/mgbhip.h lists the
+# families and layouts).  x is (p*N) x d and z is (p*N) x ncomp in the reference's row order, pts is M x d; Julia arrays
+# are column-major, so the transposes hand the library its row-major images.  Returns (values M x ncomp,
+# gradients M x ncomp x d).  A point on a shared face reports the lowest-index element's gradient, as for its value.
+function hip_interpolate_grad(family::Integer, d::Integer, k::Integer, p::Integer, N::Integer, x::Matrix{Float64},
+                              table::Vector{Float64}, z::Matrix{Float64}, pts::Matrix{Float64})
+    M, ncomp = size(pts, 1), size(z, 2)
+    xt, zt, pt = permutedims(x), permutedims(z), permutedims(pts)
+    out = Matrix{Float64}(undef, ncomp, M)
+    grad = Array{Float64,3}(undef, d, ncomp, M)
+    ctx = Ref{Ptr{Cvoid}}()
+    check(@ccall libmgbhip.mgbhip_create(ctx::Ptr{Ptr{Cvoid}}, 0::Cint, C_NULL::Ptr{Cvoid})::Cint)
+    try
+        check(@ccall libmgbhip.mgbhip_interpolate_grad(ctx[]::Ptr{Cvoid}, family::Int32, d::Int32, k::Int32, p::Int32,
+                                                       N::Int64, xt::Ptr{Float64}, table::Ptr{Float64}, ncomp::Int32,
+                                                       zt::Ptr{Float64}, M::Int64, pt::Ptr{Float64}, out::Ptr{Float64},
+                                                       grad::Ptr{Float64}, C_NULL::Ptr{Int32})::Cint)
+    finally
+        @ccall libmgbhip.mgbhip_destroy(ctx[]::Ptr{Cvoid})::Cint
+    end
+    permutedims(out), permutedims(grad, (3, 2, 1))
+end
+
 function __init__()                                                 # like the CUDA extension's __init__ (:26-30)
     ctx = Ref{Ptr{Cvoid}}()
     try

@@ -639,17 +639,18 @@ int mgbhip_reset_stage_timers(mgbhip_problem* P, int enable) {
     MGB_API_END
 }
 
-int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
-                       const double* table, int32_t ncomp, const double* z, int64_t M, const double* pts, double* out,
-                       int32_t* elem) {
-    MGB_API_BEGIN_ON(ctx)
+// the argument checks and the run shared by mgbhip_interpolate (grad = NULL) and mgbhip_interpolate_grad
+static void interpolate_checked(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                                const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
+                                const double* pts, double* out, double* grad, int32_t* elem) {
+    const bool need_out = grad == nullptr;      // the gradient entry may leave the values out
     MGB_REQUIRE(ctx != nullptr, "null context");
     MGB_REQUIRE(N > 0, "interpolate: no elements (N = 0)");
     MGB_REQUIRE(M >= 0 && ncomp >= 1 && p >= 1, "interpolate: bad sizes");
-    MGB_REQUIRE(z != nullptr && (M == 0 || (pts != nullptr && out != nullptr)), "null argument");
+    MGB_REQUIRE(z != nullptr && (M == 0 || (pts != nullptr && (out != nullptr || !need_out))), "null argument");
     InterpIn in;
     in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.ncomp = ncomp; in.M = M;
-    in.x = x; in.table = table; in.z = z; in.pts = pts; in.out = out; in.elem = elem;
+    in.x = x; in.table = table; in.z = z; in.pts = pts; in.out = out; in.grad = grad; in.elem = elem;
     const bool fem = family >= MGBHIP_INTERP_FEM1D && family <= MGBHIP_INTERP_P2;
     if (fem) {
         MGB_REQUIRE(x != nullptr && table != nullptr, "interpolate: FEM families need node coordinates and a table");
@@ -688,7 +689,25 @@ int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, in
             throw InvalidArgument("interpolate: unknown family");
     }
     MGB_REQUIRE((int64_t)p * N < (int64_t)INT32_MAX && M < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
+    MGB_REQUIRE(M * ncomp * (grad ? d : 1) < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
     interpolate_run(in, ctx->stream);
+}
+
+int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                       const double* table, int32_t ncomp, const double* z, int64_t M, const double* pts, double* out,
+                       int32_t* elem) {
+    MGB_API_BEGIN_ON(ctx)
+    interpolate_checked(ctx, family, d, k, p, N, x, table, ncomp, z, M, pts, out, nullptr, elem);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_interpolate_grad(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                            const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
+                            const double* pts, double* out, double* grad, int32_t* elem) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(grad != nullptr, "interpolate_grad: null gradient array");
+    interpolate_checked(ctx, family, d, k, p, N, x, table, ncomp, z, M, pts, out, grad, elem);
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -1,4 +1,5 @@
-// Point evaluation of broken-basis vectors: mgbhip_interpolate (include/mgbhip.h).
+// Point evaluation of broken-basis vectors and of their gradients: mgbhip_interpolate, mgbhip_interpolate_grad
+// (include/mgbhip.h).
 //
 // reference: `interpolate`, src/utils.jl:16-58 (1-D Q_k: src/TensorFEM.jl:967-1014; spectral1d: src/spectral1d.jl:140-170;
 // spectral2d: src/spectral2d.jl:85-125).  The reference has no 2-D / 3-D FEM method; here those locate every point
@@ -222,20 +223,51 @@ __device__ inline double pick(const double (&L)[S], int j) {
     return v;
 }
 
+// inverse Jacobian (adjugate / det); false if the determinant is zero or not finite
+template <int D>
+__device__ inline bool jac_inverse(const double (&J)[D][D], double (&Ji)[D][D]) {
+    if constexpr (D == 2) {
+        const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+        if (!(det != 0.0) || !isfinite(det)) return false;
+        Ji[0][0] = J[1][1] / det;
+        Ji[0][1] = -J[0][1] / det;
+        Ji[1][0] = -J[1][0] / det;
+        Ji[1][1] = J[0][0] / det;
+    } else {
+        const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+        const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+        const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+        const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+        if (!(det != 0.0) || !isfinite(det)) return false;
+        Ji[0][0] = c00 / det;
+        Ji[1][0] = c01 / det;
+        Ji[2][0] = c02 / det;
+        Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
+        Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
+        Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
+        Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
+        Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
+        Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / det;
+    }
+    return true;
+}
+
 // Q_k element e: Newton on sum_i phi_i(xi) x_i = q from xi = 0; returns true (and the basis factors at xi) when it
-// converges to a point of [-1, 1]^D within the containment tolerance.  Node lin = i0 + S i1 (+ S^2 i2), axis 0
-// fastest; axis 0 is unrolled, the outer axes are loops that pick their basis factor without run-time register indexing.
+// converges to a point of [-1, 1]^D within the containment tolerance; xi is that point.  Node lin = i0 + S i1 (+ S^2 i2),
+// axis 0 fastest; axis 0 is unrolled, the outer axes are loops that pick their basis factor without run-time register
+// indexing.
 template <int D, int S>
 __device__ bool qk_locate(const double* __restrict__ x, int64_t e, const double* nodes, const double* q,
-                          double (&L)[D][S]) {
+                          double (&L)[D][S], double (&xi)[D]) {
     constexpr int P = D == 2 ? S * S : S * S * S;
-    double xi[D], dL[D][S];
+    double dL[D][S];
     for (int a = 0; a < D; ++a) xi[a] = 0.0;
     const double* xe = x + e * P * D;
     bool conv = false;
     double xs = 0.0, tol = NEWTON_STEP_TOL;
     for (int a = 0; a < D; ++a) xs = fmax(xs, fabs(q[a]));
     for (int it = 0; it < NEWTON_MAXIT && !conv; ++it) {
+#pragma unroll
         for (int a = 0; a < D; ++a) lagrange_d<S>(nodes, xi[a], L[a], dL[a]);
         double F[D], J[D][D];
         for (int a = 0; a < D; ++a) {
@@ -276,31 +308,8 @@ __device__ bool qk_locate(const double* __restrict__ x, int64_t e, const double*
                 }
             }
         }
-        // inverse Jacobian (adjugate / det)
         double Ji[D][D];
-        if constexpr (D == 2) {
-            const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-            if (!(det != 0.0) || !isfinite(det)) return false;
-            Ji[0][0] = J[1][1] / det;
-            Ji[0][1] = -J[0][1] / det;
-            Ji[1][0] = -J[1][0] / det;
-            Ji[1][1] = J[0][0] / det;
-        } else {
-            const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-            const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-            const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-            const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-            if (!(det != 0.0) || !isfinite(det)) return false;
-            Ji[0][0] = c00 / det;
-            Ji[1][0] = c01 / det;
-            Ji[2][0] = c02 / det;
-            Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-            Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
-            Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-            Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
-            Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-            Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / det;
-        }
+        if (!jac_inverse<D>(J, Ji)) return false;
         double step = 0.0, big = 0.0, ninv = 0.0;
         for (int a = 0; a < D; ++a) {
             double dx = 0.0, row = 0.0;
@@ -321,6 +330,7 @@ __device__ bool qk_locate(const double* __restrict__ x, int64_t e, const double*
     const double acc = fmax(ACCEPT_TOL, tol);
     for (int a = 0; a < D; ++a)
         if (!(fabs(xi[a]) <= 1.0 + acc)) return false;
+#pragma unroll
     for (int a = 0; a < D; ++a) lagrange<S>(nodes, xi[a], L[a]);
     return true;
 }
@@ -363,16 +373,21 @@ struct QueryArgs {
     const double* box;         // 2-D / 3-D FEM: the padded element boxes (lo then hi per element)
     const int32_t* order;      // located families: the point processed by lane i (points sorted by cell)
     double* out;
+    double* grad;              // M x ncomp x D (GRAD kernels only)
     int32_t* elem;
 };
 
-template <int D>
+// every query kernel has a compile-time GRAD flag: the GRAD = false instantiation is the value-only kernel, the
+// GRAD = true one computes the same values by the same operations and also the gradient with respect to x
+template <int D, bool GRAD>
 __device__ inline void write_nan(const QueryArgs& a, int64_t q) {
     for (int c = 0; c < a.ncomp; ++c) a.out[q * a.ncomp + c] = dnan();
+    if constexpr (GRAD)
+        for (int c = 0; c < a.ncomp * D; ++c) a.grad[q * a.ncomp * D + c] = dnan();
     if (a.elem) a.elem[q] = -1;
 }
 
-template <int D, int S>
+template <int D, int S, bool GRAD>
 __global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.M) return;
@@ -380,10 +395,10 @@ __global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
     double pt[D];
     for (int d = 0; d < D; ++d) pt[d] = a.pts[q * D + d];
     const int64_t cell = point_cell<D>(g, pt);
-    if (cell < 0) { write_nan<D>(a, q); return; }
+    if (cell < 0) { write_nan<D, GRAD>(a, q); return; }
     double nodes[S];
     for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
-    double L[D][S];
+    double L[D][S], xi[D];
     int64_t found = -1;
     const int32_t j1 = a.start[cell + 1];
     for (int32_t j = a.start[cell]; j < j1; ++j) {
@@ -391,41 +406,103 @@ __global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
         bool inbox = true;             // a point outside the element's padded box is not in the element: skip Newton
         for (int d = 0; d < D; ++d)
             inbox = inbox && pt[d] >= a.box[e * 2 * D + d] && pt[d] <= a.box[e * 2 * D + D + d];
-        if (inbox && qk_locate<D, S>(a.x, e, nodes, pt, L)) { found = e; break; }
+        if (inbox && qk_locate<D, S>(a.x, e, nodes, pt, L, xi)) { found = e; break; }
     }
-    if (found < 0) { write_nan<D>(a, q); return; }
+    if (found < 0) { write_nan<D, GRAD>(a, q); return; }
     constexpr int P = D == 2 ? S * S : S * S * S;
+    const int n2 = D == 3 ? S : 1;
+    // GRAD: the Jacobian J[a][b] = sum_i dphi_i/dxi_b x_i[a] at the located xi in one pass over the element's nodes,
+    // then per component gxi[b] = sum_i dphi_i/dxi_b z_i next to the value sum and grad = J^{-T} gxi.  The live state
+    // is that of a Newton step (L, dL, a D x D matrix, D sums), so no variant needs more registers than qk_locate.
+    double dL[GRAD ? D : 1][S], Ji[D][D];
+    if constexpr (GRAD) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) lagrange_d<S>(nodes, xi[d], L[d], dL[d]);
+        double J[D][D];
+        for (int r = 0; r < D; ++r)
+            for (int b = 0; b < D; ++b) J[r][b] = 0.0;
+        const double* xe = a.x + found * P * D;
+#pragma unroll 1
+        for (int i2 = 0; i2 < n2; ++i2) {
+            double l2 = 1.0, d2 = 0.0;
+            if constexpr (D == 3) {
+                l2 = pick<S>(L[D - 1], i2);
+                d2 = pick<S>(dL[D - 1], i2);
+            }
+#pragma unroll 1
+            for (int i1 = 0; i1 < S; ++i1) {
+                const double l1 = pick<S>(L[1], i1), d1 = pick<S>(dL[1], i1);
+#pragma unroll
+                for (int i0 = 0; i0 < S; ++i0) {
+                    const int lin = i0 + S * i1 + S * S * i2;
+                    double dphi[D];
+                    if constexpr (D == 2) {
+                        dphi[0] = dL[0][i0] * l1;
+                        dphi[1] = L[0][i0] * d1;
+                    } else {
+                        dphi[0] = dL[0][i0] * l1 * l2;
+                        dphi[1] = L[0][i0] * d1 * l2;
+                        dphi[D - 1] = L[0][i0] * l1 * d2;
+                    }
+                    for (int r = 0; r < D; ++r)
+                        for (int b = 0; b < D; ++b) J[r][b] += dphi[b] * xe[lin * D + r];
+                }
+            }
+        }
+        if (!jac_inverse<D>(J, Ji)) { write_nan<D, GRAD>(a, q); return; }
+    }
     const double* ze = a.z + found * P * a.ncomp;
     for (int c = 0; c < a.ncomp; ++c) {
-        double v = 0.0;
-        const int n2 = D == 3 ? S : 1;
+        double v = 0.0, gxi[D];
+        for (int b = 0; b < D; ++b) gxi[b] = 0.0;
 #pragma unroll 1
         for (int i2 = 0; i2 < n2; ++i2) {
             const double l2 = D == 3 ? pick<S>(L[D - 1], i2) : 1.0;
+            double d2 = 0.0;
+            if constexpr (GRAD && D == 3) d2 = pick<S>(dL[D - 1], i2);
 #pragma unroll 1
             for (int i1 = 0; i1 < S; ++i1) {
                 const double l1 = pick<S>(L[1], i1);
+                double d1 = 0.0;
+                if constexpr (GRAD) d1 = pick<S>(dL[1], i1);
 #pragma unroll
                 for (int i0 = 0; i0 < S; ++i0) {
                     const int lin = i0 + S * i1 + S * S * i2;
                     const double phi = D == 2 ? L[0][i0] * l1 : L[0][i0] * l1 * l2;
-                    v += phi * ze[lin * a.ncomp + c];
+                    const double zv = ze[lin * a.ncomp + c];
+                    v += phi * zv;
+                    if constexpr (GRAD) {
+                        if constexpr (D == 2) {
+                            gxi[0] += dL[0][i0] * l1 * zv;
+                            gxi[1] += L[0][i0] * d1 * zv;
+                        } else {
+                            gxi[0] += dL[0][i0] * l1 * l2 * zv;
+                            gxi[1] += L[0][i0] * d1 * l2 * zv;
+                            gxi[D - 1] += L[0][i0] * l1 * d2 * zv;
+                        }
+                    }
                 }
             }
         }
         a.out[q * a.ncomp + c] = v;
+        if constexpr (GRAD)
+            for (int r = 0; r < D; ++r) {
+                double s = 0.0;
+                for (int b = 0; b < D; ++b) s += Ji[b][r] * gxi[b];
+                a.grad[(q * a.ncomp + c) * D + r] = s;
+            }
     }
     if (a.elem) a.elem[q] = (int32_t)found;
 }
 
-template <int FAM>
+template <int FAM, bool GRAD>
 __global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.M) return;
     const int64_t q = a.order[i];
     const double pt[2] = {a.pts[q * 2], a.pts[q * 2 + 1]};
     const int64_t cell = point_cell<2>(g, pt);
-    if (cell < 0) { write_nan<2>(a, q); return; }
+    if (cell < 0) { write_nan<2, GRAD>(a, q); return; }
     double l1 = 0.0, l2 = 0.0;
     int64_t found = -1;
     const int32_t j1 = a.start[cell + 1];
@@ -433,7 +510,7 @@ __global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
         const int64_t e = a.cand[j];
         if (simplex_locate<FAM>(a.x, e, a.p, pt, l1, l2)) { found = e; break; }
     }
-    if (found < 0) { write_nan<2>(a, q); return; }
+    if (found < 0) { write_nan<2, GRAD>(a, q); return; }
     const double mono[10] = {1.0, l1, l2, l1 * l1, l1 * l2, l2 * l2, l1 * l1 * l1, l1 * l1 * l2, l1 * l2 * l2, l2 * l2 * l2};
     constexpr int PMAX = 7;
     double phi[PMAX];
@@ -450,23 +527,79 @@ __global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
             if (j < a.p) v += phi[j] * ze[j * a.ncomp + c];
         a.out[q * a.ncomp + c] = v;
     }
+    if constexpr (GRAD) {
+        // the ten monomials differentiated in l1 and l2; x = c2 + l1 (c0 - c2) + l2 (c1 - c2), so with the edge vectors
+        // ea, eb of simplex_locate the gradient is [ea eb]^{-T} (du/dl1, du/dl2)
+        const double m1[10] = {0.0, 1.0, 0.0, 2 * l1, l2, 0.0, 3 * (l1 * l1), 2 * (l1 * l2), l2 * l2, 0.0};
+        const double m2[10] = {0.0, 0.0, 1.0, 0.0, l1, 2 * l2, 0.0, l1 * l1, 2 * (l1 * l2), 3 * (l2 * l2)};
+        double p1[PMAX], p2[PMAX];
+        for (int j = 0; j < PMAX; ++j) {
+            double v1 = 0.0, v2 = 0.0;
+            if (j < a.p)
+                for (int m = 1; m < 10; ++m) {
+                    v1 += a.table[j * 10 + m] * m1[m];
+                    v2 += a.table[j * 10 + m] * m2[m];
+                }
+            p1[j] = v1;
+            p2[j] = v2;
+        }
+        constexpr int s0 = 0, s1 = FAM == MGBHIP_INTERP_P1 ? 1 : 2, s2 = FAM == MGBHIP_INTERP_P1 ? 2 : 4;
+        const double* xe = a.x + found * a.p * 2;
+        const double ox = xe[2 * s2], oy = xe[2 * s2 + 1];
+        const double ax = xe[2 * s0] - ox, ay = xe[2 * s0 + 1] - oy;
+        const double bx = xe[2 * s1] - ox, by = xe[2 * s1 + 1] - oy;
+        const double det = ax * by - ay * bx;
+        for (int c = 0; c < a.ncomp; ++c) {
+            double g1 = 0.0, g2 = 0.0;
+            for (int j = 0; j < PMAX; ++j)
+                if (j < a.p) {
+                    const double zv = ze[j * a.ncomp + c];
+                    g1 += p1[j] * zv;
+                    g2 += p2[j] * zv;
+                }
+            a.grad[(q * a.ncomp + c) * 2] = (by * g1 - ay * g2) / det;
+            a.grad[(q * a.ncomp + c) * 2 + 1] = (ax * g2 - bx * g1) / det;
+        }
+    }
     if (a.elem) a.elem[q] = (int32_t)found;
 }
 
-// 1-D Q_k: the reference's algorithm step for step (src/TensorFEM.jl:967-1014), 0-based
+// d/dx of the Lagrange interpolant of element e at the reference point xi: (sum_j L_j'(xi) z_j) / (sum_j L_j'(xi) x_j)
 template <int S>
+__device__ inline void fem1d_gradient(const QueryArgs& a, int64_t q, int64_t e, double xi) {
+    double nodes[S], L[S], dL[S];
+    for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
+    lagrange_d<S>(nodes, xi, L, dL);
+    double dx = 0.0;
+    for (int j = 0; j < S; ++j) dx += dL[j] * a.x[e * S + j];
+    for (int c = 0; c < a.ncomp; ++c) {
+        double v = 0.0;
+        for (int j = 0; j < S; ++j) v += dL[j] * a.z[(e * S + j) * a.ncomp + c];
+        a.grad[q * a.ncomp + c] = v / dx;
+    }
+}
+
+// 1-D Q_k: the reference's algorithm step for step (src/TensorFEM.jl:967-1014), 0-based.  GRAD: the values are clamped
+// outside [x_lo, x_hi], so the derivative there is 0; at x_lo / x_hi it is the one-sided derivative of the end element.
+template <int S, bool GRAD>
 __global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int32_t sorted) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= a.M) return;
     const double* x = a.x;
     const double t = a.pts[q];
     const int nc = a.ncomp;
-    if (isnan(t)) { write_nan<1>(a, q); return; }
+    if (isnan(t)) { write_nan<1, GRAD>(a, q); return; }
     const double x_lo = x[0], x_hi = x[(N - 1) * S + S - 1];
     if (t <= x_lo || t >= x_hi) {
         const int64_t row = t <= x_lo ? 0 : N * S - 1;
         for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[row * nc + c];
         if (a.elem) a.elem[q] = t <= x_lo ? 0 : (int32_t)(N - 1);
+        if constexpr (GRAD) {
+            if (t == x_lo) fem1d_gradient<S>(a, q, 0, -1.0);
+            else if (t == x_hi) fem1d_gradient<S>(a, q, N - 1, 1.0);
+            else
+                for (int c = 0; c < nc; ++c) a.grad[q * nc + c] = 0.0;
+        }
         return;
     }
     int64_t e;
@@ -488,11 +621,13 @@ __global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int
     double flo = xe[0] - t;
     if (flo == 0.0) {
         for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[(e * S) * nc + c];
+        if constexpr (GRAD) fem1d_gradient<S>(a, q, e, -1.0);
         return;
     }
     const double fhi = xe[S - 1] - t;
     if (fhi == 0.0) {
         for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[(e * S + S - 1) * nc + c];
+        if constexpr (GRAD) fem1d_gradient<S>(a, q, e, 1.0);
         return;
     }
     double xi = 0.0, L[S];
@@ -517,50 +652,84 @@ __global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int
         for (int j = 0; j < S; ++j) v += L[j] * a.z[(e * S + j) * nc + c];
         a.out[q * nc + c] = v;
     }
+    if constexpr (GRAD) fem1d_gradient<S>(a, q, e, xi);
 }
 
-// spectral: sum_j c_j T_j(t) (1-D) and bx' C by (2-D) with the three-term recurrence of `_chebyshev_values`
+// spectral: sum_j c_j T_j(t) (1-D) and bx' C by (2-D) with the three-term recurrence of `_chebyshev_values`; GRAD carries
+// the differentiated recurrence T_j' = 2 T_{j-1} + 2 x T_{j-1}' - T_{j-2}' next to it (finite at x = +-1)
 __device__ inline double cheb_next(double x, double tm1, double tm2) { return 2 * x * tm1 - tm2; }
+__device__ inline double cheb_d_next(double x, double tm1, double dm1, double dm2) { return 2 * tm1 + 2 * x * dm1 - dm2; }
 
+template <bool GRAD>
 __global__ void __launch_bounds__(BLOCK) query_spectral1d(QueryArgs a, int32_t n) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= a.M) return;
     const double t = a.pts[q];
-    if (!isfinite(t)) { write_nan<1>(a, q); return; }
+    if (!isfinite(t)) { write_nan<1, GRAD>(a, q); return; }
     for (int c = 0; c < a.ncomp; ++c) {
         double v = 0.0, tm2 = 0.0, tm1 = 0.0;
+        double dv = 0.0, dm2 = 0.0, dm1 = 0.0;
         for (int j = 0; j < n; ++j) {
             const double tj = j == 0 ? 1.0 : (j == 1 ? t : cheb_next(t, tm1, tm2));
-            v += a.z[(int64_t)j * a.ncomp + c] * tj;
+            const double cj = a.z[(int64_t)j * a.ncomp + c];
+            v += cj * tj;
+            if constexpr (GRAD) {
+                const double dj = j == 0 ? 0.0 : (j == 1 ? 1.0 : cheb_d_next(t, tm1, dm1, dm2));
+                dv += cj * dj;
+                dm2 = dm1;
+                dm1 = dj;
+            }
             tm2 = tm1;
             tm1 = tj;
         }
         a.out[q * a.ncomp + c] = v;
+        if constexpr (GRAD) a.grad[q * a.ncomp + c] = dv;
     }
     if (a.elem) a.elem[q] = 0;
 }
 
+template <bool GRAD>
 __global__ void __launch_bounds__(BLOCK) query_spectral2d(QueryArgs a, int32_t n) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= a.M) return;
     const double px = a.pts[q * 2], py = a.pts[q * 2 + 1];
-    if (!isfinite(px) || !isfinite(py)) { write_nan<2>(a, q); return; }
+    if (!isfinite(px) || !isfinite(py)) { write_nan<2, GRAD>(a, q); return; }
     for (int c = 0; c < a.ncomp; ++c) {
         double v = 0.0, xm2 = 0.0, xm1 = 0.0;
+        double gx = 0.0, gy = 0.0, dxm2 = 0.0, dxm1 = 0.0;
         for (int i = 0; i < n; ++i) {
             const double bx = i == 0 ? 1.0 : (i == 1 ? px : cheb_next(px, xm1, xm2));
             double r = 0.0, ym2 = 0.0, ym1 = 0.0;
+            double rd = 0.0, dym2 = 0.0, dym1 = 0.0;
             for (int j = 0; j < n; ++j) {
                 const double by = j == 0 ? 1.0 : (j == 1 ? py : cheb_next(py, ym1, ym2));
-                r += a.z[((int64_t)i * n + j) * a.ncomp + c] * by;
+                const double cij = a.z[((int64_t)i * n + j) * a.ncomp + c];
+                r += cij * by;
+                if constexpr (GRAD) {
+                    const double dby = j == 0 ? 0.0 : (j == 1 ? 1.0 : cheb_d_next(py, ym1, dym1, dym2));
+                    rd += cij * dby;
+                    dym2 = dym1;
+                    dym1 = dby;
+                }
                 ym2 = ym1;
                 ym1 = by;
             }
             v += bx * r;
+            if constexpr (GRAD) {
+                const double dbx = i == 0 ? 0.0 : (i == 1 ? 1.0 : cheb_d_next(px, xm1, dxm1, dxm2));
+                gx += dbx * r;
+                gy += bx * rd;
+                dxm2 = dxm1;
+                dxm1 = dbx;
+            }
             xm2 = xm1;
             xm1 = bx;
         }
         a.out[q * a.ncomp + c] = v;
+        if constexpr (GRAD) {
+            a.grad[(q * a.ncomp + c) * 2] = gx;
+            a.grad[(q * a.ncomp + c) * 2 + 1] = gy;
+        }
     }
     if (a.elem) a.elem[q] = 0;
 }
@@ -581,7 +750,8 @@ inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK);
 
 template <int D, int S>
 void launch_qk(const QueryArgs& a, const Grid& g, hipStream_t st) {
-    hipLaunchKernelGGL((query_qk<D, S>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+    if (a.grad) hipLaunchKernelGGL((query_qk<D, S, true>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+    else hipLaunchKernelGGL((query_qk<D, S, false>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
 }
 
 template <int D>
@@ -599,9 +769,16 @@ void launch_qk_d(int S, const QueryArgs& a, const Grid& g, hipStream_t st) {
     }
 }
 
+template <int FAM>
+void launch_simplex(const QueryArgs& a, const Grid& g, hipStream_t st) {
+    if (a.grad) hipLaunchKernelGGL((query_simplex<FAM, true>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+    else hipLaunchKernelGGL((query_simplex<FAM, false>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+}
+
 template <int S>
 void launch_1d(const QueryArgs& a, int64_t N, int32_t sorted, hipStream_t st) {
-    hipLaunchKernelGGL((query_fem1d<S>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, N, sorted);
+    if (a.grad) hipLaunchKernelGGL((query_fem1d<S, true>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, N, sorted);
+    else hipLaunchKernelGGL((query_fem1d<S, false>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, N, sorted);
 }
 
 // the uniform grid over the union of the element boxes and its candidate lists (cell -> elements in ascending order)
@@ -704,9 +881,9 @@ void run_located(const InterpIn& in, QueryArgs a, const double* d_x, hipStream_t
         launch_qk_d<D>(in.k + 1, a, g, st);
     } else if constexpr (D == 2) {
         if (in.family == MGBHIP_INTERP_P1)
-            hipLaunchKernelGGL((query_simplex<MGBHIP_INTERP_P1>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+            launch_simplex<MGBHIP_INTERP_P1>(a, g, st);
         else
-            hipLaunchKernelGGL((query_simplex<MGBHIP_INTERP_P2>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+            launch_simplex<MGBHIP_INTERP_P2>(a, g, st);
     }
     MGB_HIP_CHECK(hipGetLastError());
     MGB_HIP_CHECK(hipStreamSynchronize(st));
@@ -717,7 +894,7 @@ void run_located(const InterpIn& in, QueryArgs a, const double* d_x, hipStream_t
 void interpolate_run(const InterpIn& in, hipStream_t st) {
     if (in.M == 0) return;
     const int64_t rows = (int64_t)in.p * in.N;
-    DevBuf<double> d_x, d_table, d_z, d_pts, d_out;
+    DevBuf<double> d_x, d_table, d_z, d_pts, d_out, d_grad;
     DevBuf<int32_t> d_elem;
     const bool fem = in.family <= MGBHIP_INTERP_P2;
     if (fem) d_x.upload(in.x, (size_t)rows * in.d, st);
@@ -725,6 +902,7 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
     d_z.upload(in.z, (size_t)rows * in.ncomp, st);
     d_pts.upload(in.pts, (size_t)in.M * in.d, st);
     d_out.alloc((size_t)in.M * in.ncomp);
+    if (in.grad) d_grad.alloc((size_t)in.M * in.ncomp * in.d);
     if (in.elem) d_elem.alloc((size_t)in.M);
     QueryArgs a{};
     a.M = in.M;
@@ -735,6 +913,7 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
     a.z = d_z.p;
     a.pts = d_pts.p;
     a.out = d_out.p;
+    a.grad = in.grad ? d_grad.p : nullptr;
     a.elem = in.elem ? d_elem.p : nullptr;
     switch (in.family) {
         case MGBHIP_INTERP_FEM1D: {
@@ -759,18 +938,25 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
             else run_located<3>(in, a, d_x.p, st);
             break;
         case MGBHIP_INTERP_SPECTRAL1D: {
-            hipLaunchKernelGGL(query_spectral1d, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
+            if (a.grad)
+                hipLaunchKernelGGL(query_spectral1d<true>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
+            else
+                hipLaunchKernelGGL(query_spectral1d<false>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
             MGB_HIP_CHECK(hipGetLastError());
             break;
         }
         case MGBHIP_INTERP_SPECTRAL2D: {
-            hipLaunchKernelGGL(query_spectral2d, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
+            if (a.grad)
+                hipLaunchKernelGGL(query_spectral2d<true>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
+            else
+                hipLaunchKernelGGL(query_spectral2d<false>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
             MGB_HIP_CHECK(hipGetLastError());
             break;
         }
         default: throw InvalidArgument("interpolate: unknown family");
     }
-    d_out.download(in.out, (size_t)in.M * in.ncomp, st);
+    if (in.out) d_out.download(in.out, (size_t)in.M * in.ncomp, st);
+    if (in.grad) d_grad.download(in.grad, (size_t)in.M * in.ncomp * in.d, st);
     if (in.elem) d_elem.download(in.elem, (size_t)in.M, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }

@@ -1,4 +1,4 @@
-// interpolate.hpp -- point evaluation behind mgbhip_interpolate (interpolate.hip).
+// interpolate.hpp -- point evaluation behind mgbhip_interpolate / mgbhip_interpolate_grad (interpolate.hip).
 #pragma once
 #include <cstdint>
 
@@ -18,7 +18,8 @@ struct InterpIn {
     int64_t table_len = 0;
     const double* z = nullptr;    // host (p*N) x ncomp
     const double* pts = nullptr;  // host M x d
-    double* out = nullptr;        // host M x ncomp
+    double* out = nullptr;        // host M x ncomp (may be NULL when grad is given)
+    double* grad = nullptr;       // host M x ncomp x d, or NULL: values only
     int32_t* elem = nullptr;      // host M, or NULL
 };
 

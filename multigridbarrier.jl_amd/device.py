@@ -115,7 +115,7 @@ EXPORTS = [
     "mgbhip_vec_alloc", "mgbhip_vec_free", "mgbhip_vec_len", "mgbhip_vec_upload", "mgbhip_vec_download",
     "mgbhip_vec_fill", "mgbhip_vec_copy", "mgbhip_vec_axpy", "mgbhip_vec_scale", "mgbhip_vec_dot",
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
-    "mgbhip_prolong_add", "mgbhip_interpolate",
+    "mgbhip_prolong_add", "mgbhip_interpolate", "mgbhip_interpolate_grad",
 ]
 
 
@@ -188,6 +188,8 @@ def load_library():
     lib.mgbhip_prolong_add.argtypes = [vp, C.c_int32, vp, vp]
     lib.mgbhip_interpolate.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32,
                                        _dp, C.c_int64, _dp, _dp, _ip]
+    lib.mgbhip_interpolate_grad.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp,
+                                            C.c_int32, _dp, C.c_int64, _dp, _dp, _dp, _ip]
     _LIB = lib
     return lib
 

@@ -2,7 +2,8 @@
 
 The reference covers 1-D Q_k FEM (src/TensorFEM.jl:957-1014), `spectral1d` (src/spectral1d.jl:140-170) and `spectral2d`
 (src/spectral2d.jl:85-125); this module also covers the 2-D and 3-D element families (Q_k, P1, P2), which the reference
-does not.  Every evaluation runs on the device in one call of `mgbhip_interpolate` (csrc/interpolate.hip); the host
+does not.  Every evaluation runs on the device in one call of `mgbhip_interpolate` (csrc/interpolate.hip), or of
+`mgbhip_interpolate_grad` when the gradient at the points is wanted as well (`gradient=True`); the host
 only checks arguments, builds the small basis tables and, for the spectral families, forms the Chebyshev coefficients
 exactly as the reference does (`evaluation(x, n) \\ z`).  Arguments are checked before any device work.
 """
@@ -83,7 +84,7 @@ def _plan(geom: Geometry):
     raise ValueError(f"interpolate: no method for {type(disc).__name__} geometries")
 
 
-def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool = False):
+def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool = False, gradient: bool = False):
     """Evaluate the element-space function with broken-basis values `z` at the points `t`.
 
     `z` is `(p*N,)` in `geom.xflat` row order (a column of `sol.z`), or `(p*N, k)`: the result then has a trailing axis
@@ -100,6 +101,21 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
 
     With `return_element=True` the result is `(values, elements)`: the int32 element used per point (-1: none; the
     spectral families report 0).
+
+    With `gradient=True` the result is `(values, grads)` or `(values, grads, elements)`: the gradient with respect to x
+    at each point, evaluated on the device next to the value (`mgbhip_interpolate_grad`).  `grads` has the shape of
+    `values` with the component axis (if any) followed by a trailing axis of length `d`; for 1-D geometries that axis
+    is dropped, so `grads` has the shape of `values`.  The values are bitwise those of `gradient=False`.
+
+    - fem2d / fem3d: `J^{-T} sum_i grad_xi phi_i z_i` with the Jacobian of the element map at the located reference
+      point (curved elements included); fem2d_P1 / fem2d_P2: the basis differentiated in barycentric coordinates and
+      mapped by the inverse transpose of the edge vectors.
+    - fem1d: the derivative of the element's interpolant over `dx/dxi`.  Values are clamped outside the mesh, so the
+      derivative there is 0.0; at `x[0]` and `x[-1]` it is the one-sided derivative of the end element; NaN gives NaN.
+    - spectral1d / spectral2d: the derivative of the Chebyshev interpolant (finite at +-1); a non-finite point gives NaN.
+    - A point whose value is NaN has NaN in every gradient entry.  The gradient of an element-space function is
+      discontinuous across element faces: a point on a shared face (or node) reports the gradient of the lowest-index
+      element that contains it, the same element its value comes from, which is what makes the result deterministic.
     """
     family, name, d, k, p, N, xnodes, table = _plan(geom)
     Z = np.asarray(z, dtype=np.float64)
@@ -137,6 +153,7 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
         Zd = Z
     M, ncomp = pts.shape[0], Z.shape[1]
     out = np.empty((M, ncomp))
+    grad = np.empty((M, ncomp, d)) if gradient else None
     elem = np.empty(M, dtype=np.int32)
     if M:
         from .device import HipContext, _check, _ptr
@@ -145,9 +162,15 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
         table = None if table is None else _c_f64(table)
         ctx = HipContext(device_id)
         try:
-            _check(ctx.lib, ctx.lib.mgbhip_interpolate(
-                ctx.handle, family, d, k, p, N, _ptr(xnodes), _ptr(table), ncomp, _ptr(Zd), M, _ptr(pts),
-                _ptr(out), elem.ctypes.data_as(C.POINTER(C.c_int32))))
+            eptr = elem.ctypes.data_as(C.POINTER(C.c_int32))
+            if gradient:
+                _check(ctx.lib, ctx.lib.mgbhip_interpolate_grad(
+                    ctx.handle, family, d, k, p, N, _ptr(xnodes), _ptr(table), ncomp, _ptr(Zd), M, _ptr(pts),
+                    _ptr(out), _ptr(grad), eptr))
+            else:
+                _check(ctx.lib, ctx.lib.mgbhip_interpolate(
+                    ctx.handle, family, d, k, p, N, _ptr(xnodes), _ptr(table), ncomp, _ptr(Zd), M, _ptr(pts),
+                    _ptr(out), eptr))
         finally:
             ctx.close()
     vals = out[:, 0] if single else out
@@ -159,4 +182,14 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
     else:
         vals = vals.reshape(shape + (() if single else (ncomp,)))
         elem_out = elem.reshape(shape)
-    return (vals, elem_out) if return_element else vals
+    if not gradient:
+        return (vals, elem_out) if return_element else vals
+    g = grad[:, 0] if single else grad                       # (M, d) or (M, ncomp, d)
+    if d == 1:
+        g = g[..., 0]
+    if scalar:
+        g = g[0]
+        g = float(g) if g.ndim == 0 else g.copy()
+    else:
+        g = g.reshape(shape + g.shape[1:])
+    return (vals, g, elem_out) if return_element else (vals, g)
