@@ -314,6 +314,26 @@ int mgbhip_interpolate_grad(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t 
                             const double* pts, double* out /* M x ncomp, may be NULL */,
                             double* grad /* M x ncomp x d */, int32_t* elem /* M or NULL */);
 
+/* ---- point locator: locate the points once, evaluate many z at them ---------------------------------------------
+ * mgbhip_locator_create does the part of mgbhip_interpolate that does not depend on z (grid of element boxes, points
+ * sorted by cell, element map inverted per point) and keeps per point the element and the reference coordinates on the
+ * device; mgbhip_locator_evaluate uploads one z, runs the evaluation half of the query and copies the result back.
+ * What it returns is bitwise what mgbhip_interpolate / mgbhip_interpolate_grad return for the same arguments (values,
+ * gradients, elements, NaN positions).  Argument meaning, layouts, checks and error codes are those of
+ * mgbhip_interpolate; x, table and pts are copied (the caller's arrays may change or go away afterwards).  A locator
+ * belongs to the context it was created from and must be destroyed before it.  M = 0 is allowed: every call is then a
+ * no-op.  ncomp may differ from call to call.                                                                      */
+typedef struct mgbhip_locator mgbhip_locator;
+int mgbhip_locator_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                          const double* x, const double* table, int64_t M, const double* pts,
+                          mgbhip_locator** out);
+/* elem[q] = the element point q was located in (-1: none; the spectral families report 0 for a finite point) */
+int mgbhip_locator_elements(const mgbhip_locator* loc, int32_t* elem /* M */);
+int mgbhip_locator_evaluate(mgbhip_locator* loc, int32_t ncomp, const double* z /* (p*N) x ncomp */,
+                            double* out /* M x ncomp, may be NULL when grad is given */,
+                            double* grad /* M x ncomp x d, or NULL: values only */);
+int mgbhip_locator_destroy(mgbhip_locator* loc); /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,6 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .device import (Device, HIPDevice, CPUDevice, native_to_device, device_to_native,
                          default_device, default_device_set, mgb_cleanup, library_path)
     from .solve import mgb_solve, MGBSOL, MGBConvergenceFailure
-    from .interpolate import interpolate
+    from .interpolate import interpolate, PointLocator
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

@@ -43,6 +43,13 @@ static int dev_of(const mgbhip_ctx* c) { return c ? c->device : -1; }
 static int dev_of(const mgbhip_problem* p) { return (p && p->ctx) ? p->ctx->device : -1; }
 static int dev_of(const mgbhip_vec* v) { return (v && v->ctx) ? v->ctx->device : -1; }
 
+// a point locator (interpolate.hpp) and the context it lives in
+struct mgbhip_locator {
+    mgbhip_ctx* ctx = nullptr;
+    Locator loc;
+};
+static int dev_of(const mgbhip_locator* l) { return (l && l->ctx) ? l->ctx->device : -1; }
+
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
 #define MGB_API_END                                   \
@@ -639,21 +646,15 @@ int mgbhip_reset_stage_timers(mgbhip_problem* P, int enable) {
     MGB_API_END
 }
 
-// the argument checks and the run shared by mgbhip_interpolate (grad = NULL) and mgbhip_interpolate_grad
-static void interpolate_checked(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
-                                const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
-                                const double* pts, double* out, double* grad, int32_t* elem) {
-    const bool need_out = grad == nullptr;      // the gradient entry may leave the values out
-    MGB_REQUIRE(ctx != nullptr, "null context");
-    MGB_REQUIRE(N > 0, "interpolate: no elements (N = 0)");
-    MGB_REQUIRE(M >= 0 && ncomp >= 1 && p >= 1, "interpolate: bad sizes");
-    MGB_REQUIRE(z != nullptr && (M == 0 || (pts != nullptr && (out != nullptr || !need_out))), "null argument");
-    InterpIn in;
-    in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.ncomp = ncomp; in.M = M;
-    in.x = x; in.table = table; in.z = z; in.pts = pts; in.out = out; in.grad = grad; in.elem = elem;
+// the checks of the geometry arguments shared by mgbhip_interpolate, mgbhip_interpolate_grad and mgbhip_locator_create;
+// fills in.table_len and in.sorted
+static void interpolate_check_geometry(InterpIn& in) {
+    const int32_t family = in.family, d = in.d, k = in.k, p = in.p;
+    const int64_t N = in.N;
+    const double* x = in.x;
     const bool fem = family >= MGBHIP_INTERP_FEM1D && family <= MGBHIP_INTERP_P2;
     if (fem) {
-        MGB_REQUIRE(x != nullptr && table != nullptr, "interpolate: FEM families need node coordinates and a table");
+        MGB_REQUIRE(x != nullptr && in.table != nullptr, "interpolate: FEM families need node coordinates and a table");
         MGB_REQUIRE(k >= 1 && k <= INTERP_MAX_DEGREE, "interpolate: element degree out of range");
     }
     switch (family) {
@@ -688,7 +689,22 @@ static void interpolate_checked(mgbhip_ctx* ctx, int32_t family, int32_t d, int3
         default:
             throw InvalidArgument("interpolate: unknown family");
     }
-    MGB_REQUIRE((int64_t)p * N < (int64_t)INT32_MAX && M < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
+    MGB_REQUIRE((int64_t)p * N < (int64_t)INT32_MAX && in.M < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
+}
+
+// the argument checks and the run shared by mgbhip_interpolate (grad = NULL) and mgbhip_interpolate_grad
+static void interpolate_checked(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                                const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
+                                const double* pts, double* out, double* grad, int32_t* elem) {
+    const bool need_out = grad == nullptr;      // the gradient entry may leave the values out
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(N > 0, "interpolate: no elements (N = 0)");
+    MGB_REQUIRE(M >= 0 && ncomp >= 1 && p >= 1, "interpolate: bad sizes");
+    MGB_REQUIRE(z != nullptr && (M == 0 || (pts != nullptr && (out != nullptr || !need_out))), "null argument");
+    InterpIn in;
+    in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.ncomp = ncomp; in.M = M;
+    in.x = x; in.table = table; in.z = z; in.pts = pts; in.out = out; in.grad = grad; in.elem = elem;
+    interpolate_check_geometry(in);
     MGB_REQUIRE(M * ncomp * (grad ? d : 1) < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
     interpolate_run(in, ctx->stream);
 }
@@ -708,6 +724,56 @@ int mgbhip_interpolate_grad(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t 
     MGB_API_BEGIN_ON(ctx)
     MGB_REQUIRE(grad != nullptr, "interpolate_grad: null gradient array");
     interpolate_checked(ctx, family, d, k, p, N, x, table, ncomp, z, M, pts, out, grad, elem);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_locator_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                          const double* table, int64_t M, const double* pts, mgbhip_locator** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(N > 0, "interpolate: no elements (N = 0)");
+    MGB_REQUIRE(M >= 0 && p >= 1, "interpolate: bad sizes");
+    MGB_REQUIRE(M == 0 || pts != nullptr, "null argument");
+    InterpIn in;
+    in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.M = M;
+    in.x = x; in.table = table; in.pts = pts;
+    interpolate_check_geometry(in);
+    std::unique_ptr<mgbhip_locator> loc(new mgbhip_locator());
+    loc->ctx = ctx;
+    locator_build(loc->loc, in, ctx->stream);
+    *out = loc.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_locator_elements(const mgbhip_locator* loc, int32_t* elem) {
+    MGB_API_BEGIN_ON(loc)
+    MGB_REQUIRE(loc != nullptr, "null locator");
+    MGB_REQUIRE(loc->loc.M == 0 || elem != nullptr, "null argument");
+    locator_elements(loc->loc, elem, loc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_locator_evaluate(mgbhip_locator* loc, int32_t ncomp, const double* z, double* out, double* grad) {
+    MGB_API_BEGIN_ON(loc)
+    MGB_REQUIRE(loc != nullptr, "null locator");
+    const Locator& L = loc->loc;
+    MGB_REQUIRE(ncomp >= 1, "interpolate: bad sizes");
+    MGB_REQUIRE(z != nullptr && (L.M == 0 || out != nullptr || grad != nullptr), "null argument");
+    MGB_REQUIRE(L.M * ncomp * (grad ? L.d : 1) < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
+    locator_evaluate(loc->loc, ncomp, z, out, grad, loc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_locator_destroy(mgbhip_locator* loc) {
+    MGB_API_BEGIN_ON(loc)
+    if (!loc) return MGBHIP_OK;
+    (void)hipStreamSynchronize(loc->ctx->stream);
+    delete loc;
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -358,7 +358,7 @@ __device__ inline bool simplex_locate(const double* __restrict__ x, int64_t e, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// query kernels: one lane per point
+// query, locate and evaluate kernels: one lane per point
 // ---------------------------------------------------------------------------------------------------------------
 
 struct QueryArgs {
@@ -377,8 +377,22 @@ struct QueryArgs {
     int32_t* elem;
 };
 
-// every query kernel has a compile-time GRAD flag: the GRAD = false instantiation is the value-only kernel, the
-// GRAD = true one computes the same values by the same operations and also the gradient with respect to x
+// What a locate kernel leaves behind for the evaluate kernels of a point locator, per lane i (the stored cell order of
+// the located families, the point index otherwise): the element (-1: none) and the reference coordinates the fused
+// query kernel would have evaluated at.
+struct LocArgs {
+    int32_t* elem;             // M
+    double* ref;               // Q_k: M x D (xi); P1 / P2: M x 2 (l1, l2); fem1d: M (xi); spectral: unused
+    int32_t* flag;             // fem1d: one of FEM1D_GENERAL .. FEM1D_CROSSED; unused otherwise
+};
+
+// Every query kernel consists of two device functions, *locate* (point -> element + reference coordinates) and
+// *evaluate* (element + reference coordinates + z -> values and, with GRAD, the gradient).  The fused query_* kernels
+// call one after the other; the locate_* / eval_* kernels of a point locator call them in separate launches with the
+// reference coordinates stored in between, so both paths run the same operations on the same numbers.
+//
+// Every query / eval kernel has a compile-time GRAD flag: the GRAD = false instantiation is the value-only kernel, the
+// GRAD = true one computes the same values by the same operations and also the gradient with respect to x.
 template <int D, bool GRAD>
 __device__ inline void write_nan(const QueryArgs& a, int64_t q) {
     for (int c = 0; c < a.ncomp; ++c) a.out[q * a.ncomp + c] = dnan();
@@ -387,33 +401,36 @@ __device__ inline void write_nan(const QueryArgs& a, int64_t q) {
     if (a.elem) a.elem[q] = -1;
 }
 
-template <int D, int S, bool GRAD>
-__global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.M) return;
-    const int64_t q = a.order[i];
-    double pt[D];
-    for (int d = 0; d < D; ++d) pt[d] = a.pts[q * D + d];
+// Q_k locate: the lowest-index candidate of the point's cell whose element map inverts to a point of the reference
+// cube; on success L holds the basis factors at xi (as qk_locate leaves them) and nodes the reference nodes of the
+// table.  -1: no element.
+template <int D, int S>
+__device__ inline int64_t qk_find(const QueryArgs& a, const Grid& g, const double (&pt)[D], double (&nodes)[S],
+                                  double (&L)[D][S], double (&xi)[D]) {
     const int64_t cell = point_cell<D>(g, pt);
-    if (cell < 0) { write_nan<D, GRAD>(a, q); return; }
-    double nodes[S];
+    if (cell < 0) return -1;
     for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
-    double L[D][S], xi[D];
-    int64_t found = -1;
     const int32_t j1 = a.start[cell + 1];
     for (int32_t j = a.start[cell]; j < j1; ++j) {
         const int64_t e = a.cand[j];
         bool inbox = true;             // a point outside the element's padded box is not in the element: skip Newton
         for (int d = 0; d < D; ++d)
             inbox = inbox && pt[d] >= a.box[e * 2 * D + d] && pt[d] <= a.box[e * 2 * D + D + d];
-        if (inbox && qk_locate<D, S>(a.x, e, nodes, pt, L, xi)) { found = e; break; }
+        if (inbox && qk_locate<D, S>(a.x, e, nodes, pt, L, xi)) return e;
     }
-    if (found < 0) { write_nan<D, GRAD>(a, q); return; }
+    return -1;
+}
+
+// Q_k evaluate at xi of element `found`; L holds lagrange<S>(nodes, xi[d]) on entry.  False (nothing written) when the
+// Jacobian at xi cannot be inverted (GRAD only).
+// GRAD: the Jacobian J[a][b] = sum_i dphi_i/dxi_b x_i[a] at the located xi in one pass over the element's nodes,
+// then per component gxi[b] = sum_i dphi_i/dxi_b z_i next to the value sum and grad = J^{-T} gxi.  The live state
+// is that of a Newton step (L, dL, a D x D matrix, D sums), so no variant needs more registers than qk_locate.
+template <int D, int S, bool GRAD>
+__device__ inline bool qk_evaluate(const QueryArgs& a, int64_t q, int64_t found, const double (&nodes)[S],
+                                   double (&L)[D][S], const double (&xi)[D]) {
     constexpr int P = D == 2 ? S * S : S * S * S;
     const int n2 = D == 3 ? S : 1;
-    // GRAD: the Jacobian J[a][b] = sum_i dphi_i/dxi_b x_i[a] at the located xi in one pass over the element's nodes,
-    // then per component gxi[b] = sum_i dphi_i/dxi_b z_i next to the value sum and grad = J^{-T} gxi.  The live state
-    // is that of a Newton step (L, dL, a D x D matrix, D sums), so no variant needs more registers than qk_locate.
     double dL[GRAD ? D : 1][S], Ji[D][D];
     if constexpr (GRAD) {
 #pragma unroll
@@ -449,7 +466,7 @@ __global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
                 }
             }
         }
-        if (!jac_inverse<D>(J, Ji)) { write_nan<D, GRAD>(a, q); return; }
+        if (!jac_inverse<D>(J, Ji)) return false;
     }
     const double* ze = a.z + found * P * a.ncomp;
     for (int c = 0; c < a.ncomp; ++c) {
@@ -492,25 +509,67 @@ __global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
                 a.grad[(q * a.ncomp + c) * D + r] = s;
             }
     }
-    if (a.elem) a.elem[q] = (int32_t)found;
+    return true;
 }
 
-template <int FAM, bool GRAD>
-__global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
+template <int D, int S, bool GRAD>
+__global__ void __launch_bounds__(BLOCK) query_qk(QueryArgs a, Grid g) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.M) return;
     const int64_t q = a.order[i];
-    const double pt[2] = {a.pts[q * 2], a.pts[q * 2 + 1]};
+    double pt[D];
+    for (int d = 0; d < D; ++d) pt[d] = a.pts[q * D + d];
+    double nodes[S], L[D][S], xi[D];
+    const int64_t found = qk_find<D, S>(a, g, pt, nodes, L, xi);
+    if (found < 0 || !qk_evaluate<D, S, GRAD>(a, q, found, nodes, L, xi)) { write_nan<D, GRAD>(a, q); return; }
+    if (a.elem) a.elem[q] = (int32_t)found;
+}
+
+// the xi stored is the one qk_locate returns, the point its closing lagrange<S> call produced L at
+template <int D, int S>
+__global__ void __launch_bounds__(BLOCK) locate_qk(QueryArgs a, Grid g, LocArgs l) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M) return;
+    const int64_t q = a.order[i];
+    double pt[D];
+    for (int d = 0; d < D; ++d) pt[d] = a.pts[q * D + d];
+    double nodes[S], L[D][S], xi[D];
+    const int64_t found = qk_find<D, S>(a, g, pt, nodes, L, xi);
+    l.elem[i] = (int32_t)found;
+    for (int d = 0; d < D; ++d) l.ref[i * D + d] = found < 0 ? 0.0 : xi[d];
+}
+
+template <int D, int S, bool GRAD>
+__global__ void __launch_bounds__(BLOCK) eval_qk(QueryArgs a, LocArgs l) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M) return;
+    const int64_t q = a.order[i];
+    const int64_t found = l.elem[i];
+    if (found < 0) { write_nan<D, GRAD>(a, q); return; }
+    double nodes[S];
+    for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
+    double L[D][S], xi[D];
+    for (int d = 0; d < D; ++d) xi[d] = l.ref[i * D + d];
+#pragma unroll
+    for (int d = 0; d < D; ++d) lagrange<S>(nodes, xi[d], L[d]);
+    if (!qk_evaluate<D, S, GRAD>(a, q, found, nodes, L, xi)) write_nan<D, GRAD>(a, q);
+}
+
+// P1 / P2 locate: the lowest-index candidate of the point's cell that contains it, with its barycentric pair
+template <int FAM>
+__device__ inline int64_t simplex_find(const QueryArgs& a, const Grid& g, const double (&pt)[2], double& l1, double& l2) {
     const int64_t cell = point_cell<2>(g, pt);
-    if (cell < 0) { write_nan<2, GRAD>(a, q); return; }
-    double l1 = 0.0, l2 = 0.0;
-    int64_t found = -1;
+    if (cell < 0) return -1;
     const int32_t j1 = a.start[cell + 1];
     for (int32_t j = a.start[cell]; j < j1; ++j) {
         const int64_t e = a.cand[j];
-        if (simplex_locate<FAM>(a.x, e, a.p, pt, l1, l2)) { found = e; break; }
+        if (simplex_locate<FAM>(a.x, e, a.p, pt, l1, l2)) return e;
     }
-    if (found < 0) { write_nan<2, GRAD>(a, q); return; }
+    return -1;
+}
+
+template <int FAM, bool GRAD>
+__device__ inline void simplex_evaluate(const QueryArgs& a, int64_t q, int64_t found, double l1, double l2) {
     const double mono[10] = {1.0, l1, l2, l1 * l1, l1 * l2, l2 * l2, l1 * l1 * l1, l1 * l1 * l2, l1 * l2 * l2, l2 * l2 * l2};
     constexpr int PMAX = 7;
     double phi[PMAX];
@@ -561,7 +620,42 @@ __global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
             a.grad[(q * a.ncomp + c) * 2 + 1] = (ax * g2 - bx * g1) / det;
         }
     }
+}
+
+template <int FAM, bool GRAD>
+__global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M) return;
+    const int64_t q = a.order[i];
+    const double pt[2] = {a.pts[q * 2], a.pts[q * 2 + 1]};
+    double l1 = 0.0, l2 = 0.0;
+    const int64_t found = simplex_find<FAM>(a, g, pt, l1, l2);
+    if (found < 0) { write_nan<2, GRAD>(a, q); return; }
+    simplex_evaluate<FAM, GRAD>(a, q, found, l1, l2);
     if (a.elem) a.elem[q] = (int32_t)found;
+}
+
+template <int FAM>
+__global__ void __launch_bounds__(BLOCK) locate_simplex(QueryArgs a, Grid g, LocArgs l) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M) return;
+    const int64_t q = a.order[i];
+    const double pt[2] = {a.pts[q * 2], a.pts[q * 2 + 1]};
+    double l1 = 0.0, l2 = 0.0;
+    const int64_t found = simplex_find<FAM>(a, g, pt, l1, l2);
+    l.elem[i] = (int32_t)found;
+    l.ref[i * 2] = found < 0 ? 0.0 : l1;
+    l.ref[i * 2 + 1] = found < 0 ? 0.0 : l2;
+}
+
+template <int FAM, bool GRAD>
+__global__ void __launch_bounds__(BLOCK) eval_simplex(QueryArgs a, LocArgs l) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M) return;
+    const int64_t q = a.order[i];
+    const int64_t found = l.elem[i];
+    if (found < 0) { write_nan<2, GRAD>(a, q); return; }
+    simplex_evaluate<FAM, GRAD>(a, q, found, l.ref[i * 2], l.ref[i * 2 + 1]);
 }
 
 // d/dx of the Lagrange interpolant of element e at the reference point xi: (sum_j L_j'(xi) z_j) / (sum_j L_j'(xi) x_j)
@@ -579,28 +673,27 @@ __device__ inline void fem1d_gradient(const QueryArgs& a, int64_t q, int64_t e, 
     }
 }
 
-// 1-D Q_k: the reference's algorithm step for step (src/TensorFEM.jl:967-1014), 0-based.  GRAD: the values are clamped
-// outside [x_lo, x_hi], so the derivative there is 0; at x_lo / x_hi it is the one-sided derivative of the end element.
-template <int S, bool GRAD>
-__global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int32_t sorted) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= a.M) return;
-    const double* x = a.x;
-    const double t = a.pts[q];
-    const int nc = a.ncomp;
-    if (isnan(t)) { write_nan<1, GRAD>(a, q); return; }
+// how a located 1-D point is evaluated (the element is -1 for a NaN point)
+constexpr int32_t FEM1D_GENERAL = 0;   // inside element e: the interpolant at the bisection's xi
+constexpr int32_t FEM1D_NODE = 1;      // on an end node of element e (xi = -1 or 1): that node's value, one-sided derivative
+constexpr int32_t FEM1D_CLAMPED = 2;   // outside the mesh: the value of the end node (xi = -1 or 1 of e), derivative 0
+// x[0] > x[end] (elements not in ascending order) and t == x[end]: the first branch of the reference's clamp takes the first
+// node's value, and the derivative is the one-sided one of the last element, as for any t == x[end]
+constexpr int32_t FEM1D_CROSSED = 3;
+
+// 1-D Q_k locate: the reference's algorithm step for step (src/TensorFEM.jl:967-1014), 0-based.  Returns the element
+// (-1 for NaN) and sets xi and the flag.
+template <int S>
+__device__ inline int64_t fem1d_locate(const double* __restrict__ x, const double (&nodes)[S], int64_t N,
+                                       int32_t sorted, double t, double& xi, int32_t& flag) {
+    xi = 0.0;
+    flag = FEM1D_GENERAL;
+    if (isnan(t)) return -1;
     const double x_lo = x[0], x_hi = x[(N - 1) * S + S - 1];
     if (t <= x_lo || t >= x_hi) {
-        const int64_t row = t <= x_lo ? 0 : N * S - 1;
-        for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[row * nc + c];
-        if (a.elem) a.elem[q] = t <= x_lo ? 0 : (int32_t)(N - 1);
-        if constexpr (GRAD) {
-            if (t == x_lo) fem1d_gradient<S>(a, q, 0, -1.0);
-            else if (t == x_hi) fem1d_gradient<S>(a, q, N - 1, 1.0);
-            else
-                for (int c = 0; c < nc; ++c) a.grad[q * nc + c] = 0.0;
-        }
-        return;
+        xi = t <= x_lo ? -1.0 : 1.0;
+        flag = t == x_lo ? FEM1D_NODE : (t == x_hi ? (t <= x_lo ? FEM1D_CROSSED : FEM1D_NODE) : FEM1D_CLAMPED);
+        return t <= x_lo ? 0 : N - 1;
     }
     int64_t e;
     if (sorted) {       // searchsortedlast over the left endpoints, clamped to [0, N-1]
@@ -614,23 +707,14 @@ __global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int
         e = 0;
         while (e < N - 1 && t > x[e * S + S - 1]) ++e;
     }
-    if (a.elem) a.elem[q] = (int32_t)e;
-    double nodes[S], xe[S];
-    for (int j = 0; j < S; ++j) { nodes[j] = a.table[j]; xe[j] = x[e * S + j]; }
+    double xe[S];
+    for (int j = 0; j < S; ++j) xe[j] = x[e * S + j];
     double lo = -1.0, hi = 1.0;
     double flo = xe[0] - t;
-    if (flo == 0.0) {
-        for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[(e * S) * nc + c];
-        if constexpr (GRAD) fem1d_gradient<S>(a, q, e, -1.0);
-        return;
-    }
+    if (flo == 0.0) { xi = -1.0; flag = FEM1D_NODE; return e; }
     const double fhi = xe[S - 1] - t;
-    if (fhi == 0.0) {
-        for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[(e * S + S - 1) * nc + c];
-        if constexpr (GRAD) fem1d_gradient<S>(a, q, e, 1.0);
-        return;
-    }
-    double xi = 0.0, L[S];
+    if (fhi == 0.0) { xi = 1.0; flag = FEM1D_NODE; return e; }
+    double L[S];
     for (int it = 0; it < BISECT_MAXIT; ++it) {
         xi = (lo + hi) / 2;
         if (xi == lo || xi == hi) break;
@@ -646,6 +730,27 @@ __global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int
             hi = xi;
         }
     }
+    return e;
+}
+
+// 1-D Q_k evaluate.  GRAD: the values are clamped outside [x_lo, x_hi], so the derivative there is 0; at x_lo / x_hi
+// (and at any other element end the point hits exactly) it is the one-sided derivative of the element.
+template <int S, bool GRAD>
+__device__ inline void fem1d_evaluate(const QueryArgs& a, const double (&nodes)[S], int64_t N, int64_t q, int64_t e,
+                                      double xi, int32_t flag) {
+    const int nc = a.ncomp;
+    if (flag != FEM1D_GENERAL) {
+        const int64_t row = xi < 0.0 ? e * S : e * S + S - 1;
+        for (int c = 0; c < nc; ++c) a.out[q * nc + c] = a.z[row * nc + c];
+        if constexpr (GRAD) {
+            if (flag == FEM1D_NODE) fem1d_gradient<S>(a, q, e, xi);
+            else if (flag == FEM1D_CROSSED) fem1d_gradient<S>(a, q, N - 1, 1.0);
+            else
+                for (int c = 0; c < nc; ++c) a.grad[q * nc + c] = 0.0;
+        }
+        return;
+    }
+    double L[S];
     lagrange<S>(nodes, xi, L);
     for (int c = 0; c < nc; ++c) {
         double v = 0.0;
@@ -655,15 +760,50 @@ __global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int
     if constexpr (GRAD) fem1d_gradient<S>(a, q, e, xi);
 }
 
+template <int S, bool GRAD>
+__global__ void __launch_bounds__(BLOCK) query_fem1d(QueryArgs a, int64_t N, int32_t sorted) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.M) return;
+    double nodes[S], xi;
+    for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
+    int32_t flag;
+    const int64_t e = fem1d_locate<S>(a.x, nodes, N, sorted, a.pts[q], xi, flag);
+    if (e < 0) { write_nan<1, GRAD>(a, q); return; }
+    if (a.elem) a.elem[q] = (int32_t)e;
+    fem1d_evaluate<S, GRAD>(a, nodes, N, q, e, xi, flag);
+}
+
+template <int S>
+__global__ void __launch_bounds__(BLOCK) locate_fem1d(QueryArgs a, int64_t N, int32_t sorted, LocArgs l) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.M) return;
+    double nodes[S], xi;
+    for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
+    int32_t flag;
+    l.elem[q] = (int32_t)fem1d_locate<S>(a.x, nodes, N, sorted, a.pts[q], xi, flag);
+    l.ref[q] = xi;
+    l.flag[q] = flag;
+}
+
+template <int S, bool GRAD>
+__global__ void __launch_bounds__(BLOCK) eval_fem1d(QueryArgs a, int64_t N, LocArgs l) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.M) return;
+    const int64_t e = l.elem[q];
+    if (e < 0) { write_nan<1, GRAD>(a, q); return; }
+    double nodes[S];
+    for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
+    fem1d_evaluate<S, GRAD>(a, nodes, N, q, e, l.ref[q], l.flag[q]);
+}
+
 // spectral: sum_j c_j T_j(t) (1-D) and bx' C by (2-D) with the three-term recurrence of `_chebyshev_values`; GRAD carries
-// the differentiated recurrence T_j' = 2 T_{j-1} + 2 x T_{j-1}' - T_{j-2}' next to it (finite at x = +-1)
+// the differentiated recurrence T_j' = 2 T_{j-1} + 2 x T_{j-1}' - T_{j-2}' next to it (finite at x = +-1).  There is
+// nothing to locate: a point locator keeps the points, and eval_spectral* is the query without the element output.
 __device__ inline double cheb_next(double x, double tm1, double tm2) { return 2 * x * tm1 - tm2; }
 __device__ inline double cheb_d_next(double x, double tm1, double dm1, double dm2) { return 2 * tm1 + 2 * x * dm1 - dm2; }
 
 template <bool GRAD>
-__global__ void __launch_bounds__(BLOCK) query_spectral1d(QueryArgs a, int32_t n) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= a.M) return;
+__device__ inline void spectral1d_point(const QueryArgs& a, int64_t q, int32_t n) {
     const double t = a.pts[q];
     if (!isfinite(t)) { write_nan<1, GRAD>(a, q); return; }
     for (int c = 0; c < a.ncomp; ++c) {
@@ -689,9 +829,7 @@ __global__ void __launch_bounds__(BLOCK) query_spectral1d(QueryArgs a, int32_t n
 }
 
 template <bool GRAD>
-__global__ void __launch_bounds__(BLOCK) query_spectral2d(QueryArgs a, int32_t n) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= a.M) return;
+__device__ inline void spectral2d_point(const QueryArgs& a, int64_t q, int32_t n) {
     const double px = a.pts[q * 2], py = a.pts[q * 2 + 1];
     if (!isfinite(px) || !isfinite(py)) { write_nan<2, GRAD>(a, q); return; }
     for (int c = 0; c < a.ncomp; ++c) {
@@ -734,6 +872,31 @@ __global__ void __launch_bounds__(BLOCK) query_spectral2d(QueryArgs a, int32_t n
     if (a.elem) a.elem[q] = 0;
 }
 
+template <bool GRAD>
+__global__ void __launch_bounds__(BLOCK) query_spectral1d(QueryArgs a, int32_t n) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < a.M) spectral1d_point<GRAD>(a, q, n);
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(BLOCK) query_spectral2d(QueryArgs a, int32_t n) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < a.M) spectral2d_point<GRAD>(a, q, n);
+}
+
+// the locator's kernels: a.elem is NULL (the elements of a spectral locator are all 0 and never stored)
+template <bool GRAD>
+__global__ void __launch_bounds__(BLOCK) eval_spectral1d(QueryArgs a, int32_t n) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < a.M) spectral1d_point<GRAD>(a, q, n);
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(BLOCK) eval_spectral2d(QueryArgs a, int32_t n) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < a.M) spectral2d_point<GRAD>(a, q, n);
+}
+
 template <int D>
 __global__ void query_keys(int64_t M, Grid g, const double* __restrict__ pts, uint32_t* __restrict__ keys,
                            int32_t* __restrict__ idx) {
@@ -748,37 +911,114 @@ __global__ void query_keys(int64_t M, Grid g, const double* __restrict__ pts, ui
 
 inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
+// which kernels a launch sequence runs: the fused query (mgbhip_interpolate*), or one half of it for a point locator
+enum class Pass { FUSED, LOCATE, EVAL };
+
 template <int D, int S>
-void launch_qk(const QueryArgs& a, const Grid& g, hipStream_t st) {
-    if (a.grad) hipLaunchKernelGGL((query_qk<D, S, true>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
-    else hipLaunchKernelGGL((query_qk<D, S, false>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+void launch_qk(Pass pass, const QueryArgs& a, const Grid& g, const LocArgs& l, hipStream_t st) {
+    const dim3 gr(grid_1d(a.M)), bl(BLOCK);
+    if (pass == Pass::LOCATE) hipLaunchKernelGGL((locate_qk<D, S>), gr, bl, 0, st, a, g, l);
+    else if (pass == Pass::EVAL) {
+        if (a.grad) hipLaunchKernelGGL((eval_qk<D, S, true>), gr, bl, 0, st, a, l);
+        else hipLaunchKernelGGL((eval_qk<D, S, false>), gr, bl, 0, st, a, l);
+    } else {
+        if (a.grad) hipLaunchKernelGGL((query_qk<D, S, true>), gr, bl, 0, st, a, g);
+        else hipLaunchKernelGGL((query_qk<D, S, false>), gr, bl, 0, st, a, g);
+    }
 }
 
 template <int D>
-void launch_qk_d(int S, const QueryArgs& a, const Grid& g, hipStream_t st) {
+void launch_qk_d(int S, Pass pass, const QueryArgs& a, const Grid& g, const LocArgs& l, hipStream_t st) {
     switch (S) {
-        case 2: launch_qk<D, 2>(a, g, st); break;
-        case 3: launch_qk<D, 3>(a, g, st); break;
-        case 4: launch_qk<D, 4>(a, g, st); break;
-        case 5: launch_qk<D, 5>(a, g, st); break;
-        case 6: launch_qk<D, 6>(a, g, st); break;
-        case 7: launch_qk<D, 7>(a, g, st); break;
-        case 8: launch_qk<D, 8>(a, g, st); break;
-        case 9: launch_qk<D, 9>(a, g, st); break;
+        case 2: launch_qk<D, 2>(pass, a, g, l, st); break;
+        case 3: launch_qk<D, 3>(pass, a, g, l, st); break;
+        case 4: launch_qk<D, 4>(pass, a, g, l, st); break;
+        case 5: launch_qk<D, 5>(pass, a, g, l, st); break;
+        case 6: launch_qk<D, 6>(pass, a, g, l, st); break;
+        case 7: launch_qk<D, 7>(pass, a, g, l, st); break;
+        case 8: launch_qk<D, 8>(pass, a, g, l, st); break;
+        case 9: launch_qk<D, 9>(pass, a, g, l, st); break;
         default: throw InvalidArgument("interpolate: Q_k degree out of range");
     }
 }
 
 template <int FAM>
-void launch_simplex(const QueryArgs& a, const Grid& g, hipStream_t st) {
-    if (a.grad) hipLaunchKernelGGL((query_simplex<FAM, true>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
-    else hipLaunchKernelGGL((query_simplex<FAM, false>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);
+void launch_simplex(Pass pass, const QueryArgs& a, const Grid& g, const LocArgs& l, hipStream_t st) {
+    const dim3 gr(grid_1d(a.M)), bl(BLOCK);
+    if (pass == Pass::LOCATE) hipLaunchKernelGGL((locate_simplex<FAM>), gr, bl, 0, st, a, g, l);
+    else if (pass == Pass::EVAL) {
+        if (a.grad) hipLaunchKernelGGL((eval_simplex<FAM, true>), gr, bl, 0, st, a, l);
+        else hipLaunchKernelGGL((eval_simplex<FAM, false>), gr, bl, 0, st, a, l);
+    } else {
+        if (a.grad) hipLaunchKernelGGL((query_simplex<FAM, true>), gr, bl, 0, st, a, g);
+        else hipLaunchKernelGGL((query_simplex<FAM, false>), gr, bl, 0, st, a, g);
+    }
+}
+
+// Q_k / P1 / P2 in D dimensions; EVAL needs no grid
+template <int D>
+void launch_located(int32_t family, int32_t k, Pass pass, const QueryArgs& a, const Grid& g, const LocArgs& l,
+                    hipStream_t st) {
+    if (family == MGBHIP_INTERP_QK) {
+        launch_qk_d<D>(k + 1, pass, a, g, l, st);
+    } else if constexpr (D == 2) {
+        if (family == MGBHIP_INTERP_P1)
+            launch_simplex<MGBHIP_INTERP_P1>(pass, a, g, l, st);
+        else
+            launch_simplex<MGBHIP_INTERP_P2>(pass, a, g, l, st);
+    }
+    MGB_HIP_CHECK(hipGetLastError());
 }
 
 template <int S>
-void launch_1d(const QueryArgs& a, int64_t N, int32_t sorted, hipStream_t st) {
-    if (a.grad) hipLaunchKernelGGL((query_fem1d<S, true>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, N, sorted);
-    else hipLaunchKernelGGL((query_fem1d<S, false>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, N, sorted);
+void launch_1d(Pass pass, const QueryArgs& a, int64_t N, int32_t sorted, const LocArgs& l, hipStream_t st) {
+    const dim3 gr(grid_1d(a.M)), bl(BLOCK);
+    if (pass == Pass::LOCATE) hipLaunchKernelGGL((locate_fem1d<S>), gr, bl, 0, st, a, N, sorted, l);
+    else if (pass == Pass::EVAL) {
+        if (a.grad) hipLaunchKernelGGL((eval_fem1d<S, true>), gr, bl, 0, st, a, N, l);
+        else hipLaunchKernelGGL((eval_fem1d<S, false>), gr, bl, 0, st, a, N, l);
+    } else {
+        if (a.grad) hipLaunchKernelGGL((query_fem1d<S, true>), gr, bl, 0, st, a, N, sorted);
+        else hipLaunchKernelGGL((query_fem1d<S, false>), gr, bl, 0, st, a, N, sorted);
+    }
+}
+
+void launch_1d_s(int S, Pass pass, const QueryArgs& a, int64_t N, int32_t sorted, const LocArgs& l, hipStream_t st) {
+    switch (S) {
+        case 2: launch_1d<2>(pass, a, N, sorted, l, st); break;
+        case 3: launch_1d<3>(pass, a, N, sorted, l, st); break;
+        case 4: launch_1d<4>(pass, a, N, sorted, l, st); break;
+        case 5: launch_1d<5>(pass, a, N, sorted, l, st); break;
+        case 6: launch_1d<6>(pass, a, N, sorted, l, st); break;
+        case 7: launch_1d<7>(pass, a, N, sorted, l, st); break;
+        case 8: launch_1d<8>(pass, a, N, sorted, l, st); break;
+        case 9: launch_1d<9>(pass, a, N, sorted, l, st); break;
+        default: throw InvalidArgument("interpolate: fem1d degree out of range");
+    }
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
+// FUSED: the query with the element output; EVAL: a locator's evaluation (a.elem is NULL)
+void launch_spectral(int32_t family, Pass pass, const QueryArgs& a, int32_t n, hipStream_t st) {
+    const dim3 gr(grid_1d(a.M)), bl(BLOCK);
+    if (family == MGBHIP_INTERP_SPECTRAL1D) {
+        if (pass == Pass::EVAL) {
+            if (a.grad) hipLaunchKernelGGL(eval_spectral1d<true>, gr, bl, 0, st, a, n);
+            else hipLaunchKernelGGL(eval_spectral1d<false>, gr, bl, 0, st, a, n);
+        } else {
+            if (a.grad) hipLaunchKernelGGL(query_spectral1d<true>, gr, bl, 0, st, a, n);
+            else hipLaunchKernelGGL(query_spectral1d<false>, gr, bl, 0, st, a, n);
+        }
+    } else {
+        if (pass == Pass::EVAL) {
+            if (a.grad) hipLaunchKernelGGL(eval_spectral2d<true>, gr, bl, 0, st, a, n);
+            else hipLaunchKernelGGL(eval_spectral2d<false>, gr, bl, 0, st, a, n);
+        } else {
+            if (a.grad) hipLaunchKernelGGL(query_spectral2d<true>, gr, bl, 0, st, a, n);
+            else hipLaunchKernelGGL(query_spectral2d<false>, gr, bl, 0, st, a, n);
+        }
+    }
+    MGB_HIP_CHECK(hipGetLastError());
 }
 
 // the uniform grid over the union of the element boxes and its candidate lists (cell -> elements in ascending order)
@@ -853,8 +1093,12 @@ void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, 
     // the temporaries are freed at scope exit; hipFree waits for the work that uses them
 }
 
+// The located families: build the grid, sort the points by cell and run the fused query (pass FUSED) or the locate
+// kernel alone (pass LOCATE: l receives the result in cell order and `order` is left to the caller, who keeps it).  The
+// grid, the candidate lists, the boxes and the sort buffers are freed on return.
 template <int D>
-void run_located(const InterpIn& in, QueryArgs a, const double* d_x, hipStream_t st) {
+void run_located(const InterpIn& in, Pass pass, QueryArgs a, const LocArgs& l, const double* d_x, hipStream_t st,
+                 DevBuf<int32_t>& order) {
     Grid g;
     DevBuf<int32_t> start, cand;
     DevBuf<double> box;
@@ -866,26 +1110,18 @@ void run_located(const InterpIn& in, QueryArgs a, const double* d_x, hipStream_t
     // (all kernels of a call, P2 at L = 9 with 4 M random points: 0.69 ms against 0.87 ms unsorted; fem3d k = 3 at
     // L = 5 with 1 M points: 3.0 ms against 5.8 ms)
     DevBuf<uint32_t> k0, k1;
-    DevBuf<int32_t> i0, i1;
-    k0.alloc((size_t)a.M); k1.alloc((size_t)a.M); i0.alloc((size_t)a.M); i1.alloc((size_t)a.M);
+    DevBuf<int32_t> i0;
+    k0.alloc((size_t)a.M); k1.alloc((size_t)a.M); i0.alloc((size_t)a.M); order.alloc((size_t)a.M);
     hipLaunchKernelGGL((query_keys<D>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a.M, g, a.pts, k0.p, i0.p);
     unsigned bits = 1;
     while (bits < 32 && ((uint64_t)g.ncell >> bits) != 0) ++bits;
     size_t sort_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, i0.p, i1.p, (size_t)a.M, 0u, bits, st));
+    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)a.M, 0u, bits, st));
     DevBuf<char> tmp;
     tmp.alloc(sort_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, i0.p, i1.p, (size_t)a.M, 0u, bits, st));
-    a.order = i1.p;
-    if (in.family == MGBHIP_INTERP_QK) {
-        launch_qk_d<D>(in.k + 1, a, g, st);
-    } else if constexpr (D == 2) {
-        if (in.family == MGBHIP_INTERP_P1)
-            launch_simplex<MGBHIP_INTERP_P1>(a, g, st);
-        else
-            launch_simplex<MGBHIP_INTERP_P2>(a, g, st);
-    }
-    MGB_HIP_CHECK(hipGetLastError());
+    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)a.M, 0u, bits, st));
+    a.order = order.p;
+    launch_located<D>(in.family, in.k, pass, a, g, l, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
@@ -895,7 +1131,7 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
     if (in.M == 0) return;
     const int64_t rows = (int64_t)in.p * in.N;
     DevBuf<double> d_x, d_table, d_z, d_pts, d_out, d_grad;
-    DevBuf<int32_t> d_elem;
+    DevBuf<int32_t> d_elem, d_order;
     const bool fem = in.family <= MGBHIP_INTERP_P2;
     if (fem) d_x.upload(in.x, (size_t)rows * in.d, st);
     if (in.table) d_table.upload(in.table, (size_t)in.table_len, st);
@@ -915,49 +1151,130 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
     a.out = d_out.p;
     a.grad = in.grad ? d_grad.p : nullptr;
     a.elem = in.elem ? d_elem.p : nullptr;
+    const LocArgs none{};
     switch (in.family) {
-        case MGBHIP_INTERP_FEM1D: {
-            switch (in.k + 1) {
-                case 2: launch_1d<2>(a, in.N, in.sorted, st); break;
-                case 3: launch_1d<3>(a, in.N, in.sorted, st); break;
-                case 4: launch_1d<4>(a, in.N, in.sorted, st); break;
-                case 5: launch_1d<5>(a, in.N, in.sorted, st); break;
-                case 6: launch_1d<6>(a, in.N, in.sorted, st); break;
-                case 7: launch_1d<7>(a, in.N, in.sorted, st); break;
-                case 8: launch_1d<8>(a, in.N, in.sorted, st); break;
-                case 9: launch_1d<9>(a, in.N, in.sorted, st); break;
-                default: throw InvalidArgument("interpolate: fem1d degree out of range");
-            }
-            MGB_HIP_CHECK(hipGetLastError());
+        case MGBHIP_INTERP_FEM1D:
+            launch_1d_s(in.k + 1, Pass::FUSED, a, in.N, in.sorted, none, st);
             break;
-        }
         case MGBHIP_INTERP_QK:
         case MGBHIP_INTERP_P1:
         case MGBHIP_INTERP_P2:
-            if (in.d == 2) run_located<2>(in, a, d_x.p, st);
-            else run_located<3>(in, a, d_x.p, st);
+            if (in.d == 2) run_located<2>(in, Pass::FUSED, a, none, d_x.p, st, d_order);
+            else run_located<3>(in, Pass::FUSED, a, none, d_x.p, st, d_order);
             break;
-        case MGBHIP_INTERP_SPECTRAL1D: {
-            if (a.grad)
-                hipLaunchKernelGGL(query_spectral1d<true>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
-            else
-                hipLaunchKernelGGL(query_spectral1d<false>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
-            MGB_HIP_CHECK(hipGetLastError());
+        case MGBHIP_INTERP_SPECTRAL1D:
+        case MGBHIP_INTERP_SPECTRAL2D:
+            launch_spectral(in.family, Pass::FUSED, a, (int32_t)(in.k + 1), st);
             break;
-        }
-        case MGBHIP_INTERP_SPECTRAL2D: {
-            if (a.grad)
-                hipLaunchKernelGGL(query_spectral2d<true>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
-            else
-                hipLaunchKernelGGL(query_spectral2d<false>, dim3(grid_1d(in.M)), dim3(BLOCK), 0, st, a, (int32_t)(in.k + 1));
-            MGB_HIP_CHECK(hipGetLastError());
-            break;
-        }
         default: throw InvalidArgument("interpolate: unknown family");
     }
     if (in.out) d_out.download(in.out, (size_t)in.M * in.ncomp, st);
     if (in.grad) d_grad.download(in.grad, (size_t)in.M * in.ncomp * in.d, st);
     if (in.elem) d_elem.download(in.elem, (size_t)in.M, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// point locator: locate once, evaluate many z
+// ---------------------------------------------------------------------------------------------------------------
+
+void locator_build(Locator& L, const InterpIn& in, hipStream_t st) {
+    L.family = in.family; L.d = in.d; L.k = in.k; L.p = in.p; L.N = in.N; L.M = in.M;
+    if (in.M == 0) return;
+    const int64_t rows = (int64_t)in.p * in.N;
+    const bool fem = in.family <= MGBHIP_INTERP_P2;
+    if (!fem) {                                  // nothing to locate: the points are the resident state
+        L.pts.upload(in.pts, (size_t)in.M * in.d, st);
+        MGB_HIP_CHECK(hipStreamSynchronize(st));
+        return;
+    }
+    DevBuf<double> d_pts;                        // freed on return: the evaluation reads only (element, reference point)
+    L.x.upload(in.x, (size_t)rows * in.d, st);
+    L.table.upload(in.table, (size_t)in.table_len, st);
+    d_pts.upload(in.pts, (size_t)in.M * in.d, st);
+    L.elem.alloc((size_t)in.M);
+    L.ref.alloc((size_t)in.M * (in.family == MGBHIP_INTERP_FEM1D ? 1 : in.d));
+    if (in.family == MGBHIP_INTERP_FEM1D) L.flag.alloc((size_t)in.M);
+    QueryArgs a{};
+    a.M = in.M;
+    a.p = in.p;
+    a.x = L.x.p;
+    a.table = L.table.p;
+    a.pts = d_pts.p;
+    const LocArgs l{L.elem.p, L.ref.p, L.flag.p};
+    if (in.family == MGBHIP_INTERP_FEM1D) {
+        launch_1d_s(in.k + 1, Pass::LOCATE, a, in.N, in.sorted, l, st);
+        MGB_HIP_CHECK(hipStreamSynchronize(st));
+    } else if (in.d == 2) {
+        run_located<2>(in, Pass::LOCATE, a, l, L.x.p, st, L.order);
+    } else {
+        run_located<3>(in, Pass::LOCATE, a, l, L.x.p, st, L.order);
+    }
+}
+
+void locator_elements(const Locator& L, int32_t* elem, hipStream_t st) {
+    if (L.M == 0) return;
+    if (L.family > MGBHIP_INTERP_P2) {           // spectral: one element; a non-finite point has none (as write_nan reports)
+        std::vector<double> pts((size_t)L.M * L.d);
+        L.pts.download(pts.data(), pts.size(), st);
+        MGB_HIP_CHECK(hipStreamSynchronize(st));
+        for (int64_t q = 0; q < L.M; ++q) {
+            bool fin = true;
+            for (int a = 0; a < L.d; ++a) fin = fin && std::isfinite(pts[(size_t)(q * L.d + a)]);
+            elem[q] = fin ? 0 : -1;
+        }
+        return;
+    }
+    if (!L.order.p) {                            // fem1d: stored by point
+        L.elem.download(elem, (size_t)L.M, st);
+        MGB_HIP_CHECK(hipStreamSynchronize(st));
+        return;
+    }
+    std::vector<int32_t> e((size_t)L.M), o((size_t)L.M);
+    L.elem.download(e.data(), (size_t)L.M, st);
+    L.order.download(o.data(), (size_t)L.M, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < L.M; ++i) elem[o[(size_t)i]] = e[(size_t)i];
+}
+
+void locator_evaluate(Locator& L, int32_t ncomp, const double* z, double* out, double* grad, hipStream_t st) {
+    if (L.M == 0) return;
+    const int64_t rows = (int64_t)L.p * L.N;
+    // grown to the largest ncomp seen and kept: no allocation in a run of calls with the same ncomp
+    L.z.upload(z, (size_t)rows * ncomp, st);
+    L.out.ensure((size_t)L.M * ncomp);
+    if (grad) L.grad.ensure((size_t)L.M * ncomp * L.d);
+    QueryArgs a{};
+    a.M = L.M;
+    a.p = L.p;
+    a.ncomp = ncomp;
+    a.x = L.x.p;
+    a.table = L.table.p;
+    a.z = L.z.p;
+    a.pts = L.pts.p;
+    a.order = L.order.p;
+    a.out = L.out.p;
+    a.grad = grad ? L.grad.p : nullptr;
+    const LocArgs l{L.elem.p, L.ref.p, L.flag.p};
+    const Grid g{};
+    switch (L.family) {
+        case MGBHIP_INTERP_FEM1D:
+            launch_1d_s(L.k + 1, Pass::EVAL, a, L.N, 1, l, st);
+            break;
+        case MGBHIP_INTERP_QK:
+        case MGBHIP_INTERP_P1:
+        case MGBHIP_INTERP_P2:
+            if (L.d == 2) launch_located<2>(L.family, L.k, Pass::EVAL, a, g, l, st);
+            else launch_located<3>(L.family, L.k, Pass::EVAL, a, g, l, st);
+            break;
+        case MGBHIP_INTERP_SPECTRAL1D:
+        case MGBHIP_INTERP_SPECTRAL2D:
+            launch_spectral(L.family, Pass::EVAL, a, (int32_t)(L.k + 1), st);
+            break;
+        default: throw InvalidArgument("interpolate: unknown family");
+    }
+    if (out) L.out.download(out, (size_t)L.M * ncomp, st);
+    if (grad) L.grad.download(grad, (size_t)L.M * ncomp * L.d, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -1,4 +1,5 @@
-// interpolate.hpp -- point evaluation behind mgbhip_interpolate / mgbhip_interpolate_grad (interpolate.hip).
+// interpolate.hpp -- point evaluation behind mgbhip_interpolate / mgbhip_interpolate_grad and the point locator behind
+// mgbhip_locator_* (interpolate.hip).
 #pragma once
 #include <cstdint>
 
@@ -25,5 +26,22 @@ struct InterpIn {
 
 // one launch sequence on st; complete (results on the host) on return
 void interpolate_run(const InterpIn& in, hipStream_t st);
+
+// A point locator: the location half of interpolate_run done once, its result resident on the device, and the
+// evaluation half run per z.  Resident: the node coordinates and the basis table (FEM families), per point the element,
+// the reference coordinates and (2-D / 3-D) its place in the cell order; for the spectral families the points.
+struct Locator {
+    int32_t family = 0, d = 0, k = 0, p = 0;
+    int64_t N = 0, M = 0;
+    DevBuf<double> x, table, pts, ref;
+    DevBuf<int32_t> elem, order, flag;
+    DevBuf<double> z, out, grad;      // per evaluate call: grown to the largest ncomp seen and kept
+};
+
+// in.z / in.ncomp / in.out / in.grad / in.elem are not read
+void locator_build(Locator& L, const InterpIn& in, hipStream_t st);
+void locator_elements(const Locator& L, int32_t* elem, hipStream_t st);
+// z host (p*N) x ncomp; out host M x ncomp or NULL; grad host M x ncomp x d or NULL; complete on return
+void locator_evaluate(Locator& L, int32_t ncomp, const double* z, double* out, double* grad, hipStream_t st);
 
 }  // namespace mgbhip

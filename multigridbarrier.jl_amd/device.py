@@ -116,6 +116,7 @@ EXPORTS = [
     "mgbhip_vec_fill", "mgbhip_vec_copy", "mgbhip_vec_axpy", "mgbhip_vec_scale", "mgbhip_vec_dot",
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
     "mgbhip_prolong_add", "mgbhip_interpolate", "mgbhip_interpolate_grad",
+    "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
 ]
 
 
@@ -190,6 +191,11 @@ def load_library():
                                        _dp, C.c_int64, _dp, _dp, _ip]
     lib.mgbhip_interpolate_grad.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp,
                                             C.c_int32, _dp, C.c_int64, _dp, _dp, _dp, _ip]
+    lib.mgbhip_locator_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int64,
+                                          _dp, C.POINTER(vp)]
+    lib.mgbhip_locator_elements.argtypes = [vp, _ip]
+    lib.mgbhip_locator_evaluate.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    lib.mgbhip_locator_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 

@@ -6,6 +6,10 @@ does not.  Every evaluation runs on the device in one call of `mgbhip_interpolat
 `mgbhip_interpolate_grad` when the gradient at the points is wanted as well (`gradient=True`); the host
 only checks arguments, builds the small basis tables and, for the spectral families, forms the Chebyshev coefficients
 exactly as the reference does (`evaluation(x, n) \\ z`).  Arguments are checked before any device work.
+
+`PointLocator(geom, t)` does the part of that call that does not depend on `z` once (`mgbhip_locator_create`) and keeps
+the result on the device; its `evaluate(z)` is bitwise `interpolate(geom, z, t)` and shares the argument checks, the
+coefficient solve and the result shapes with it.
 """
 from __future__ import annotations
 
@@ -29,23 +33,41 @@ def _c_f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def _spectral1d_coefficients(geom: Geometry, Z: np.ndarray) -> np.ndarray:
-    """c = evaluation(x, n) \\ z, column by column (src/spectral1d.jl:140-150)."""
-    x = geom.xflat[:, 0]
-    V = evaluation(x, len(x))
-    return np.stack([np.linalg.solve(V, Z[:, j]) for j in range(Z.shape[1])], axis=1)
+def _spectral_basis(family: int, geom: Geometry):
+    """The Chebyshev evaluation matrix the coefficients are solved against: (V, n), or None for the FEM families."""
+    if family == SPECTRAL_1D:
+        x = geom.xflat[:, 0]
+        return evaluation(x, len(x)), len(x)
+    if family == SPECTRAL_2D:
+        n = geom.discretization.n
+        return evaluation(geom.xflat[:n, 0], n), n
+    return None
 
 
-def _spectral2d_coefficients(geom: Geometry, Z: np.ndarray) -> np.ndarray:
-    """C = V \\ reshape(z, n, n) / V', column by column (src/spectral2d.jl:85-92); row i*n + j of the result is C[i, j]."""
-    n = geom.discretization.n
-    V = evaluation(geom.xflat[:n, 0], n)
+def _spectral_coefficients(family: int, basis, Z: np.ndarray) -> np.ndarray:
+    """What the device evaluates: Z itself for the FEM families, the Chebyshev coefficients for the spectral ones.
+
+    spectral1d: c = evaluation(x, n) \\ z, column by column (src/spectral1d.jl:140-150).  spectral2d:
+    C = V \\ reshape(z, n, n) / V', column by column (src/spectral2d.jl:85-92); row i*n + j of the result is C[i, j]."""
+    if basis is None:
+        return Z
+    V, n = basis
+    if family == SPECTRAL_1D:
+        return np.stack([np.linalg.solve(V, Z[:, j]) for j in range(Z.shape[1])], axis=1)
     cols = []
     for j in range(Z.shape[1]):
         Y = np.linalg.solve(V, Z[:, j].reshape(n, n, order="F"))
         Cm = np.linalg.solve(V, Y.T).T                 # Y / V'  =  (V \\ Y')'
         cols.append(Cm.reshape(-1))
     return np.stack(cols, axis=1)
+
+
+def _spectral1d_coefficients(geom: Geometry, Z: np.ndarray) -> np.ndarray:
+    return _spectral_coefficients(SPECTRAL_1D, _spectral_basis(SPECTRAL_1D, geom), Z)
+
+
+def _spectral2d_coefficients(geom: Geometry, Z: np.ndarray) -> np.ndarray:
+    return _spectral_coefficients(SPECTRAL_2D, _spectral_basis(SPECTRAL_2D, geom), Z)
 
 
 def _check_p2_straight(x: np.ndarray, bubble: bool) -> None:
@@ -84,6 +106,70 @@ def _plan(geom: Geometry):
     raise ValueError(f"interpolate: no method for {type(disc).__name__} geometries")
 
 
+def _columns(name: str, p: int, N: int, z):
+    """(Z as (p*N, ncomp), whether z was a vector); ValueError unless z is a vector or matrix of p*N rows."""
+    Z = np.asarray(z, dtype=np.float64)
+    if Z.ndim not in (1, 2):
+        raise ValueError(f"interpolate: z must be a vector or a matrix (got {Z.ndim} dimensions)")
+    single = Z.ndim == 1
+    Z = Z.reshape(Z.shape[0], -1)
+    if Z.shape[0] != p * N:
+        raise ValueError(f"{name} interpolation needs {p * N} values (got {Z.shape[0]})")
+    if Z.shape[1] < 1:
+        raise ValueError("interpolate: z has no columns")
+    return Z, single
+
+
+def _points(name: str, d: int, N: int, xnodes, t):
+    """(points as (M, d), scalar, shape of the leading axes); ValueError for a wrong shape or an unusable mesh."""
+    if N == 0:
+        raise ValueError(f"{name} interpolation needs at least one element")
+    T = np.asarray(t, dtype=np.float64)
+    if d == 1:
+        scalar = T.ndim == 0
+        shape = T.shape
+        pts = T.reshape(-1, 1)
+    else:
+        if T.ndim == 1 and T.shape[0] == d:
+            scalar, shape = True, ()
+            pts = T.reshape(1, d)
+        elif T.ndim == 2 and T.shape[1] == d:
+            scalar, shape = False, (T.shape[0],)
+            pts = T
+        else:
+            raise ValueError(f"{name} interpolation points must form an M-by-{d} array (got shape {T.shape})")
+    if xnodes is not None and not np.all(np.isfinite(xnodes)):
+        raise ValueError(f"{name} interpolation: the mesh has non-finite node coordinates")
+    return pts, scalar, shape
+
+
+def _shape_elements(elem: np.ndarray, scalar: bool, shape):
+    return int(elem[0]) if scalar else elem.reshape(shape)
+
+
+def _shape_values(out: np.ndarray, grad, d: int, single: bool, scalar: bool, shape):
+    """(values, grads or None) in the shapes interpolate() documents, from out (M, ncomp) and grad (M, ncomp, d)."""
+    ncomp = out.shape[1]
+    vals = out[:, 0] if single else out
+    if scalar:
+        vals = vals[0] if single else vals[0].copy()
+        if single:
+            vals = float(vals)
+    else:
+        vals = vals.reshape(shape + (() if single else (ncomp,)))
+    if grad is None:
+        return vals, None
+    g = grad[:, 0] if single else grad                       # (M, d) or (M, ncomp, d)
+    if d == 1:
+        g = g[..., 0]
+    if scalar:
+        g = g[0]
+        g = float(g) if g.ndim == 0 else g.copy()
+    else:
+        g = g.reshape(shape + g.shape[1:])
+    return vals, g
+
+
 def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool = False, gradient: bool = False):
     """Evaluate the element-space function with broken-basis values `z` at the points `t`.
 
@@ -118,39 +204,9 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
       element that contains it, the same element its value comes from, which is what makes the result deterministic.
     """
     family, name, d, k, p, N, xnodes, table = _plan(geom)
-    Z = np.asarray(z, dtype=np.float64)
-    if Z.ndim not in (1, 2):
-        raise ValueError(f"interpolate: z must be a vector or a matrix (got {Z.ndim} dimensions)")
-    single = Z.ndim == 1
-    Z = Z.reshape(Z.shape[0], -1)
-    if Z.shape[0] != p * N:
-        raise ValueError(f"{name} interpolation needs {p * N} values (got {Z.shape[0]})")
-    if Z.shape[1] < 1:
-        raise ValueError("interpolate: z has no columns")
-    if N == 0:
-        raise ValueError(f"{name} interpolation needs at least one element")
-    T = np.asarray(t, dtype=np.float64)
-    if d == 1:
-        scalar = T.ndim == 0
-        shape = T.shape
-        pts = T.reshape(-1, 1)
-    else:
-        if T.ndim == 1 and T.shape[0] == d:
-            scalar, shape = True, ()
-            pts = T.reshape(1, d)
-        elif T.ndim == 2 and T.shape[1] == d:
-            scalar, shape = False, (T.shape[0],)
-            pts = T
-        else:
-            raise ValueError(f"{name} interpolation points must form an M-by-{d} array (got shape {T.shape})")
-    if xnodes is not None and not np.all(np.isfinite(xnodes)):
-        raise ValueError(f"{name} interpolation: the mesh has non-finite node coordinates")
-    if family == SPECTRAL_1D:
-        Zd = _spectral1d_coefficients(geom, Z)
-    elif family == SPECTRAL_2D:
-        Zd = _spectral2d_coefficients(geom, Z)
-    else:
-        Zd = Z
+    Z, single = _columns(name, p, N, z)
+    pts, scalar, shape = _points(name, d, N, xnodes, t)
+    Zd = _spectral_coefficients(family, _spectral_basis(family, geom), Z)
     M, ncomp = pts.shape[0], Z.shape[1]
     out = np.empty((M, ncomp))
     grad = np.empty((M, ncomp, d)) if gradient else None
@@ -173,23 +229,102 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
                     _ptr(out), eptr))
         finally:
             ctx.close()
-    vals = out[:, 0] if single else out
-    if scalar:
-        vals = vals[0] if single else vals[0].copy()
-        if single:
-            vals = float(vals)
-        elem_out = int(elem[0])
-    else:
-        vals = vals.reshape(shape + (() if single else (ncomp,)))
-        elem_out = elem.reshape(shape)
+    vals, g = _shape_values(out, grad, d, single, scalar, shape)
+    elem_out = _shape_elements(elem, scalar, shape)
     if not gradient:
         return (vals, elem_out) if return_element else vals
-    g = grad[:, 0] if single else grad                       # (M, d) or (M, ncomp, d)
-    if d == 1:
-        g = g[..., 0]
-    if scalar:
-        g = g[0]
-        g = float(g) if g.ndim == 0 else g.copy()
-    else:
-        g = g.reshape(shape + g.shape[1:])
     return (vals, g, elem_out) if return_element else (vals, g)
+
+
+class PointLocator:
+    """The points `t` located once in `geom`, for evaluating many `z` at them: `loc.evaluate(z)` is bitwise
+    `interpolate(geom, z, t)`, `loc.evaluate(z, gradient=True)` bitwise `interpolate(geom, z, t, gradient=True)` and
+    `loc.elements` the elements `return_element=True` reports.
+
+    The constructor makes every check `interpolate()` makes on the geometry and the points, then runs the part of the
+    work that does not depend on `z` (`mgbhip_locator_create`: location grid, points sorted by cell, element map
+    inverted per point) and leaves each point's element and reference coordinates on the device.  `evaluate` uploads
+    one `z`, runs the evaluation kernel and copies the result back.  The locator holds copies of what it needs: later
+    changes to `t` or `geom.x` do not change its results.  Use it as a context manager or call `close()`; a locator of
+    zero points needs no device and no library.
+    """
+
+    def __init__(self, geom: Geometry, t, device_id: int = 0):
+        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
+        self.closed = False
+        self._family, self._name, self._d, k, self._p, self._N, xnodes, table = _plan(geom)
+        pts, self._scalar, self._shape = _points(self._name, self._d, self._N, xnodes, t)
+        self._basis = _spectral_basis(self._family, geom)
+        self.n_points = int(pts.shape[0])
+        if self.n_points:
+            from .device import HipContext, _check, _ptr
+            pts = _c_f64(pts)
+            xnodes = None if xnodes is None else _c_f64(xnodes)
+            table = None if table is None else _c_f64(table)
+            self._ctx = HipContext(device_id)
+            h = C.c_void_p()
+            try:
+                _check(self._ctx.lib, self._ctx.lib.mgbhip_locator_create(
+                    self._ctx.handle, self._family, self._d, k, self._p, self._N, _ptr(xnodes), _ptr(table),
+                    self.n_points, _ptr(pts), C.byref(h)))
+            except Exception:
+                self._ctx.close()
+                self._ctx = None
+                raise
+            self._handle = h
+
+    def _open(self):
+        if self.closed:
+            raise ValueError("PointLocator: the locator is closed")
+
+    @property
+    def elements(self):
+        """The int32 element of each point (-1: none; the spectral families report 0, and -1 for a non-finite point),
+        shaped like the points' leading axes (one point given as `(d,)` or a scalar: an int), as
+        `interpolate(..., return_element=True)` reports it."""
+        self._open()
+        elem = np.zeros(self.n_points, dtype=np.int32)
+        if self.n_points:
+            from .device import _check
+            _check(self._ctx.lib, self._ctx.lib.mgbhip_locator_elements(
+                self._handle, elem.ctypes.data_as(C.POINTER(C.c_int32))))
+        return _shape_elements(elem, self._scalar, self._shape)
+
+    def evaluate(self, z, gradient: bool = False):
+        """`interpolate(geom, z, t)` at the located points, or `(values, grads)` with `gradient=True`; shapes, the vector /
+        matrix rule for `z` and the errors are those of `interpolate()`."""
+        self._open()
+        Z, single = _columns(self._name, self._p, self._N, z)
+        M, ncomp, d = self.n_points, Z.shape[1], self._d
+        out = np.empty((M, ncomp))
+        grad = np.empty((M, ncomp, d)) if gradient else None
+        if M:
+            from .device import _check, _ptr
+            Zd = _c_f64(_spectral_coefficients(self._family, self._basis, Z))
+            _check(self._ctx.lib, self._ctx.lib.mgbhip_locator_evaluate(
+                self._handle, ncomp, _ptr(Zd), _ptr(out), _ptr(grad)))
+        vals, g = _shape_values(out, grad, d, single, self._scalar, self._shape)
+        return (vals, g) if gradient else vals
+
+    def close(self):
+        """Free the device state; calling it again does nothing."""
+        self.closed = True
+        if self._handle is not None:
+            self._ctx.lib.mgbhip_locator_destroy(self._handle)
+            self._handle = None
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
