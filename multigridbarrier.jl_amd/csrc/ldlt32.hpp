@@ -1,5 +1,5 @@
 // 32 x 32 LDL' of a diagonal block on ONE wave with the trailing updates on the fp64 matrix cores.
-// Included by mf_numeric.hip (inside its namespace, after fast_recip / readlane_f64) and by tools/micro/ldlt32_mfma_test.hip.
+// Included by mf_big_inv.hpp (inside its namespace, after fast_recip / readlane_f64 of mf_device.hpp) and by tools/micro/ldlt32_mfma_test.hip.
 #pragma once
 
 struct Blk4 { double w10, w20, w21, w30, w31, w32, i0, i1, i2, i3, d0, d1, d2, d3; };

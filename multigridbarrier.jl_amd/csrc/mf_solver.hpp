@@ -33,6 +33,26 @@ struct MfLaunch {          // one kernel launch: a contiguous range of fronts of
                            // over ranks (MfSolver::iface_reduce), then factored redundantly on every rank
 };
 
+// Device arrays of the factorization in progress / of one triangular sweep, as the launchers beside the kernels
+// (mf_small.hpp, mf_big_subst.hpp, mf_big_inv.hpp) hand them on.
+struct FactorArgs {
+    const FrontDev* fr;
+    const int32_t *children, *rel, *a_src, *a_dst, *a_colptr;
+    const double* values;
+    double *arena, *dscr, *dvec;
+    int32_t* status;
+    hipStream_t st;
+};
+struct SolveArgs {
+    const FrontDev* fr;
+    const int32_t *front_idx, *children, *rel;
+    const int64_t *ug_ptr, *ug_src;
+    const double *arena, *dvec;
+    const double* b;                    // forward sweep: right-hand side
+    double *y, *x, *uvec, *tbig, *tsol; // x: backward sweep only
+    hipStream_t st;
+};
+
 class MfSolver {
    public:
     MfPlan plan;
@@ -102,8 +122,11 @@ class MfSolver {
     bool factored_inv = false;
 
    private:
-    bool launch_big_assemble(const MfLaunch& L, dim3 grid, const double* d_values, const int32_t* a_src_p, hipStream_t st,
-                             bool with_diag);     // returns true when block 0 of every front was factored by the launch
+    void upload_plan(hipStream_t st);     // analyze(): plan arrays and work buffers
+    SolveArgs solve_args(const double* d_b, double* d_x, hipStream_t st) const {
+        return {d_fronts.p, d_front_idx.p, d_children.p, d_rel.p, d_ug_ptr.p, d_ug_src.p, d_arena.p, d_dvec.p, d_b, d_y.p, d_x,
+                d_uvec.p, d_tbig.p, d_tsol.p, st};
+    }
     void forward_pass(const double* d_b_np1, hipStream_t st, StageTimers* timers);
     void backward_pass(double* d_x_np1, hipStream_t st, StageTimers* timers);
     DevBuf<double> d_bx, d_xx, d_one;     // bordered right-hand side / solution of solve(), the constant 1
@@ -121,9 +144,6 @@ class MfSolver {
     DevBuf<FrontDev> d_fronts_c;
     DevBuf<int32_t> d_a_src_c, d_a_dst_c, d_a_colptr_c;
     DevBuf<LeafDesc> d_leaf_desc;
-    const FrontDev* cur_fr = nullptr;     // arrays of the factorization in progress
-    const int32_t* cur_adst = nullptr;
-    const int32_t* cur_acol = nullptr;
     std::vector<std::vector<MfLaunch>> level_launches;   // per level, leaves first (factorization: one per LDS class)
     std::vector<std::vector<MfLaunch>> level_solves;     // triangular solves: all LDS-class fronts of a level in one launch
     int32_t lds_cap = 88;           // largest m factored out of LDS
