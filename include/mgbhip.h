@@ -334,6 +334,34 @@ int mgbhip_locator_evaluate(mgbhip_locator* loc, int32_t ncomp, const double* z 
                             double* grad /* M x ncomp x d, or NULL: values only */);
 int mgbhip_locator_destroy(mgbhip_locator* loc); /* NULL is a no-op */
 
+/* ---- level sets: level curves (d = 2) and isosurfaces (d = 3) of an element-space function ------------------------
+ * Every element is sampled on a uniform reference lattice of refine + 1 points per axis (Q_k; axis 0 fastest) or on
+ * the barycentric lattice of the refine-fold uniform subdivision (P1 / P2) with its own basis; a lattice square is
+ * split into two triangles along the diagonal from corner [i, j] to [i+1, j+1], a lattice cube into the six Kuhn
+ * tetrahedra around the diagonal from [i, j, k] to [i+1, j+1, k+1]; every simplex is cut linearly at every level
+ * [a vertex with value >= level is above; a simplex with a non-finite vertex value emits nothing].  The result is an
+ * unindexed list of S simplices of d vertices each: segments [d = 2] or triangles [d = 3].
+ *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1 and P2
+ *    [straight elements] are accepted.
+ *  - fields is (p*N) x nfield row-major, 1 <= nfield <= 5: column 0 is contoured, the others are carried along and
+ *    interpolated linearly to every vertex of the result.
+ *  - levels: nlevels finite values [nlevels = 0 gives S = 0]; duplicates are separate levels.
+ *  - refine: 1..16 for d = 2, 1..8 for d = 3.
+ * Order of the simplices: element, lattice cell, simplex of the cell, level index, triangle of a 2-2 split of a
+ * tetrahedron.  It is produced by a count pass, an exclusive scan and an emit pass, without atomics: two calls return
+ * bitwise equal arrays.  create leaves the result on the device and reports S; fetch copies it out: points S x d x d
+ * [simplex, vertex, coordinate], level S [index into levels], element S, carried S x d x (nfield - 1) or NULL.  The
+ * handle belongs to the context it was created from and must be destroyed before it.  Host pointers; the work runs
+ * on ctx's stream and is complete on return.                                                                       */
+typedef struct mgbhip_contour mgbhip_contour;
+int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                          const double* x, const double* table, int32_t nfield /* 1 + ncarry */, const double* fields,
+                          int32_t nlevels, const double* levels, int32_t refine,
+                          mgbhip_contour** out, int64_t* nsimplices);
+int mgbhip_contour_fetch(const mgbhip_contour* c, double* points, int32_t* level, int32_t* element,
+                         double* carried /* or NULL */);
+int mgbhip_contour_destroy(mgbhip_contour* c); /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

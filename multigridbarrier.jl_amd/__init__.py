@@ -26,5 +26,6 @@ try:  # the device layer needs the built shared library; importing the setup lay
                          default_device, default_device_set, mgb_cleanup, library_path)
     from .solve import mgb_solve, MGBSOL, MGBConvergenceFailure
     from .interpolate import interpolate, PointLocator
+    from .contour import isocontour, Contour
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

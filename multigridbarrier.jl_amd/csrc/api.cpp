@@ -9,6 +9,7 @@
 #include <memory>
 #include <string>
 
+#include "contour.hpp"
 #include "interpolate.hpp"
 #include "problem.hpp"
 
@@ -49,6 +50,13 @@ struct mgbhip_locator {
     Locator loc;
 };
 static int dev_of(const mgbhip_locator* l) { return (l && l->ctx) ? l->ctx->device : -1; }
+
+// a simplex soup (contour.hpp) and the context it lives in
+struct mgbhip_contour {
+    mgbhip_ctx* ctx = nullptr;
+    Contour con;
+};
+static int dev_of(const mgbhip_contour* c) { return (c && c->ctx) ? c->ctx->device : -1; }
 
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
@@ -774,6 +782,54 @@ int mgbhip_locator_destroy(mgbhip_locator* loc) {
     if (!loc) return MGBHIP_OK;
     (void)hipStreamSynchronize(loc->ctx->stream);
     delete loc;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                          const double* table, int32_t nfield, const double* fields, int32_t nlevels,
+                          const double* levels, int32_t refine, mgbhip_contour** out, int64_t* nsimplices) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr && nsimplices != nullptr, "null output pointer");
+    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
+                "contour: only the Q_k (d = 2, 3), P1 and P2 families have level sets");
+    MGB_REQUIRE(N > 0, "contour: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1 && nlevels >= 0, "contour: bad sizes");
+    MGB_REQUIRE(nfield >= 1 && nfield <= CONTOUR_MAX_FIELDS, "contour: nfield must be 1..5 (at most four carried fields)");
+    MGB_REQUIRE(fields != nullptr && (nlevels == 0 || levels != nullptr), "null argument");
+    InterpIn geo;
+    geo.family = family; geo.d = d; geo.k = k; geo.p = p; geo.N = N; geo.x = x; geo.table = table;
+    interpolate_check_geometry(geo);
+    MGB_REQUIRE(refine >= 1 && refine <= (d == 3 ? CONTOUR_MAX_REFINE_3D : CONTOUR_MAX_REFINE_2D),
+                d == 3 ? "contour: refine must be 1..8 for d = 3" : "contour: refine must be 1..16 for d = 2");
+    for (int32_t l = 0; l < nlevels; ++l) MGB_REQUIRE(std::isfinite(levels[l]), "contour: a level is not finite");
+    ContourIn in;
+    in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.nfield = nfield; in.nlevels = nlevels;
+    in.refine = refine; in.x = x; in.table = table; in.fields = fields; in.levels = levels;
+    std::unique_ptr<mgbhip_contour> c(new mgbhip_contour());
+    c->ctx = ctx;
+    contour_build(c->con, in, ctx->stream);
+    *nsimplices = c->con.S;
+    *out = c.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_contour_fetch(const mgbhip_contour* c, double* points, int32_t* level, int32_t* element, double* carried) {
+    MGB_API_BEGIN_ON(c)
+    MGB_REQUIRE(c != nullptr, "null contour");
+    MGB_REQUIRE(c->con.S == 0 || (points != nullptr && level != nullptr && element != nullptr), "null argument");
+    contour_fetch(c->con, points, level, element, carried, c->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_contour_destroy(mgbhip_contour* c) {
+    MGB_API_BEGIN_ON(c)
+    if (!c) return MGBHIP_OK;
+    (void)hipStreamSynchronize(c->ctx->stream);
+    delete c;
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -117,6 +117,7 @@ EXPORTS = [
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
     "mgbhip_prolong_add", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
+    "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy",
 ]
 
 
@@ -196,6 +197,10 @@ def load_library():
     lib.mgbhip_locator_elements.argtypes = [vp, _ip]
     lib.mgbhip_locator_evaluate.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     lib.mgbhip_locator_destroy.argtypes = [vp]
+    lib.mgbhip_contour_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32,
+                                          _dp, C.c_int32, _dp, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64)]
+    lib.mgbhip_contour_fetch.argtypes = [vp, _dp, _ip, _ip, _dp]
+    lib.mgbhip_contour_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 
