@@ -362,6 +362,43 @@ int mgbhip_contour_fetch(const mgbhip_contour* c, double* points, int32_t* level
                          double* carried /* or NULL */);
 int mgbhip_contour_destroy(mgbhip_contour* c); /* NULL is a no-op */
 
+/* ---- ray casting: line integrals and volume rendering of an element-space function --------------------------------
+ * R rays x = origin + t dir [R x d each, row-major; dir of unit length, so t is arc length] are clipped to
+ * [t_min, t_max] and against the axis-parallel box [box: 2 d doubles, lo then hi] by the slab test: for an axis a with
+ * dir[a] != 0, t1 = (lo[a] - o[a]) / dir[a], t2 = (hi[a] - o[a]) / dir[a], tmin = max(tmin, min(t1, t2)), tmax =
+ * min(tmax, max(t1, t2)); an axis with dir[a] == 0 misses unless lo[a] <= o[a] <= hi[a]; a ray with !(tmax > tmin) has
+ * no samples.  Otherwise it has n = max(1, floor((tmax - tmin) / step + 0.5)) samples of step h = (tmax - tmin) / n, sample
+ * i at t = tmin + (i + 0.5) h, x[a] = o[a] + t dir[a] [no fused multiply-add].  create lays the samples out ray by ray
+ * [count pass, exclusive scan, emit pass; no atomics], locates them like mgbhip_locator_create and keeps per sample the
+ * element and the reference coordinates on the device; it reports the number of samples S, and S > 2^31 - 1 is
+ * MGBHIP_ERR_INVALID before the sample arrays are allocated.
+ *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1 and P2
+ *    [straight elements] are accepted.  R = 0 is allowed.
+ *  - offsets [R + 1]: ray r owns samples offsets[r] .. offsets[r + 1] - 1.  samples [S x d]: the positions, regenerated.
+ *  - lengths: step[r] = h of ray r [0 without samples], length[r] = h x the number of its samples that lie in an
+ *    element; either pointer may be NULL.
+ *  - integrate: z is (p*N) x ncomp; out[r, c] = h x the sum, in sample order, of the finite values of column c at the
+ *    samples of ray r [a sample outside the mesh has the value NaN].
+ *  - render: u is p*N values, transfer K x 4 rows of (r, g, b, sigma), K >= 2, finite, sigma >= 0 per unit length;
+ *    lo < hi finite.  Front to back from T = 1, C = 0, per sample with a finite value v: s = min(1, max(0, (v - lo) /
+ *    (hi - lo))), f = s (K - 1), j = min(floor(f), K - 2), w = f - j, row = T[j] + w (T[j+1] - T[j]), e = exp(-(sigma h)),
+ *    C += (T (1 - e)) row_rgb, T = T e.  out [R x 4] = (C_r, C_g, C_b, 1 - T): premultiplied colour and alpha.
+ * The handle belongs to the context it was created from and must be destroyed before it.  Host pointers; the work runs
+ * on ctx's stream and is complete on return.                                                                        */
+typedef struct mgbhip_raycast mgbhip_raycast;
+int mgbhip_raycast_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                          const double* x, const double* table, int64_t R, const double* origin, const double* dir,
+                          const double* box, double step, double t_min, double t_max,
+                          mgbhip_raycast** out, int64_t* nsamples);
+int mgbhip_raycast_offsets(const mgbhip_raycast* rc, int64_t* offsets /* R + 1 */);
+int mgbhip_raycast_samples(const mgbhip_raycast* rc, double* pts /* S x d */);
+int mgbhip_raycast_lengths(const mgbhip_raycast* rc, double* step /* R or NULL */, double* length /* R or NULL */);
+int mgbhip_raycast_integrate(mgbhip_raycast* rc, int32_t ncomp, const double* z /* (p*N) x ncomp */,
+                             double* out /* R x ncomp */);
+int mgbhip_raycast_render(mgbhip_raycast* rc, const double* u /* p*N */, int32_t K, const double* transfer /* K x 4 */,
+                          double lo, double hi, double* out /* R x 4 */);
+int mgbhip_raycast_destroy(mgbhip_raycast* rc); /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,5 +27,6 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .solve import mgb_solve, MGBSOL, MGBConvergenceFailure
     from .interpolate import interpolate, PointLocator
     from .contour import isocontour, Contour
+    from .raycast import RayCaster, camera_rays, render_volume
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

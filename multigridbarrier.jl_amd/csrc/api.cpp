@@ -12,6 +12,7 @@
 #include "contour.hpp"
 #include "interpolate.hpp"
 #include "problem.hpp"
+#include "raycast.hpp"
 
 using namespace mgbhip;
 
@@ -57,6 +58,13 @@ struct mgbhip_contour {
     Contour con;
 };
 static int dev_of(const mgbhip_contour* c) { return (c && c->ctx) ? c->ctx->device : -1; }
+
+// a ray caster (raycast.hpp) and the context it lives in
+struct mgbhip_raycast {
+    mgbhip_ctx* ctx = nullptr;
+    RayCaster rc;
+};
+static int dev_of(const mgbhip_raycast* r) { return (r && r->ctx) ? r->ctx->device : -1; }
 
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
@@ -830,6 +838,101 @@ int mgbhip_contour_destroy(mgbhip_contour* c) {
     if (!c) return MGBHIP_OK;
     (void)hipStreamSynchronize(c->ctx->stream);
     delete c;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                          const double* table, int64_t R, const double* origin, const double* dir, const double* box,
+                          double step, double t_min, double t_max, mgbhip_raycast** out, int64_t* nsamples) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr && nsamples != nullptr, "null output pointer");
+    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
+                "raycast: only the Q_k (d = 2, 3), P1 and P2 families are ray cast");
+    MGB_REQUIRE(N > 0, "raycast: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1 && R >= 0 && R < (int64_t)INT32_MAX, "raycast: bad sizes");
+    MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && box != nullptr), "null argument");
+    RayIn in;
+    in.geo.family = family; in.geo.d = d; in.geo.k = k; in.geo.p = p; in.geo.N = N; in.geo.x = x; in.geo.table = table;
+    interpolate_check_geometry(in.geo);
+    MGB_REQUIRE(std::isfinite(step) && step > 0.0, "raycast: step must be finite and positive");
+    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, "raycast: t_min must be finite and t_max > t_min");
+    for (int64_t i = 0; i < R * d; ++i)
+        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "raycast: origins and directions must be finite");
+    for (int64_t r = 0; r < R; ++r) {
+        double s = 0.0;
+        for (int a = 0; a < d; ++a) s += dir[r * d + a] * dir[r * d + a];
+        MGB_REQUIRE(std::fabs(s - 1.0) <= 1e-12, "raycast: directions must have unit length");
+    }
+    for (int a = 0; a < d && R > 0; ++a)
+        MGB_REQUIRE(std::isfinite(box[a]) && std::isfinite(box[d + a]) && box[a] <= box[d + a], "raycast: bad clip box");
+    in.R = R; in.origin = origin; in.dir = dir; in.box = box; in.step = step; in.t_min = t_min; in.t_max = t_max;
+    std::unique_ptr<mgbhip_raycast> rc(new mgbhip_raycast());
+    rc->ctx = ctx;
+    raycast_build(rc->rc, in, ctx->stream);
+    *nsamples = rc->rc.S;
+    *out = rc.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_offsets(const mgbhip_raycast* rc, int64_t* offsets) {
+    MGB_API_BEGIN_ON(rc)
+    MGB_REQUIRE(rc != nullptr, "null ray caster");
+    MGB_REQUIRE(offsets != nullptr, "null argument");
+    raycast_offsets(rc->rc, offsets, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_samples(const mgbhip_raycast* rc, double* pts) {
+    MGB_API_BEGIN_ON(rc)
+    MGB_REQUIRE(rc != nullptr, "null ray caster");
+    MGB_REQUIRE(rc->rc.S == 0 || pts != nullptr, "null argument");
+    raycast_samples(rc->rc, pts, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_lengths(const mgbhip_raycast* rc, double* step, double* length) {
+    MGB_API_BEGIN_ON(rc)
+    MGB_REQUIRE(rc != nullptr, "null ray caster");
+    raycast_lengths(rc->rc, step, length, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_integrate(mgbhip_raycast* rc, int32_t ncomp, const double* z, double* out) {
+    MGB_API_BEGIN_ON(rc)
+    MGB_REQUIRE(rc != nullptr, "null ray caster");
+    MGB_REQUIRE(ncomp >= 1, "raycast: bad sizes");
+    MGB_REQUIRE(z != nullptr && (rc->rc.R == 0 || out != nullptr), "null argument");
+    raycast_integrate(rc->rc, ncomp, z, out, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_render(mgbhip_raycast* rc, const double* u, int32_t K, const double* transfer, double lo, double hi,
+                          double* out) {
+    MGB_API_BEGIN_ON(rc)
+    MGB_REQUIRE(rc != nullptr, "null ray caster");
+    MGB_REQUIRE(u != nullptr && transfer != nullptr && (rc->rc.R == 0 || out != nullptr), "null argument");
+    MGB_REQUIRE(K >= 2, "raycast: the transfer table needs at least two rows");
+    for (int64_t i = 0; i < (int64_t)K * 4; ++i)
+        MGB_REQUIRE(std::isfinite(transfer[i]) && (i % 4 != 3 || transfer[i] >= 0.0),
+                    "raycast: the transfer table must be finite with sigma >= 0");
+    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "raycast: clim must be finite with lo < hi");
+    raycast_render(rc->rc, u, K, transfer, lo, hi, out, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_destroy(mgbhip_raycast* rc) {
+    MGB_API_BEGIN_ON(rc)
+    if (!rc) return MGBHIP_OK;
+    (void)hipStreamSynchronize(rc->ctx->stream);
+    delete rc;
     return MGBHIP_OK;
     MGB_API_END
 }

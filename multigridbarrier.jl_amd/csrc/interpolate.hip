@@ -1179,19 +1179,26 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------------
 
 void locator_build(Locator& L, const InterpIn& in, hipStream_t st) {
-    L.family = in.family; L.d = in.d; L.k = in.k; L.p = in.p; L.N = in.N; L.M = in.M;
-    if (in.M == 0) return;
-    const int64_t rows = (int64_t)in.p * in.N;
     const bool fem = in.family <= MGBHIP_INTERP_P2;
-    if (!fem) {                                  // nothing to locate: the points are the resident state
-        L.pts.upload(in.pts, (size_t)in.M * in.d, st);
+    if (in.M == 0 || !fem) {
+        L.family = in.family; L.d = in.d; L.k = in.k; L.p = in.p; L.N = in.N; L.M = in.M;
+        if (in.M == 0) return;
+        L.pts.upload(in.pts, (size_t)in.M * in.d, st);      // nothing to locate: the points are the resident state
         MGB_HIP_CHECK(hipStreamSynchronize(st));
         return;
     }
     DevBuf<double> d_pts;                        // freed on return: the evaluation reads only (element, reference point)
+    d_pts.upload(in.pts, (size_t)in.M * in.d, st);
+    locator_build_device(L, in, d_pts.p, st);
+}
+
+void locator_build_device(Locator& L, const InterpIn& in, const double* d_pts, hipStream_t st) {
+    L.family = in.family; L.d = in.d; L.k = in.k; L.p = in.p; L.N = in.N; L.M = in.M;
+    if (in.M == 0) return;
+    MGB_REQUIRE(in.family <= MGBHIP_INTERP_P2, "interpolate: only the FEM families locate device-resident points");
+    const int64_t rows = (int64_t)in.p * in.N;
     L.x.upload(in.x, (size_t)rows * in.d, st);
     L.table.upload(in.table, (size_t)in.table_len, st);
-    d_pts.upload(in.pts, (size_t)in.M * in.d, st);
     L.elem.alloc((size_t)in.M);
     L.ref.alloc((size_t)in.M * (in.family == MGBHIP_INTERP_FEM1D ? 1 : in.d));
     if (in.family == MGBHIP_INTERP_FEM1D) L.flag.alloc((size_t)in.M);
@@ -1200,7 +1207,7 @@ void locator_build(Locator& L, const InterpIn& in, hipStream_t st) {
     a.p = in.p;
     a.x = L.x.p;
     a.table = L.table.p;
-    a.pts = d_pts.p;
+    a.pts = d_pts;
     const LocArgs l{L.elem.p, L.ref.p, L.flag.p};
     if (in.family == MGBHIP_INTERP_FEM1D) {
         launch_1d_s(in.k + 1, Pass::LOCATE, a, in.N, in.sorted, l, st);
@@ -1239,6 +1246,14 @@ void locator_elements(const Locator& L, int32_t* elem, hipStream_t st) {
 
 void locator_evaluate(Locator& L, int32_t ncomp, const double* z, double* out, double* grad, hipStream_t st) {
     if (L.M == 0) return;
+    locator_evaluate_device(L, ncomp, z, grad != nullptr, st);
+    if (out) L.out.download(out, (size_t)L.M * ncomp, st);
+    if (grad) L.grad.download(grad, (size_t)L.M * ncomp * L.d, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void locator_evaluate_device(Locator& L, int32_t ncomp, const double* z, bool grad, hipStream_t st) {
+    if (L.M == 0) return;
     const int64_t rows = (int64_t)L.p * L.N;
     // grown to the largest ncomp seen and kept: no allocation in a run of calls with the same ncomp
     L.z.upload(z, (size_t)rows * ncomp, st);
@@ -1273,9 +1288,6 @@ void locator_evaluate(Locator& L, int32_t ncomp, const double* z, double* out, d
             break;
         default: throw InvalidArgument("interpolate: unknown family");
     }
-    if (out) L.out.download(out, (size_t)L.M * ncomp, st);
-    if (grad) L.grad.download(grad, (size_t)L.M * ncomp * L.d, st);
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 }  // namespace mgbhip

@@ -40,8 +40,14 @@ struct Locator {
 
 // in.z / in.ncomp / in.out / in.grad / in.elem are not read
 void locator_build(Locator& L, const InterpIn& in, hipStream_t st);
+// the same for M points already on the device (d_pts, M x d; read, not kept; in.pts is not read): the 2-D / 3-D FEM
+// families and fem1d.  raycast.hip locates the samples it generates through this entry.
+void locator_build_device(Locator& L, const InterpIn& in, const double* d_pts, hipStream_t st);
 void locator_elements(const Locator& L, int32_t* elem, hipStream_t st);
 // z host (p*N) x ncomp; out host M x ncomp or NULL; grad host M x ncomp x d or NULL; complete on return
 void locator_evaluate(Locator& L, int32_t ncomp, const double* z, double* out, double* grad, hipStream_t st);
+// the launches of locator_evaluate alone: the values stay in L.out (M x ncomp, by point) and, with grad, the gradients
+// in L.grad; queued on st, not waited for
+void locator_evaluate_device(Locator& L, int32_t ncomp, const double* z, bool grad, hipStream_t st);
 
 }  // namespace mgbhip

@@ -1,0 +1,44 @@
+// raycast.hpp -- rays sampled through a mesh behind mgbhip_raycast_* (raycast.hip): a point locator (interpolate.hpp) whose
+// points are generated on the device, a per-ray integration kernel and a per-ray compositing kernel.
+#pragma once
+#include <cstdint>
+
+#include "../../include/mgbhip.h"
+#include "common.hpp"
+#include "interpolate.hpp"
+
+namespace mgbhip {
+
+struct RayIn {
+    InterpIn geo;                    // family, d, k, p, N, x, table (table_len set): QK (d = 2, 3), P1, P2
+    int64_t R = 0;
+    const double* origin = nullptr;  // host R x d, finite
+    const double* dir = nullptr;     // host R x d, unit length
+    const double* box = nullptr;     // host 2 d: the clip box, lo then hi
+    double step = 0.0, t_min = 0.0, t_max = 0.0;
+};
+
+// Resident: per ray the origin, the direction, the first parameter, the step, the first sample and the length in the
+// mesh; per sample what a Locator keeps (element, reference coordinates, place in the cell order) and, per call, the
+// values.  The sample positions and the location grid are freed once the samples are located.
+struct RayCaster {
+    int32_t d = 0;
+    int64_t R = 0, S = 0;
+    DevBuf<double> origin, dir, tmin, h, length;   // R x d, R x d, R, R, R
+    DevBuf<int64_t> off;                           // R + 1
+    Locator loc;                                   // M = S
+    DevBuf<double> transfer, result;               // per call: grown to the largest seen and kept
+};
+
+// count pass, exclusive scan over the rays, emit pass, location; complete on return (RC.S is known)
+void raycast_build(RayCaster& RC, const RayIn& in, hipStream_t st);
+void raycast_offsets(const RayCaster& RC, int64_t* offsets, hipStream_t st);                 // R + 1
+void raycast_lengths(const RayCaster& RC, double* step, double* length, hipStream_t st);     // R, R (either may be NULL)
+void raycast_samples(const RayCaster& RC, double* pts, hipStream_t st);                      // S x d, regenerated
+// z host (p*N) x ncomp, out host R x ncomp: h_r * sum of the finite sample values, in sample order
+void raycast_integrate(RayCaster& RC, int32_t ncomp, const double* z, double* out, hipStream_t st);
+// u host p*N, transfer host K x 4 (r, g, b, sigma), out host R x 4: front-to-back emission-absorption compositing
+void raycast_render(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi, double* out,
+                    hipStream_t st);
+
+}  // namespace mgbhip

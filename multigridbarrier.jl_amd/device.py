@@ -118,6 +118,8 @@ EXPORTS = [
     "mgbhip_prolong_add", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy",
+    "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
+    "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy",
 ]
 
 
@@ -201,6 +203,15 @@ def load_library():
                                           _dp, C.c_int32, _dp, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.mgbhip_contour_fetch.argtypes = [vp, _dp, _ip, _ip, _dp]
     lib.mgbhip_contour_destroy.argtypes = [vp]
+    lib.mgbhip_raycast_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int64,
+                                          _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.POINTER(vp),
+                                          C.POINTER(C.c_int64)]
+    lib.mgbhip_raycast_offsets.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.mgbhip_raycast_samples.argtypes = [vp, _dp]
+    lib.mgbhip_raycast_lengths.argtypes = [vp, _dp, _dp]
+    lib.mgbhip_raycast_integrate.argtypes = [vp, C.c_int32, _dp, _dp]
+    lib.mgbhip_raycast_render.argtypes = [vp, _dp, C.c_int32, _dp, C.c_double, C.c_double, _dp]
+    lib.mgbhip_raycast_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 
