@@ -273,6 +273,16 @@ int mgbhip_solver_stats(mgbhip_problem* prob, int32_t level, double* out8);
  * [6] doubles the trailing updates move beyond one pass over the arena, [7] reserved.  The reference's counterpart is
  * opaque (cuDSS FACTORIZATION + SOLVE per Newton iteration, ext/MultiGridBarrierCUDAExt/cudss_solver.jl:279-288). */
 int mgbhip_solver_chain(mgbhip_problem* prob, int32_t level, double* out8);
+/* Which kernels the shape gates of a level selected (inspection only; nothing is computed or built).  out[0] R_unit
+ * (prolongation fused into the element kernel), [1] R_long (a row of R longer than 64: wave per row), [2] T_long (a column
+ * of R longer than 64: wave per row of R'), [3] T_chunks (> 0: chunked restriction, chunks per row of R'), [4] bit 0: selection
+ * level, bit 1: direct values, [5] acc (LDS accumulation), [6] acc_split, [7] long_lists (wave per contribution list),
+ * [8] gather_chunk, [9] gather_nchunk (> 1: two-stage gather), [10] projection kernel of the last f2 (MGBHIP_PROJ_*),
+ * [11] longest row of R, [12] longest column of R, [13] cmax (widest per-state column set of an element), [14] mean
+ * contribution-list length (integer quotient), [15] 1 once the assembly plan exists (the first f2 of the level builds it;
+ * [4]..[10], [13] and [14] describe it and are zero / defaults before).                                                   */
+enum { MGBHIP_PROJ_NONE = 0, MGBHIP_PROJ_LOOP = 1, MGBHIP_PROJ_STAGED = 2, MGBHIP_PROJ_MFMA = 3, MGBHIP_PROJ_ACCUMULATE = 4 };
+int mgbhip_level_plan(mgbhip_problem* prob, int32_t level, int32_t* out16);
 
 /* ---- point evaluation (reference: `interpolate`, src/utils.jl:16-58) ---------------------------------------------
  * out[q, c] = the element-space function with broken-basis values z[:, c] at point q, for M points pts (M x d,

@@ -177,6 +177,31 @@ static void check_level(mgbhip_problem* P, int32_t level) {
     MGB_REQUIRE(level >= 0 && level < (int32_t)P->levels.size(), "level out of range");
 }
 
+int mgbhip_level_plan(mgbhip_problem* P, int32_t level, int32_t* out) {
+    MGB_API_BEGIN
+    check_level(P, level);
+    MGB_REQUIRE(out != nullptr, "null argument");
+    const Level& L = P->levels[level];
+    out[0] = L.R_unit;
+    out[1] = L.R_long;
+    out[2] = L.T_long;
+    out[3] = L.T_chunks;
+    out[4] = (L.selection ? 1 : 0) | (L.direct ? 2 : 0);
+    out[5] = L.acc;
+    out[6] = L.acc_split;
+    out[7] = L.long_lists;
+    out[8] = L.gather_chunk;
+    out[9] = L.gather_nchunk;
+    out[10] = L.proj_kernel;
+    out[11] = L.max_row;
+    out[12] = L.max_col;
+    out[13] = L.cmax;
+    out[14] = L.nnz > 0 ? (int32_t)(L.list_total / L.nnz) : 0;
+    out[15] = L.planned;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
 static void stage_inputs(mgbhip_problem* P, int32_t level, const double* s, const double* c, const double* z0) {
     hipStream_t st = P->stream();
     P->d_x.upload(s, (size_t)P->levels[level].m, st);

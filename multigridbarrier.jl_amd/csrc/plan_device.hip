@@ -239,6 +239,7 @@ void build_plan_device(const PlanDeviceIn& in, Level& L, hipStream_t st) {
     L.Hcol.download(L.hHcol.data(), (size_t)nnz, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     L.long_lists = nnz > 0 && total / nnz > 48;
+    L.list_total = total;
     // direct-value map (selection levels): lets the solver read single-contribution entries straight from the slab
     L.direct = false;
     if (in.selection && in.extra_base > 0 && nnz > 0 && in.extra_base + nnz + m + 1 < (int64_t)INT32_MAX) {

@@ -71,6 +71,8 @@ static void upload_csr(const mgbhip_csr& R, Level& L, hipStream_t st) {
     int32_t maxr = 0;
     for (int64_t i = 0; i < R.rows; ++i) maxr = std::max(maxr, L.hRptr[i + 1] - L.hRptr[i]);
     L.R_long = maxr > 64;
+    L.max_row = maxr;
+    L.max_col = maxrow;
     {   // selection rows: the element kernels read s through the column map and no prolongation kernel runs
         bool unit = maxr <= 1 && getenv("MGBHIP_NO_FUSED_PROLONG") == nullptr;
         for (int64_t q = 0; q < nnz && unit; ++q) unit = L.hRval[q] == 1.0;
@@ -622,6 +624,7 @@ void mgbhip_problem::ensure_plan(int level) {
             ccount[q + 1] += ccount[q];
         }
         L.long_lists = L.nnz > 0 && total / L.nnz > 48;
+        L.list_total = total;
         std::vector<int32_t> fill(ccount.begin(), ccount.end() - 1);
         std::vector<int32_t> cidx((size_t)total);
         for (size_t t = 0; t < ppos.size(); ++t) cidx[fill[ppos[t]]++] = psrc[t];   // element order within a list
@@ -938,6 +941,7 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
         zf_stamp = -1;              // nothing ran: base_params may have promised d_zfull to a kernel that was not launched
     }
     L.H_condensed = false;
+    L.proj_kernel = MGBHIP_PROJ_NONE;
     {
         // fine-level launches are timed apart: they are the ones the HBM roofline is quoted on
         StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "f2" : "f2_coarse");
@@ -977,6 +981,7 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
             const bool upper = !materialize && rhs != nullptr && L.nup > 0 && !L.acc && !full_h;
             PP.upper_only = upper ? 1 : 0;
             if (L.acc) {
+                L.proj_kernel = MGBHIP_PROJ_ACCUMULATE;
                 launch_panel_accumulate(PP, L.ecols.p, (int32_t)L.m, L.acc_waves, L.acc_split, L.acc_chunk, L.acc_ctmax,
                                         L.acc_copies.p, L.Hval.p, st);
             } else {
@@ -984,8 +989,14 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
                 // the two products of the projection on the matrix cores; the loop kernels remain for elements whose
                 // staging does not fit (staged variant while four workgroups still fit a CU: narrow supports)
                 if (launch_panel_project_mfma(PP, st)) {
-                } else if (panel_accumulate_lds(p, nu, L.acc_ctmax) <= 40 * 1024) launch_panel_project_staged(PP, L.acc_ctmax, st);
-                else launch_panel_project(PP, st);
+                    L.proj_kernel = MGBHIP_PROJ_MFMA;
+                } else if (panel_accumulate_lds(p, nu, L.acc_ctmax) <= 40 * 1024) {
+                    L.proj_kernel = MGBHIP_PROJ_STAGED;
+                    launch_panel_project_staged(PP, L.acc_ctmax, st);
+                } else {
+                    L.proj_kernel = MGBHIP_PROJ_LOOP;
+                    launch_panel_project(PP, st);
+                }
                 launch_gather_assemble(L.nnz, L.cptr.p, L.sorted_slab ? nullptr : L.cidx.p, L.slab.p, L.Hval.p, L.long_lists, st, L.gather_chunk,
                                        L.gather_nchunk, L.gather_part.p, upper ? L.upq.p : nullptr, upper ? L.nup : 0);
             }

@@ -41,6 +41,7 @@ struct Level {
     DevBuf<int32_t> Rptr, Rcol, Tptr, Tcol;
     DevBuf<double> Rval, Tval;
     bool T_long = false, R_long = false;
+    int32_t max_row = 0, max_col = 0;      // longest row / column of R (what the gates above were decided from)
     bool R_unit = false;                  // every row of R: at most one entry, equal to 1 -> the element kernels prolong (Rsel)
     DevBuf<int32_t> Rsel;
     int32_t T_chunks = 0;                 // > 0: rows of R' are long enough for the chunked matvec
@@ -59,6 +60,8 @@ struct Level {
     int64_t slab_doubles = 0;
     int32_t cmax = 1;
     bool long_lists = false;
+    int64_t list_total = 0;               // summands over all contribution lists (mean list length = list_total / nnz)
+    int32_t proj_kernel = 0;              // projection kernel of the last eval_f2 (MGBHIP_PROJ_* of include/mgbhip.h)
     int32_t gather_chunk = 0, gather_nchunk = 0;   // very long lists: two-stage gather (chunk length, chunks per list)
     DevBuf<double> gather_part;
     DevBuf<int32_t> upq;                  // general (projected) levels: CSR positions with col >= row, what the Newton loop assembles

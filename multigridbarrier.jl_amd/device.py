@@ -115,7 +115,7 @@ EXPORTS = [
     "mgbhip_vec_alloc", "mgbhip_vec_free", "mgbhip_vec_len", "mgbhip_vec_upload", "mgbhip_vec_download",
     "mgbhip_vec_fill", "mgbhip_vec_copy", "mgbhip_vec_axpy", "mgbhip_vec_scale", "mgbhip_vec_dot",
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
-    "mgbhip_prolong_add", "mgbhip_interpolate", "mgbhip_interpolate_grad",
+    "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy",
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
@@ -171,6 +171,7 @@ def load_library():
     lib.mgbhip_reset_stage_timers.argtypes = [C.c_void_p, C.c_int]
     lib.mgbhip_solver_stats.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.mgbhip_solver_chain.argtypes = [C.c_void_p, C.c_int32, _dp]
+    lib.mgbhip_level_plan.argtypes = [C.c_void_p, C.c_int32, _ip]
     vp = C.c_void_p
     lib.mgbhip_vec_alloc.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     lib.mgbhip_vec_free.argtypes = [vp]
@@ -635,6 +636,25 @@ class DeviceProblem:
         keys = ("pivot_blocks_on_critical_path", "large_front_tree_levels", "launches_per_factorization",
                 "launches_per_backward_sweep", "arena_doubles", "factor_flops", "extra_trailing_doubles", "reserved")
         return dict(zip(keys, out.tolist()))
+
+    PLAN_KEYS = ("R_unit", "R_long", "T_long", "T_chunks", "selection", "acc", "acc_split", "long_lists", "gather_chunk",
+                 "gather_nchunk", "projection", "max_row", "max_col", "cmax", "mean_list", "planned")
+    PROJECTION = ("none", "loop", "staged", "mfma", "accumulate")
+
+    def level_plan(self, level: int) -> dict:
+        """Which kernels the shape gates of `level` selected (`mgbhip_level_plan`): read-only, nothing is built.  The assembly
+        fields describe the plan that the first f2 of the level builds (`planned`); `projection` names the projection kernel
+        of the last f2; `selection`: every row of R has at most one entry, equal to 1; `direct`: the solver reads the values
+        of such a level straight from the element blocks."""
+        out = (C.c_int32 * 16)()
+        _check(self.lib, self.lib.mgbhip_level_plan(self.handle, level, out))
+        d = dict(zip(self.PLAN_KEYS, (int(v) for v in out)))
+        d["projection"] = self.PROJECTION[d["projection"]]
+        d["direct"] = bool(d["selection"] & 2)
+        d["selection"] = bool(d["selection"] & 1)
+        for k in ("R_unit", "R_long", "T_long", "acc", "long_lists", "planned"):
+            d[k] = bool(d[k])
+        return d
 
     def close(self):
         if self.handle:
