@@ -408,6 +408,44 @@ int mgbhip_raycast_integrate(mgbhip_raycast* rc, int32_t ncomp, const double* z 
 int mgbhip_raycast_render(mgbhip_raycast* rc, const double* u /* p*N */, int32_t K, const double* transfer /* K x 4 */,
                           double lo, double hi, double* out /* R x 4 */);
 int mgbhip_raycast_destroy(mgbhip_raycast* rc); /* NULL is a no-op */
+/* render with nhits [1..8] layers per ray merged into the samples by depth: t_hit [R x nhits] ascends along every ray
+ * [+inf: no layer], layer [R x nhits x 4] holds finite premultiplied colour and alpha.  From T = 1, C = 0 the layers
+ * with t_hit <= t_i are applied before sample i [t_i = tmin + (i + 0.5) h], the finite ones that remain after the last
+ * sample; a layer does C += T layer_rgb, T = T (1 - layer_alpha); a sample does what render does.  A ray without
+ * samples composites its layers alone.                                                                              */
+int mgbhip_raycast_render_layers(mgbhip_raycast* rc, const double* u /* p*N */, int32_t K,
+                                 const double* transfer /* K x 4 */, double lo, double hi, int32_t nhits,
+                                 const double* t_hit /* R x nhits */, const double* layer /* R x nhits x 4 */,
+                                 double* out /* R x 4 */);
+
+/* ---- rays against a triangle soup: nearest hits and their shading ---------------------------------------------------
+ * create uploads T triangles [points: T x 3 x 3, triangle, vertex, coordinate; finite; T = 0 is allowed] and sorts them
+ * into a uniform grid of cells [boxes, union, count pass, exclusive scan, emit pass, stable radix sort by cell; no
+ * atomics].  The grid decides only which triangles a ray is tested against, never the result.
+ *  - trace: R rays x = origin + t dir [dir of unit length].  With v0, v1, v2 the vertices of a triangle, a x b the cross
+ *    product [(a x b)[0] = a1 b2 - a2 b1, cyclically] and a . b = (a0 b0 + a1 b1) + a2 b2, without fused multiply-add:
+ *      e1 = v1 - v0, e2 = v2 - v0, p = dir x e2, det = e1 . p, s = origin - v0, u = (s . p) / det, q = s x e1,
+ *      v = (dir . q) / det, t = (e2 . q) / det.
+ *    The triangle is hit iff det is finite and non-zero, u >= 0, v >= 0, u + v <= 1 and t_min <= t <= t_max [two-sided].
+ *    Per ray the K [1..8] nearest hits in the order of (t, triangle index) are written to t, tri, u, v [R x K each];
+ *    a missing entry is t = +inf, tri = -1, u = v = NaN.
+ *  - shade: tri, u, v as trace returned them; values [T x 3] is a value per triangle vertex, table [Kt x 4] rows of
+ *    (r, g, b, alpha) looked up as render looks up its table: c = ((1 - u - v) c0 + u c1) + v c2, s = min(1, max(0, (c -
+ *    lo) / (hi - lo))), f = s (Kt - 1), j = min(floor(f), Kt - 2), w = f - j, row = table[j] + w (table[j+1] - table[j]);
+ *    n = e1 x e2, nn = n / sqrt(n . n), shade = ambient + (1 - ambient) |nn . dir|, alpha = min(1, max(0, row[3]));
+ *    layer [R x K x 4] = ((alpha shade) r, (alpha shade) g, (alpha shade) b, alpha); a missing hit or a non-finite c
+ *    gives a zero layer.
+ * The handle belongs to the context it was created from and must be destroyed before it.  Host pointers; the work runs
+ * on ctx's stream and is complete on return.                                                                        */
+typedef struct mgbhip_surface mgbhip_surface;
+int mgbhip_surface_create(mgbhip_ctx* ctx, int64_t T, const double* points /* T x 3 x 3 */, mgbhip_surface** out);
+int mgbhip_surface_trace(mgbhip_surface* s, int64_t R, const double* origin, const double* dir, double t_min,
+                         double t_max, int32_t K, double* t, int32_t* tri, double* u, double* v /* R x K each */);
+int mgbhip_surface_shade(mgbhip_surface* s, int64_t R, int32_t K, const double* dir, const int32_t* tri,
+                         const double* u, const double* v, const double* values /* T x 3 */, int32_t Kt,
+                         const double* table /* Kt x 4 */, double lo, double hi, double ambient,
+                         double* layer /* R x K x 4 */);
+int mgbhip_surface_destroy(mgbhip_surface* s); /* NULL is a no-op */
 
 #ifdef __cplusplus
 }

@@ -28,5 +28,6 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .interpolate import interpolate, PointLocator
     from .contour import isocontour, Contour
     from .raycast import RayCaster, camera_rays, render_volume
+    from .surface import TriangleCaster, Hits, render_surfaces, render_figure
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

@@ -13,6 +13,7 @@
 #include "interpolate.hpp"
 #include "problem.hpp"
 #include "raycast.hpp"
+#include "surface.hpp"
 
 using namespace mgbhip;
 
@@ -65,6 +66,13 @@ struct mgbhip_raycast {
     RayCaster rc;
 };
 static int dev_of(const mgbhip_raycast* r) { return (r && r->ctx) ? r->ctx->device : -1; }
+
+// a triangle soup in its grid (surface.hpp) and the context it lives in
+struct mgbhip_surface {
+    mgbhip_ctx* ctx = nullptr;
+    Surface sf;
+};
+static int dev_of(const mgbhip_surface* s) { return (s && s->ctx) ? s->ctx->device : -1; }
 
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
@@ -958,6 +966,98 @@ int mgbhip_raycast_destroy(mgbhip_raycast* rc) {
     if (!rc) return MGBHIP_OK;
     (void)hipStreamSynchronize(rc->ctx->stream);
     delete rc;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_raycast_render_layers(mgbhip_raycast* rc, const double* u, int32_t K, const double* transfer, double lo,
+                                 double hi, int32_t nhits, const double* t_hit, const double* layer, double* out) {
+    MGB_API_BEGIN_ON(rc)
+    MGB_REQUIRE(rc != nullptr, "null ray caster");
+    MGB_REQUIRE(u != nullptr && transfer != nullptr && (rc->rc.R == 0 || (out != nullptr && t_hit != nullptr && layer != nullptr)),
+                "null argument");
+    MGB_REQUIRE(K >= 2, "raycast: the transfer table needs at least two rows");
+    MGB_REQUIRE(nhits >= 1 && nhits <= SURFACE_MAX_HITS, "raycast: the number of layers per ray must be 1..8");
+    for (int64_t i = 0; i < (int64_t)K * 4; ++i)
+        MGB_REQUIRE(std::isfinite(transfer[i]) && (i % 4 != 3 || transfer[i] >= 0.0),
+                    "raycast: the transfer table must be finite with sigma >= 0");
+    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "raycast: clim must be finite with lo < hi");
+    for (int64_t r = 0; r < rc->rc.R; ++r)
+        for (int32_t k = 0; k < nhits; ++k) {
+            const double th = t_hit[r * nhits + k];
+            MGB_REQUIRE(!std::isnan(th) && (k == 0 || t_hit[r * nhits + k - 1] <= th),
+                        "raycast: the layer depths of a ray must ascend (+inf for a missing layer)");
+            for (int c = 0; c < 4; ++c)
+                MGB_REQUIRE(std::isfinite(layer[(r * nhits + k) * 4 + c]), "raycast: every layer entry must be finite");
+        }
+    raycast_render_layers(rc->rc, u, K, transfer, lo, hi, nhits, t_hit, layer, out, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_surface_create(mgbhip_ctx* ctx, int64_t T, const double* points, mgbhip_surface** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(T >= 0 && T < (int64_t)INT32_MAX / 9, "surface: bad sizes");
+    MGB_REQUIRE(T == 0 || points != nullptr, "null argument");
+    for (int64_t i = 0; i < T * 9; ++i) MGB_REQUIRE(std::isfinite(points[i]), "surface: every vertex must be finite");
+    std::unique_ptr<mgbhip_surface> s(new mgbhip_surface());
+    s->ctx = ctx;
+    surface_build(s->sf, T, points, ctx->stream);
+    *out = s.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_surface_trace(mgbhip_surface* s, int64_t R, const double* origin, const double* dir, double t_min,
+                         double t_max, int32_t K, double* t, int32_t* tri, double* u, double* v) {
+    MGB_API_BEGIN_ON(s)
+    MGB_REQUIRE(s != nullptr, "null surface");
+    MGB_REQUIRE(K >= 1 && K <= SURFACE_MAX_HITS, "surface: K must be 1..8");
+    MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * SURFACE_MAX_HITS), "surface: bad sizes");
+    MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && t != nullptr && tri != nullptr && u != nullptr && v != nullptr),
+                "null argument");
+    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, "surface: t_min must be finite and t_max > t_min");
+    for (int64_t i = 0; i < R * 3; ++i)
+        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "surface: origins and directions must be finite");
+    for (int64_t r = 0; r < R; ++r) {
+        double q = 0.0;
+        for (int a = 0; a < 3; ++a) q += dir[r * 3 + a] * dir[r * 3 + a];
+        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, "surface: directions must have unit length");
+    }
+    surface_trace(s->sf, R, origin, dir, t_min, t_max, K, t, tri, u, v, s->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_surface_shade(mgbhip_surface* s, int64_t R, int32_t K, const double* dir, const int32_t* tri, const double* u,
+                         const double* v, const double* values, int32_t Kt, const double* table, double lo, double hi,
+                         double ambient, double* layer) {
+    MGB_API_BEGIN_ON(s)
+    MGB_REQUIRE(s != nullptr, "null surface");
+    MGB_REQUIRE(K >= 1 && K <= SURFACE_MAX_HITS, "surface: K must be 1..8");
+    MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * SURFACE_MAX_HITS), "surface: bad sizes");
+    MGB_REQUIRE(R == 0 || (dir != nullptr && tri != nullptr && u != nullptr && v != nullptr && layer != nullptr),
+                "null argument");
+    MGB_REQUIRE(table != nullptr && (s->sf.T == 0 || values != nullptr), "null argument");
+    MGB_REQUIRE(Kt >= 2, "surface: the colour table needs at least two rows");
+    for (int64_t i = 0; i < (int64_t)Kt * 4; ++i) MGB_REQUIRE(std::isfinite(table[i]), "surface: the colour table must be finite");
+    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "surface: clim must be finite with lo < hi");
+    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "surface: ambient must be in [0, 1]");
+    for (int64_t i = 0; i < R * 3; ++i) MGB_REQUIRE(std::isfinite(dir[i]), "surface: directions must be finite");
+    for (int64_t i = 0; i < R * K; ++i)
+        MGB_REQUIRE(tri[i] >= -1 && (int64_t)tri[i] < s->sf.T, "surface: a triangle index is out of range");
+    surface_shade(s->sf, R, K, dir, tri, u, v, values, Kt, table, lo, hi, ambient, layer, s->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_surface_destroy(mgbhip_surface* s) {
+    MGB_API_BEGIN_ON(s)
+    if (!s) return MGBHIP_OK;
+    (void)hipStreamSynchronize(s->ctx->stream);
+    delete s;
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -161,6 +161,64 @@ __global__ void __launch_bounds__(BLOCK) ray_composite(int64_t R, int32_t K, con
     out[r * 4 + 3] = 1.0 - T;
 }
 
+// ray_composite with up to KH opaque or translucent layers per ray merged into the samples by depth: hit k (t_hit
+// ascending along the ray, +inf for a missing entry) is applied before sample i iff t_hit <= t_i, with t_i formed as
+// ray_emit forms it; the hits behind the last sample are applied after it.  ray_composite itself is left as it is: a
+// call without layers runs it unchanged.
+__global__ void __launch_bounds__(BLOCK) ray_composite_layers(int64_t R, int32_t K, const int64_t* __restrict__ off,
+                                                              const double* __restrict__ tmin, const double* __restrict__ h,
+                                                              const double* __restrict__ val,
+                                                              const double* __restrict__ table, double lo, double hi,
+                                                              int32_t KH, const double* __restrict__ t_hit,
+                                                              const double* __restrict__ layer, double* __restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const double hr = h[r], t0r = tmin[r], width = hi - lo, km1 = (double)(K - 1);
+    const double* th = t_hit + r * KH;
+    const double* ly = layer + r * KH * 4;
+    double T = 1.0, C0 = 0.0, C1 = 0.0, C2 = 0.0;
+    int32_t k = 0;
+    const int64_t s0 = off[r], s1 = off[r + 1];
+    for (int64_t s = s0; s < s1; ++s) {
+        const double ti = t0r + ((double)(s - s0) + 0.5) * hr;
+        for (; k < KH && th[k] <= ti; ++k) {
+            C0 += T * ly[k * 4];
+            C1 += T * ly[k * 4 + 1];
+            C2 += T * ly[k * 4 + 2];
+            T = T * (1.0 - ly[k * 4 + 3]);
+        }
+        const double v = val[s];
+        if (!isfinite(v)) continue;
+        const double sc = fmin(1.0, fmax(0.0, (v - lo) / width));
+        const double f = sc * km1;
+        int32_t j = (int32_t)floor(f);           // 0 <= f <= K - 1
+        j = j < K - 2 ? j : K - 2;
+        const double w = f - (double)j;
+        const double* t0 = table + (int64_t)j * 4;
+        const double cr = t0[0] + w * (t0[4] - t0[0]);
+        const double cg = t0[1] + w * (t0[5] - t0[1]);
+        const double cb = t0[2] + w * (t0[6] - t0[2]);
+        const double sg = t0[3] + w * (t0[7] - t0[3]);
+        const double e = exp(-(sg * hr));
+        const double alpha = 1.0 - e;
+        const double ta = T * alpha;
+        C0 += ta * cr;
+        C1 += ta * cg;
+        C2 += ta * cb;
+        T = T * e;
+    }
+    for (; k < KH && th[k] < INFINITY; ++k) {
+        C0 += T * ly[k * 4];
+        C1 += T * ly[k * 4 + 1];
+        C2 += T * ly[k * 4 + 2];
+        T = T * (1.0 - ly[k * 4 + 3]);
+    }
+    out[r * 4] = C0;
+    out[r * 4 + 1] = C1;
+    out[r * 4 + 2] = C2;
+    out[r * 4 + 3] = 1.0 - T;
+}
+
 template <int D>
 void emit(const RayCaster& RC, double* d_pts, hipStream_t st) {
     hipLaunchKernelGGL((ray_emit<D>), dim3(grid_1d(RC.S)), dim3(BLOCK), 0, st, RC.S, RC.R, RC.off.p, RC.origin.p, RC.dir.p,
@@ -272,6 +330,21 @@ void raycast_render(RayCaster& RC, const double* u, int32_t K, const double* tra
     if (RC.S) locator_evaluate_device(RC.loc, 1, u, false, st);
     hipLaunchKernelGGL(ray_composite, dim3(grid_1d(RC.R)), dim3(BLOCK), 0, st, RC.R, K, RC.off.p, RC.h.p, RC.loc.out.p,
                        RC.transfer.p, lo, hi, RC.result.p);
+    MGB_HIP_CHECK(hipGetLastError());
+    RC.result.download(out, (size_t)RC.R * 4, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void raycast_render_layers(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi,
+                           int32_t KH, const double* t_hit, const double* layer, double* out, hipStream_t st) {
+    if (RC.R == 0) return;
+    RC.result.ensure((size_t)RC.R * 4);
+    RC.transfer.upload(transfer, (size_t)K * 4, st);
+    RC.t_hit.upload(t_hit, (size_t)RC.R * KH, st);
+    RC.layer.upload(layer, (size_t)RC.R * KH * 4, st);
+    if (RC.S) locator_evaluate_device(RC.loc, 1, u, false, st);
+    hipLaunchKernelGGL(ray_composite_layers, dim3(grid_1d(RC.R)), dim3(BLOCK), 0, st, RC.R, K, RC.off.p, RC.tmin.p, RC.h.p,
+                       RC.loc.out.p, RC.transfer.p, lo, hi, KH, RC.t_hit.p, RC.layer.p, RC.result.p);
     MGB_HIP_CHECK(hipGetLastError());
     RC.result.download(out, (size_t)RC.R * 4, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));

@@ -28,6 +28,7 @@ struct RayCaster {
     DevBuf<int64_t> off;                           // R + 1
     Locator loc;                                   // M = S
     DevBuf<double> transfer, result;               // per call: grown to the largest seen and kept
+    DevBuf<double> t_hit, layer;                   // per call of render_layers: R x KH, R x KH x 4
 };
 
 // count pass, exclusive scan over the rays, emit pass, location; complete on return (RC.S is known)
@@ -40,5 +41,9 @@ void raycast_integrate(RayCaster& RC, int32_t ncomp, const double* z, double* ou
 // u host p*N, transfer host K x 4 (r, g, b, sigma), out host R x 4: front-to-back emission-absorption compositing
 void raycast_render(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi, double* out,
                     hipStream_t st);
+// the same with KH layers per ray (t_hit host R x KH ascending, +inf = none; layer host R x KH x 4 premultiplied colour and
+// alpha) merged into the samples by depth: a hit is applied before sample i iff t_hit <= t_i
+void raycast_render_layers(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi,
+                           int32_t KH, const double* t_hit, const double* layer, double* out, hipStream_t st);
 
 }  // namespace mgbhip

@@ -119,7 +119,8 @@ EXPORTS = [
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy",
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
-    "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy",
+    "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy", "mgbhip_raycast_render_layers",
+    "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
 ]
 
 
@@ -213,6 +214,12 @@ def load_library():
     lib.mgbhip_raycast_integrate.argtypes = [vp, C.c_int32, _dp, _dp]
     lib.mgbhip_raycast_render.argtypes = [vp, _dp, C.c_int32, _dp, C.c_double, C.c_double, _dp]
     lib.mgbhip_raycast_destroy.argtypes = [vp]
+    lib.mgbhip_raycast_render_layers.argtypes = [vp, _dp, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, _dp, _dp, _dp]
+    lib.mgbhip_surface_create.argtypes = [vp, C.c_int64, _dp, C.POINTER(vp)]
+    lib.mgbhip_surface_trace.argtypes = [vp, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_int32, _dp, _ip, _dp, _dp]
+    lib.mgbhip_surface_shade.argtypes = [vp, C.c_int64, C.c_int32, _dp, _ip, _dp, _dp, _dp, C.c_int32, _dp, C.c_double,
+                                         C.c_double, C.c_double, _dp]
+    lib.mgbhip_surface_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 

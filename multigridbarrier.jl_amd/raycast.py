@@ -308,7 +308,7 @@ class RayCaster:
             _check(self._ctx.lib, self._ctx.lib.mgbhip_raycast_integrate(self._handle, ncomp, _ptr(Z), _ptr(out)))
         return out[:, 0] if single else out
 
-    def render(self, u, transfer=None, clim=None) -> np.ndarray:
+    def render(self, u, transfer=None, clim=None, layers=None) -> np.ndarray:
         """`(R, 4)` float64: premultiplied colour and alpha of every ray by front-to-back emission-absorption
         compositing of the element-space function `u` (`(p*N,)`).
 
@@ -323,6 +323,13 @@ class RayCaster:
 
         and a sample whose value is not finite (outside the mesh, or NaN in `u`) contributes nothing.  The result is
         `(C_r, C_g, C_b, 1 - T)`.  There is no early ray termination: every sample is composited.
+
+        `layers=(t_hit, layer)` puts surfaces into the volume (3-D only): `t_hit` is `(R, K)`, `1 <= K <= 8`, ascending
+        along every ray with `inf` for a missing entry, and `layer` is `(R, K, 4)`, finite: premultiplied colour and
+        alpha, as `TriangleCaster.trace` and `.shade` return them for the same rays.  A layer is applied before sample
+        `i` iff `t_hit <= t_i` (`t_i = tmin + (i + 0.5) h`), the finite ones that remain after the last sample, by
+        `C += T*layer[:3];  T = T*(1 - layer[3])`; a ray without samples composites its layers alone.  With `None` the
+        path without layers runs, unchanged.
         """
         self._open()
         U = np.asarray(u, dtype=np.float64)
@@ -331,12 +338,34 @@ class RayCaster:
                              f"{self._name} geometry (got shape {U.shape})")
         T = default_transfer(self.diagonal) if transfer is None else _check_transfer(transfer)
         lo, hi = _check_clim(clim, U)
+        if layers is not None:
+            try:
+                t_hit, layer = layers
+            except (TypeError, ValueError):
+                raise ValueError("RayCaster.render: layers must be (t_hit, layer)") from None
+            TH, LY = np.asarray(t_hit, dtype=np.float64), np.asarray(layer, dtype=np.float64)
+            if self._d != 3:
+                raise ValueError(f"RayCaster.render: layers need a 3-D mesh (this is a {self._name} geometry)")
+            if TH.ndim != 2 or TH.shape[0] != self.nrays or not 1 <= TH.shape[1] <= 8 or LY.shape != TH.shape + (4,):
+                raise ValueError(f"RayCaster.render: layers must be ({self.nrays}, K) and ({self.nrays}, K, 4) with K in "
+                                 f"1..8 (got shapes {TH.shape} and {LY.shape})")
+            if np.any(np.isnan(TH)) or np.any(TH[:, 1:] < TH[:, :-1]):
+                raise ValueError("RayCaster.render: the t_hit of layers must ascend along every ray (inf for a missing "
+                                 "entry, no NaN)")
+            if not np.all(np.isfinite(LY)):
+                raise ValueError("RayCaster.render: every entry of the layer of layers must be finite")
         out = np.zeros((self.nrays, 4))
         if self.nrays:
             from .device import _check, _ptr
             U, T = _c_f64(U), _c_f64(T)
-            _check(self._ctx.lib, self._ctx.lib.mgbhip_raycast_render(
-                self._handle, _ptr(U), int(T.shape[0]), _ptr(T), lo, hi, _ptr(out)))
+            if layers is None:
+                _check(self._ctx.lib, self._ctx.lib.mgbhip_raycast_render(
+                    self._handle, _ptr(U), int(T.shape[0]), _ptr(T), lo, hi, _ptr(out)))
+            else:
+                TH, LY = _c_f64(TH), _c_f64(LY)
+                _check(self._ctx.lib, self._ctx.lib.mgbhip_raycast_render_layers(
+                    self._handle, _ptr(U), int(T.shape[0]), _ptr(T), lo, hi, int(TH.shape[1]), _ptr(TH), _ptr(LY),
+                    _ptr(out)))
         return out
 
     def close(self):

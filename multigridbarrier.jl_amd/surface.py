@@ -1,0 +1,387 @@
+"""Rays against surfaces: `TriangleCaster` (nearest hits of rays with a triangle soup and their shading),
+`render_surfaces(contours, eye, target)` and `render_figure(geom, u, eye, target)`.
+
+The reference's default picture of a `fem3d` solution draws a volume render, five isosurfaces and optional slices into
+one image (ext/MultiGridBarrierPyPlotExt/plot3d.jl:85-149, PyVista on the CPU).  `isocontour()` gives the isosurfaces and
+slices as a triangle soup and `RayCaster` the volume render; this module turns the soup into pixels on the device
+(csrc/surface.hip) and puts it into the volume's front-to-back compositing at the right depth
+(`RayCaster.render(..., layers=...)`).  The host only checks arguments (before any device work), normalises the
+directions and concatenates soups.  Nothing here plots or writes image files: the result is a plain array.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from .contour import Contour, isocontour
+from .interpolate import _c_f64
+from .multigrid import Geometry
+from .raycast import (RayCaster, _check_clim, _check_size, _check_transfer, _diagonal, _raycast_plan, camera_rays, clip_box,
+                      default_transfer, normalize)
+
+MAX_HITS = 8            # csrc/surface.hpp SURFACE_MAX_HITS
+REFERENCE_ISOSURFACES = (0.1, 0.3, 0.5, 0.7, 0.9)     # plot3d.jl: fractions of the range of u
+
+
+@dataclass
+class Hits:
+    """The `K` nearest hits of `R` rays, nearest first; a missing entry is `t = inf`, `triangle = -1`, `u = v = NaN`."""
+    t: np.ndarray            # (R, K) float64: the ray parameter (arc length)
+    triangle: np.ndarray     # (R, K) int32
+    u: np.ndarray            # (R, K) float64: the hit point is (1 - u - v) v0 + u v1 + v v2
+    v: np.ndarray            # (R, K) float64
+
+
+def _check_rays(who: str, o, d):
+    O, D = np.asarray(o, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    if O.ndim == 1 and D.ndim == 1:
+        O, D = O.reshape(1, -1), D.reshape(1, -1)
+    if O.ndim != 2 or O.shape[1] != 3 or D.shape != O.shape:
+        raise ValueError(f"{who}: o and d must both be (R, 3) (got shapes {O.shape} and {D.shape})")
+    if not np.all(np.isfinite(O)):
+        raise ValueError(f"{who}: every ray origin o must be finite")
+    if not np.all(np.isfinite(D)):
+        raise ValueError(f"{who}: every ray direction d must be finite")
+    if np.any(np.all(D == 0.0, axis=1)):
+        raise ValueError(f"{who}: a ray direction d is zero")
+    Dn = normalize(D)
+    if not np.all(np.abs(np.sum(Dn * Dn, axis=1) - 1.0) <= 1e-12):      # also false for NaN
+        raise ValueError(f"{who}: a ray direction d is too long or too short to normalise (sum d*d overflows or vanishes)")
+    return O, Dn
+
+
+def _check_max_hits(who: str, max_hits) -> int:
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= max_hits <= MAX_HITS:
+        raise ValueError(f"{who}: max_hits must be an integer in 1..{MAX_HITS} (got {max_hits!r})")
+    return int(max_hits)
+
+
+def _check_ambient(who: str, ambient) -> float:
+    if not (isinstance(ambient, (int, float, np.integer, np.floating)) and 0.0 <= ambient <= 1.0):
+        raise ValueError(f"{who}: ambient must be a number in [0, 1] (got {ambient!r})")
+    return float(ambient)
+
+
+def _check_table(who: str, transfer) -> np.ndarray:
+    T = np.asarray(transfer, dtype=np.float64)
+    if T.ndim != 2 or T.shape[1] != 4 or T.shape[0] < 2:
+        raise ValueError(f"{who}: transfer must be (K, 4) with K >= 2 (got shape {T.shape})")
+    if not np.all(np.isfinite(T)):
+        raise ValueError(f"{who}: every transfer entry must be finite")
+    return T
+
+
+def _clim(who: str, clim, data: np.ndarray, name: str):
+    """`raycast._check_clim` with the errors naming `who` and the argument the default is taken from."""
+    try:
+        return _check_clim(clim, data)
+    except ValueError as e:
+        raise ValueError(str(e).replace("RayCaster.render: u ", f"{who}: {name} ").replace("RayCaster.render", who)) from None
+
+
+def default_surface_table(K: int = 256) -> np.ndarray:
+    """The `(K, 4)` table `shade` uses when `transfer` is None: the grey ramp of `default_transfer` with its fourth
+    column replaced by 1 (opaque)."""
+    T = default_transfer(1.0, K)
+    T[:, 3] = 1.0
+    return T
+
+
+def composite_layers(layers: np.ndarray) -> np.ndarray:
+    """`(R, 4)`: the layers `(R, K, 4)` of each ray composited front to back from `T = 1, C = 0` by `C += T layer_rgb`,
+    `T *= 1 - alpha`; the result is `(C, 1 - T)`.  A sum of at most eight terms per ray, formed on the host."""
+    L = np.asarray(layers, dtype=np.float64)
+    T = np.ones(L.shape[0])
+    Cc = np.zeros((L.shape[0], 3))
+    for k in range(L.shape[1]):
+        Cc = Cc + T[:, None] * L[:, k, :3]
+        T = T * (1.0 - L[:, k, 3])
+    return np.concatenate([Cc, (1.0 - T)[:, None]], axis=1)
+
+
+class TriangleCaster:
+    """A triangle soup `points` (`(T, 3, 3)`: triangle, vertex, coordinate; finite) sorted once into a uniform grid of
+    cells on the device, for tracing many bundles of rays against it.  `T = 0` is allowed: every ray misses and no
+    device work is done.
+
+    The triangle test (the same on the device and in the NumPy restatement the tests compare it with,
+    tests/surface_twin.py), for the ray `o + t dn` with `dn = d / sqrt(sum d*d)` and the vertices `v0, v1, v2`, in IEEE
+    double without fused multiply-adds, with `(a x b)[0] = a1*b2 - a2*b1` (cyclically) and `a . b = (a0*b0 + a1*b1) + a2*b2`:
+
+        e1 = v1 - v0;  e2 = v2 - v0;  p = dn x e2;  det = e1 . p
+        s = o - v0;  u = (s . p) / det;  q = s x e1;  v = (dn . q) / det;  t = (e2 . q) / det
+
+    The triangle is hit iff `det` is finite and non-zero, `u >= 0`, `v >= 0`, `u + v <= 1` and `t_min <= t <= t_max`;
+    both sides are hit.  A ray keeps its `max_hits` nearest hits in the order of `(t, triangle index)`.  Which
+    triangles a ray is tested against is decided by the grid (a 3-D DDA from the ray's entry into the grid box); what
+    it hits is not.
+
+    Use it as a context manager or call `close()`.
+    """
+
+    def __init__(self, points, device_id: int = 0):
+        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
+        self.closed = False
+        P = np.asarray(points, dtype=np.float64)
+        if P.ndim != 3 or P.shape[1:] != (3, 3):
+            raise ValueError(f"TriangleCaster: points must be (T, 3, 3) (got shape {P.shape})")
+        if not np.all(np.isfinite(P)):
+            raise ValueError("TriangleCaster: every entry of points must be finite")
+        self.ntriangles = T = int(P.shape[0])
+        if T:
+            from .device import HipContext, _check, _ptr
+            P = _c_f64(P)
+            self._ctx = HipContext(device_id)
+            h = C.c_void_p()
+            try:
+                _check(self._ctx.lib, self._ctx.lib.mgbhip_surface_create(self._ctx.handle, T, _ptr(P), C.byref(h)))
+            except Exception:
+                self._ctx.close()
+                self._ctx = None
+                raise
+            self._handle = h
+
+    def _open(self):
+        if self.closed:
+            raise ValueError("TriangleCaster: the caster is closed")
+
+    def trace(self, o, d, t_min: float = 0.0, t_max: float = np.inf, max_hits: int = 1) -> Hits:
+        """The `max_hits` (1..8) nearest hits of every ray `o + t d` (`(R, 3)` each; one ray may be given as `(3,)`) with
+        `t_min <= t <= t_max`; `t` is arc length."""
+        self._open()
+        O, Dn = _check_rays("TriangleCaster.trace", o, d)
+        try:
+            t_min, t_max = float(t_min), float(t_max)
+        except (TypeError, ValueError):
+            raise ValueError("TriangleCaster.trace: t_min and t_max must be numbers") from None
+        if not math.isfinite(t_min):
+            raise ValueError(f"TriangleCaster.trace: t_min must be finite (got {t_min})")
+        if not t_max > t_min:
+            raise ValueError(f"TriangleCaster.trace: t_max must be greater than t_min (got t_min = {t_min}, "
+                             f"t_max = {t_max})")
+        K = _check_max_hits("TriangleCaster.trace", max_hits)
+        R = int(O.shape[0])
+        t = np.full((R, K), np.inf)
+        tri = np.full((R, K), -1, dtype=np.int32)
+        u, v = np.full((R, K), np.nan), np.full((R, K), np.nan)
+        if R and self.ntriangles:
+            from .device import _check, _ptr
+            O, Dn = _c_f64(O), _c_f64(Dn)
+            _check(self._ctx.lib, self._ctx.lib.mgbhip_surface_trace(
+                self._handle, R, _ptr(O), _ptr(Dn), t_min, t_max, K, _ptr(t), tri.ctypes.data_as(C.POINTER(C.c_int32)),
+                _ptr(u), _ptr(v)))
+        return Hits(t, tri, u, v)
+
+    def shade(self, hits: Hits, d, values, transfer=None, clim=None, ambient: float = 0.3) -> np.ndarray:
+        """`(R, K, 4)` float64: premultiplied colour and alpha of every hit.
+
+        `d` are the directions the hits were traced with, `values` is `(T, 3)`: a value per triangle vertex.  The carried
+        value of a hit is `c = ((1 - u - v) c0 + u c1) + v c2`; its row of `transfer` (`(K, 4)`: `r, g, b, alpha`; the
+        default is `default_surface_table()`) is found as `RayCaster.render` finds it, between `clim = (lo, hi)` (the
+        default is the minimum and maximum of the finite `values`).  With `n = e1 x e2`, `nn = n / sqrt(n . n)` and
+        `shade = ambient + (1 - ambient) |nn . dn|`, the layer is `alpha shade (r, g, b)` and `alpha = min(1, max(0,
+        row[3]))`.  A missing hit or a non-finite `c` gives a zero layer.
+        """
+        self._open()
+        who = "TriangleCaster.shade"
+        if not isinstance(hits, Hits):
+            raise ValueError(f"{who}: hits must be what trace() returned (got {type(hits).__name__})")
+        _, Dn = _check_rays(who, np.zeros_like(np.asarray(d, dtype=np.float64)), d)
+        R = int(Dn.shape[0])
+        tri = np.asarray(hits.triangle)
+        if tri.ndim != 2 or tri.shape[0] != R or not 1 <= tri.shape[1] <= MAX_HITS:
+            raise ValueError(f"{who}: hits hold {tri.shape} entries for {R} directions d")
+        K = int(tri.shape[1])
+        hu, hv = np.asarray(hits.u, dtype=np.float64), np.asarray(hits.v, dtype=np.float64)
+        if hu.shape != tri.shape or hv.shape != tri.shape:
+            raise ValueError(f"{who}: hits.u and hits.v must have the shape of hits.triangle {tri.shape}")
+        if tri.size and (tri.min() < -1 or tri.max() >= self.ntriangles):
+            raise ValueError(f"{who}: hits.triangle has an index outside -1..{self.ntriangles - 1}")
+        V = np.asarray(values, dtype=np.float64)
+        if V.shape != (self.ntriangles, 3):
+            raise ValueError(f"{who}: values must be ({self.ntriangles}, 3) (got shape {V.shape})")
+        T = default_surface_table() if transfer is None else _check_table(who, transfer)
+        if clim is None and self.ntriangles == 0:
+            clim = (0.0, 1.0)                    # nothing to colour
+        lo, hi = _clim(who, clim, V, "values")
+        ambient = _check_ambient(who, ambient)
+        layer = np.zeros((R, K, 4))
+        if R and self.ntriangles:
+            from .device import _check, _ptr
+            Dn, V, T, hu, hv = _c_f64(Dn), _c_f64(V), _c_f64(T), _c_f64(hu), _c_f64(hv)
+            tri = np.ascontiguousarray(tri, dtype=np.int32)
+            _check(self._ctx.lib, self._ctx.lib.mgbhip_surface_shade(
+                self._handle, R, K, _ptr(Dn), tri.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(hu), _ptr(hv), _ptr(V),
+                int(T.shape[0]), _ptr(T), lo, hi, ambient, _ptr(layer)))
+        return layer
+
+    def close(self):
+        """Free the device state; calling it again does nothing."""
+        self.closed = True
+        if self._handle is not None:
+            self._ctx.lib.mgbhip_surface_destroy(self._handle)
+            self._handle = None
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _soup(who: str, contours, values, levels):
+    """The concatenated triangles `(T, 3, 3)` and vertex values `(T, 3)` of one `Contour` or a list of them."""
+    cs = [contours] if isinstance(contours, Contour) else list(contours)
+    for c in cs:
+        if not isinstance(c, Contour):
+            raise ValueError(f"{who}: contours must be a Contour or a list of them (got {type(c).__name__})")
+        if c.points.ndim != 3 or c.points.shape[1:] != (3, 3):
+            raise ValueError(f"{who}: contours must hold triangles, (S, 3, 3) (got points of shape {c.points.shape}: "
+                             "level curves of a 2-D mesh are not surfaces)")
+    pts = np.concatenate([c.points for c in cs]) if cs else np.zeros((0, 3, 3))
+    T = int(pts.shape[0])
+    if values is not None:
+        V = np.asarray(values, dtype=np.float64)
+        if V.shape == (T,):
+            V = np.repeat(V[:, None], 3, axis=1)
+        if V.shape != (T, 3):
+            raise ValueError(f"{who}: values must be ({T},) or ({T}, 3) for these contours (got shape {V.shape})")
+        return pts, V
+    if levels is not None:
+        levels = [levels] if isinstance(contours, Contour) else list(levels)
+        if len(levels) != len(cs):
+            raise ValueError(f"{who}: levels must give one array of level values per contour ({len(cs)})")
+    vals = []
+    for i, c in enumerate(cs):
+        if c.carried is not None:
+            vals.append(c.carried[..., 0])
+        elif levels is not None:
+            lev = np.asarray(levels[i], dtype=np.float64).reshape(-1)
+            if lev.shape[0] != c.nlevels:
+                raise ValueError(f"{who}: levels[{i}] has {lev.shape[0]} values for a contour of {c.nlevels} levels")
+            vals.append(np.repeat(lev[c.level][:, None], 3, axis=1))
+        else:
+            raise ValueError(f"{who}: a contour without carried fields needs values= or levels= (a Contour keeps the "
+                             "index of each triangle's level, not its value)")
+    return pts, (np.concatenate(vals) if vals else np.zeros((0, 3)))
+
+
+def render_surfaces(contours, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0,
+                    height: Optional[float] = None, values=None, levels=None, transfer=None, clim=None,
+                    ambient: float = 0.3, max_hits: int = 1, device_id: int = 0):
+    """`(image, depth)`: the `(H, W, 4)` premultiplied colour and alpha of the triangles of one `Contour` (3-D) or a list
+    of them seen by the camera of `camera_rays`, row 0 at the top, and the `(H, W)` ray parameter of each pixel's first
+    hit (`inf` where there is none).
+
+    `values` is `(T,)` or `(T, 3)` over the concatenated triangles.  Its default is `carried[..., 0]` for a contour that
+    carries fields and the level value per triangle otherwise, looked up in `levels` (the values given to
+    `isocontour`; one array per contour).  `transfer`, `clim` and `ambient` are those of `TriangleCaster.shade`.  The
+    `max_hits` layers of a pixel are composited front to back (`composite_layers`).
+    """
+    who = "render_surfaces"
+    pts, V = _soup(who, contours, values, levels)
+    W, H = _check_size(size)
+    o, d = camera_rays(eye, target, up, (W, H), fov, height)
+    K = _check_max_hits(who, max_hits)
+    T = default_surface_table() if transfer is None else _check_table(who, transfer)
+    ambient = _check_ambient(who, ambient)
+    if pts.shape[0] == 0:
+        return np.zeros((H, W, 4)), np.full((H, W), np.inf)
+    if not np.all(np.isfinite(pts)):
+        raise ValueError(f"{who}: the contours have non-finite points")
+    clim = _clim(who, clim, V, "values")
+    with TriangleCaster(pts, device_id=device_id) as tc:
+        hits = tc.trace(o, d, max_hits=K)
+        layers = tc.shade(hits, d, V, T, clim, ambient)
+    return composite_layers(layers).reshape(H, W, 4), hits.t[:, 0].reshape(H, W)
+
+
+def render_figure(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0, isosurfaces=None,
+                  slices=None, volume: bool = True, surface_alpha: float = 1.0, step: Optional[float] = None,
+                  transfer=None, clim=None, ambient: float = 0.3, device_id: int = 0) -> np.ndarray:
+    """`(H, W, 4)`: the reference's default figure of the `fem3d` solution `u`: the volume render of `render_volume` with
+    isosurfaces and slices composited into it at their depth, row 0 at the top.
+
+    - `isosurfaces`: the level values; the default is the reference's `[0.1, 0.3, 0.5, 0.7, 0.9] * (max - min) + min`
+      over the finite entries of `u`; `[]` draws none.  Their triangles are coloured by their level value.
+    - `slices`: a list of `(axis, coordinate)` pairs, each the plane `x[axis] = coordinate` cut by
+      `isocontour(geom, geom.xflat[:, axis], [coordinate], carry=u)` and coloured by `u` on it.
+    - `volume=False` gives the surfaces alone.
+    - `transfer` (`(K, 4)`: `r, g, b, sigma`; the default is that of `render_volume`) and `clim` are shared: the surfaces
+      take the table's colours with the alpha `surface_alpha` in place of `sigma`.  A pixel keeps its nearest hit when
+      `surface_alpha == 1` and its four nearest otherwise.
+    - `step` is the sample distance of the volume (the default is 1/256 of the clip box's diagonal).
+    """
+    who = "render_figure"
+    _, name, dim, _, p, N, _, _ = _raycast_plan(geom, who)
+    if dim != 3:
+        raise ValueError(f"{who}: {name} geometries are not supported (the camera is 3-D: fem3d only)")
+    W, H = _check_size(size)
+    o, d = camera_rays(eye, target, up, (W, H), fov)
+    U = np.asarray(u, dtype=np.float64)
+    if U.ndim != 1 or U.shape[0] != p * N:
+        raise ValueError(f"{who}: u must be a vector of {p * N} values for this {name} geometry (got shape {U.shape})")
+    clim = _clim(who, clim, U, "u")
+    box = clip_box(geom)
+    table = default_transfer(_diagonal(box)) if transfer is None else _check_transfer(transfer)
+    if not (isinstance(surface_alpha, (int, float, np.integer, np.floating)) and 0.0 <= surface_alpha <= 1.0):
+        raise ValueError(f"{who}: surface_alpha must be a number in [0, 1] (got {surface_alpha!r})")
+    ambient = _check_ambient(who, ambient)
+    if isosurfaces is None:
+        fin = U[np.isfinite(U)]
+        lev = np.array(REFERENCE_ISOSURFACES) * (float(fin.max()) - float(fin.min())) + float(fin.min())
+    else:
+        lev = np.asarray(isosurfaces, dtype=np.float64).reshape(-1)
+        if not np.all(np.isfinite(lev)):
+            raise ValueError(f"{who}: every entry of isosurfaces must be finite")
+    planes = []
+    for s in ([] if slices is None else slices):
+        try:
+            axis, coord = s
+            coord = float(coord)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: slices must be a list of (axis, coordinate) pairs (got {s!r})") from None
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or axis not in (0, 1, 2) \
+                or not math.isfinite(coord):
+            raise ValueError(f"{who}: a slice needs an axis in 0..2 and a finite coordinate (got {s!r})")
+        planes.append((int(axis), coord))
+    if step is None:
+        step = _diagonal(box) / 256.0
+    elif not (isinstance(step, (int, float, np.integer, np.floating)) and math.isfinite(step) and step > 0.0):
+        raise ValueError(f"{who}: step must be finite and positive (got {step!r})")
+    # the soup: isosurfaces coloured by their level value, slices by the carried u
+    pts, vals = [], []
+    if lev.size:
+        iso = isocontour(geom, U, lev, device_id=device_id)
+        pts.append(iso.points)
+        vals.append(np.repeat(lev[iso.level][:, None], 3, axis=1))
+    for axis, coord in planes:
+        cut = isocontour(geom, geom.xflat[:, axis], [coord], carry=U, device_id=device_id)
+        pts.append(cut.points)
+        vals.append(cut.carried[..., 0])
+    pts = np.concatenate(pts) if pts else np.zeros((0, 3, 3))
+    vals = np.concatenate(vals) if vals else np.zeros((0, 3))
+    surf_table = table.copy()
+    surf_table[:, 3] = float(surface_alpha)
+    K = 1 if surface_alpha == 1 else 4
+    with TriangleCaster(pts, device_id=device_id) as tc:
+        hits = tc.trace(o, d, max_hits=K)
+        layers = tc.shade(hits, d, vals, surf_table, clim, ambient)
+    if not volume:
+        return composite_layers(layers).reshape(H, W, 4)
+    with RayCaster(geom, o, d, step, device_id=device_id) as rc:
+        return rc.render(U, table, clim, layers=(hits.t, layers)).reshape(H, W, 4)
