@@ -283,6 +283,18 @@ int mgbhip_solver_chain(mgbhip_problem* prob, int32_t level, double* out8);
  * [4]..[10], [13] and [14] describe it and are zero / defaults before).                                                   */
 enum { MGBHIP_PROJ_NONE = 0, MGBHIP_PROJ_LOOP = 1, MGBHIP_PROJ_STAGED = 2, MGBHIP_PROJ_MFMA = 3, MGBHIP_PROJ_ACCUMULATE = 4 };
 int mgbhip_level_plan(mgbhip_problem* prob, int32_t level, int32_t* out16);
+/* The factorization launches of a level's sparse LDL', leaves first (inspection only, valid after the level's first solve;
+ * nothing is computed or changed).  Returns the number of launches, or -status on an error, and writes at most `cap` rows of
+ * MGBHIP_LAUNCH_ROW int32 to out (out may be NULL with cap = 0):  [0] tree level, [1] first front, [2] fronts, [3] LDS class
+ * (0: large-front path), [4] largest front m, [5] largest pivot block k, [6] most children of a front, [7] tiny (16 lanes per
+ * leaf front), [8] wave (one wave per front), [9] inverse-based large-front kernels, [10] interface front, [11] fronts stored
+ * as packed triangles, [12] assembly kernel of a large-front launch (MGBHIP_ASM_*), [13] where block 0 of the pivot chain is
+ * factored (MGBHIP_B0_*), [14] backward sweep of an LDS launch (MGBHIP_BWD_*), [15] reserved.                                */
+enum { MGBHIP_LAUNCH_ROW = 16 };
+enum { MGBHIP_ASM_NONE = 0, MGBHIP_ASM_GATHER = 1, MGBHIP_ASM_COLUMNS = 2 };
+enum { MGBHIP_B0_NA = 0, MGBHIP_B0_GATHER = 1, MGBHIP_B0_DIAG0 = 2, MGBHIP_B0_STEP0 = 3 };
+enum { MGBHIP_BWD_NA = 0, MGBHIP_BWD_K8 = 1, MGBHIP_BWD_K16 = 2, MGBHIP_BWD_GENERAL = 3 };
+int64_t mgbhip_solver_launches(mgbhip_problem* prob, int32_t level, int32_t* out, int64_t cap);
 
 /* ---- point evaluation (reference: `interpolate`, src/utils.jl:16-58) ---------------------------------------------
  * out[q, c] = the element-space function with broken-basis values z[:, c] at point q, for M points pts (M x d,

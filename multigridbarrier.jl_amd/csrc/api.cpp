@@ -683,6 +683,25 @@ int mgbhip_solver_chain(mgbhip_problem* P, int32_t level, double* out) {
     MGB_API_END
 }
 
+static_assert(MGBHIP_LAUNCH_ROW == mgbhip::MF_LAUNCH_ROW && MGBHIP_ASM_GATHER == mgbhip::MF_ASM_GATHER &&
+              MGBHIP_ASM_COLUMNS == mgbhip::MF_ASM_COLS && MGBHIP_B0_GATHER == mgbhip::MF_B0_GATHER &&
+              MGBHIP_B0_DIAG0 == mgbhip::MF_B0_DIAG0 && MGBHIP_B0_STEP0 == mgbhip::MF_B0_STEP0 && MGBHIP_BWD_K8 == mgbhip::MF_BWD_K8 &&
+              MGBHIP_BWD_K16 == mgbhip::MF_BWD_K16 && MGBHIP_BWD_GENERAL == mgbhip::MF_BWD_GENERAL, "mgbhip.h and mf_launch_plan.hpp disagree");
+
+int64_t mgbhip_solver_launches(mgbhip_problem* P, int32_t level, int32_t* out, int64_t cap) {
+    int64_t count = 0;
+    const int rc = [&]() -> int {
+        MGB_API_BEGIN
+        check_level(P, level);
+        MGB_REQUIRE(cap >= 0 && (out != nullptr || cap == 0), "bad output buffer");
+        MGB_REQUIRE(P->levels[level].solver.analyzed, "mgbhip_solver_launches: the level has not been factored yet");
+        count = P->levels[level].solver.launches(out, cap);
+        return MGBHIP_OK;
+        MGB_API_END
+    }();
+    return rc == MGBHIP_OK ? count : -(int64_t)rc;
+}
+
 #ifdef MGB_STEP_PROBE
 int mgbhip_debug_probe(long long* out64) { (void)hipDeviceSynchronize(); mgbhip::mf_debug_probe(out64); return 0; }
 #endif

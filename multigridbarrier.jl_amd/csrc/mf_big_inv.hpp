@@ -20,7 +20,6 @@
 namespace mgbhip {
 namespace {
 
-constexpr int BIG_INV_MAX_M = 7000;     // work vectors of the single-workgroup solves stay in LDS
 constexpr int BIGI_THREADS = 1024;
 
 #include "ldlt32.hpp"
@@ -346,7 +345,6 @@ __global__ __launch_bounds__(256) void mf_big_diag0(const FrontDev* __restrict__
 // destination entry is formed ONCE in a register -- the children's entries that land on it, added in child order,
 // all their loads in flight together -- and stored once.  No zero pass, no read-modify-write of the arena, and
 // the dependent-load chains of the children run side by side instead of one child after the other.
-constexpr int GATHER_MAX_CHILD = 8;
 __global__ __launch_bounds__(256) void mf_big_gather(const FrontDev* __restrict__ fr, int32_t first,
                                                      const int32_t* __restrict__ children,
                                                      const int32_t* __restrict__ rel,
@@ -810,23 +808,20 @@ __global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv(const FrontDev* __res
 }
 
 // ---- host launchers ------------------------------------------------------------------------------------------
-// mf_big_gather: for every child the position of each front row in the child's update block
-inline size_t big_gather_lds(const MfLaunch& L) { return (size_t)L.max_child * (size_t)L.max_m * sizeof(int32_t); }
-// Assembly of the fronts of a large-front launch: the gathering kernel when it applies (few children, index table
-// within 40 KB), the column-tiled one otherwise.  with_diag asks the gather launch for an extra workgroup per front
-// that factors block 0; returns true when that happened.
-inline bool launch_big_assemble(const FactorArgs& a, const MfLaunch& L, bool with_diag) {
-    const size_t lds = big_gather_lds(L);
-    if (L.max_child < 1 || L.max_child > GATHER_MAX_CHILD || lds > 40 * 1024) {
+// Assembly of the fronts of a large-front launch: the gathering kernel when it applies (big_assembly_kind,
+// mf_launch_plan.hpp), the column-tiled one otherwise.  with_diag asks the gather launch for an extra workgroup per
+// front that factors block 0 (big_block0_kind says MF_B0_GATHER only when the gathering kernel applies).
+inline void launch_big_assemble(const FactorArgs& a, const MfLaunch& L, bool with_diag) {
+    if (big_assembly_kind(L) != MF_ASM_GATHER) {
         launch_big_assemble_cols(a, L);
-        return false;
+        return;
     }
+    const size_t lds = big_gather_lds(L);
     dim3 ga = big_assemble_grid(L);
     const int ct = CT;                 // (one column per wave on levels with few fronts, ct = 4: no gain, measured in round 4)
     if (with_diag) ga.x += 1;          // the diagonal-block workgroup
     hipLaunchKernelGGL(mf_big_gather, ga, dim3(256), lds, a.st, a.fr, L.first, a.children, a.rel, a.a_src, a.a_dst, a.a_colptr,
                        a.values, a.arena, L.max_m, a.dscr, a.status, with_diag ? 1 : 0, ct);
-    return with_diag;
 }
 
 inline void launch_big_diag0(const FactorArgs& a, const MfLaunch& L, int nfronts) {

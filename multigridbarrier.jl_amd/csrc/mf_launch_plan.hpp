@@ -1,0 +1,274 @@
+// mf_launch_plan.hpp -- the launch plan of the numeric multifrontal LDL': which kernel every front of a symbolic plan goes to.
+// Pure host C++ (no HIP), like mf_analysis.hpp: mf_numeric.hip includes it for MfSolver::analyze() / factor(), and the CPU
+// checker build (oracle/csrc/mf_host.cpp) runs the same classification without a device, so that a test can pin, per launch,
+// the kernel a hand-built pattern must get (tests/solver_gate_cases.py).
+//
+// The shape predicates of the launchers live here too (assembly kind, block-0 kind, backward variant): the launch code in
+// mf_small.hpp / mf_big_inv.hpp / mf_numeric.hip and the read-only report launch_rows() call the same functions.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+#include "mf_analysis.hpp"
+
+namespace mgbhip {
+
+struct MfLaunch {          // one kernel launch: a contiguous range of fronts of one size class
+    int32_t first, count;
+    int32_t cls;           // LDS working size (0 = large-front multi-workgroup path)
+    int32_t max_m, max_k;  // largest front / pivot block in the range
+    int32_t max_child = 0; // most children of a front in the range
+    bool tiny = false;     // leaf fronts with m <= 16: 16-lanes-per-front kernels
+    bool wave = false;     // m <= 48 and only small children: one wave per front (mf_factor_wave), packed LDS triangle
+    bool inv = false;      // large fronts on the inverse-based path (W_j = L_jj^{-1} in the arena, pivots in dvec)
+    bool iface = false;    // the interface front of a domain-decomposed system, alone in its launch: assembled, summed
+                           // over ranks (MfSolver::iface_reduce), then factored redundantly on every rank
+};
+
+constexpr int BIG_INV_MAX_M = 7000;     // work vectors of the single-workgroup solves stay in LDS
+constexpr int GATHER_MAX_CHILD = 8;     // children whose index tables mf_big_gather keeps in LDS
+constexpr int BIG_DIAG0_MIN_COUNT = 24; // fronts of a launch from which block 0 gets a launch of its own (mf_big_diag0)
+
+// Environment switches of the launch plan (tools/README.md, switch table), read in one place by analyze().
+struct MfSwitches {
+    bool no_geo;            // MGBHIP_NO_GEO=1: no coordinates for the ordering (BFS level-set bisection)
+    bool old_big;           // MGBHIP_OLD_BIG=1: substitution kernels for every large front
+    bool merge_groups;      // off with MGBHIP_NO_MERGE_GROUPS=1
+    bool packed_leaves;     // off with MGBHIP_NO_PACKED_LEAVES=1
+    bool wave_small;        // off with MGBHIP_NO_WAVE_SMALL=1
+    // Size gates of the two fastest kernel families (A/B switches of tests/test_gpu_solver.py).  Round 2 kept both off
+    // systems of < 1024 unknowns after two creeping solves failed with them.  Round 3: all kernel selections are
+    // equally backward stable on graded matrices (2.9e-13 componentwise) and the 27-problem sweep agrees with the
+    // oracle without any gate (the 37-unknown case that motivated the wave gate: 5356 vs 5355 iterations), so the
+    // one-wave kernel is ungated.  The inverse-based large-front path keeps its gate: without it config 4's phase I
+    // (fem3d L=6, 9 000 iterations hugging the wall on a 145-unknown level) ends in "Initial centering failed" --
+    // applying W = L_jj^{-1} is only forward stable in cond(L_jj), and such systems gain nothing from it.
+    int64_t inv_min_n;      // MGBHIP_INV_MIN_N, default 1024
+    int64_t wave_min_n;     // MGBHIP_WAVE_MIN_N, default 0
+    static MfSwitches from_env() {
+        auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+        auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
+        return {on("MGBHIP_NO_GEO"), on("MGBHIP_OLD_BIG"), !on("MGBHIP_NO_MERGE_GROUPS"), !on("MGBHIP_NO_PACKED_LEAVES"),
+                !on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0)};
+    }
+};
+
+using LevelLaunches = std::vector<std::vector<MfLaunch>>;
+
+inline MfLaunch launch_of_range(const MfPlan& plan, MfLaunch L, int32_t first, int32_t count) {     // L's flags over [first, first + count)
+    L.first = first; L.count = count;
+    L.max_m = 0; L.max_k = 0; L.max_child = 0;
+    for (int32_t t = first; t < first + count; ++t) {
+        L.max_m = std::max(L.max_m, plan.fronts[t].m);
+        L.max_k = std::max(L.max_k, plan.fronts[t].k);
+        L.max_child = std::max(L.max_child, plan.fronts[t].nchild);
+    }
+    return L;
+}
+
+// Launches of one level are independent but share a stream: a straggler group (4 fronts of the next
+// smaller class, 60 LDS-sized fronts beside 196 large ones) costs a full, latency-bound launch of
+// 20-30 us.  Fold small groups into their neighbour:
+//   (1) LDS-class fronts of a level whose bulk is on the large-front path join that path (it handles any m);
+//   (2) an LDS class with few fronts joins the next larger LDS class of the level.
+// Fronts are sorted by m inside a level, so a merge just extends the neighbour's range downwards.
+inline void merge_straggler_groups(const MfPlan& plan, std::vector<MfLaunch>& G) {
+    auto absorb = [&](size_t into, size_t from) {        // from == into - 1
+        MfLaunch& A = G[into];
+        const MfLaunch& B = G[from];
+        A.first = B.first;
+        A.count += B.count;
+        A.max_k = std::max(A.max_k, B.max_k);
+        A.max_child = std::max(A.max_child, B.max_child);
+        G.erase(G.begin() + (long)from);
+    };
+    if (G.size() >= 2 && G.back().cls == 0 && G.back().inv) {
+        int64_t lds_count = 0;
+        bool ok = true;
+        for (size_t g = 0; g + 1 < G.size(); ++g) { lds_count += G[g].count; ok = ok && !G[g].tiny && plan.fronts[G[g].first].m > 32; }
+        if (ok && lds_count <= G.back().count)
+            while (G.size() >= 2) absorb(G.size() - 1, G.size() - 2);
+    }
+    for (size_t g = 0; g + 1 < G.size();) {
+        const bool next_lds = G[g + 1].cls != 0;
+        if (next_lds && !G[g].tiny && (G[g].count < 256 || 4 * (int64_t)G[g].count < G[g + 1].count)) absorb(g + 1, g);
+        else ++g;
+    }
+}
+
+// The interface front gets a launch of its own on the large-front path (assemble / reduce / factor are separate
+// kernels there, whatever its size): the launch that holds it is split around it.
+inline void split_interface_front(const MfPlan& plan, LevelLaunches& levels, bool inv_allowed) {
+    const int32_t q = plan.iface_front;
+    for (auto& G : levels) {
+        for (size_t g = 0; g < G.size(); ++g) {
+            const MfLaunch L = G[g];
+            if (q < L.first || q >= L.first + L.count) continue;
+            std::vector<MfLaunch> out;
+            if (q > L.first) out.push_back(launch_of_range(plan, L, L.first, q - L.first));
+            MfLaunch I = launch_of_range(plan, L, q, 1);
+            I.cls = 0; I.tiny = false; I.wave = false; I.iface = true;
+            I.inv = (I.max_m <= BIG_INV_MAX_M && inv_allowed);
+            out.push_back(I);
+            if (q + 1 < L.first + L.count) out.push_back(launch_of_range(plan, L, q + 1, L.first + L.count - q - 1));
+            G.erase(G.begin() + (long)g);
+            G.insert(G.begin() + (long)g, out.begin(), out.end());
+            break;
+        }
+    }
+}
+
+// Launches of fronts with m <= 48 whose children are all small (update block <= 8 x 8: the element leaves under a
+// level-1 front, or no children) go to the one-wave-per-front kernel mf_factor_wave; with large children the
+// 256-thread kernel's extend-add is faster and the launch stays there.
+inline bool only_small_children(const MfPlan& plan, const MfLaunch& L) {
+    for (int32_t q = L.first; q < L.first + L.count; ++q) {
+        const Front& f = plan.fronts[q];
+        for (int32_t c = 0; c < f.nchild; ++c) {
+            const Front& ch = plan.fronts[plan.children[f.child_off + c]];
+            if ((ch.m - ch.k) * (ch.m - ch.k) > 64) return false;
+        }
+    }
+    return true;
+}
+
+// The factorization's launches, per tree level and leaves first: a function of the plan, the LDS cap, whether the
+// inverse-based solves got their LDS (inv_ok) and the switches -- no device call.
+inline LevelLaunches classify_launches(const MfPlan& plan, int32_t lds_cap, bool inv_ok, const MfSwitches& sw) {
+    static const int32_t classes[] = {16, 32, 48, 64, 88, 128};
+    const bool inv_allowed = inv_ok && !sw.old_big && plan.n >= sw.inv_min_n;
+    const int32_t nlev = (int32_t)plan.level_ptr.size() - 1;
+    LevelLaunches levels(nlev);
+    for (int32_t l = 0; l < nlev; ++l) {
+        int32_t i = plan.level_ptr[l];
+        const int32_t end = plan.level_ptr[l + 1];
+        while (i < end) {
+            const int32_t m = plan.fronts[i].m;
+            int32_t cls = 0;
+            for (int32_t c : classes)
+                if (m <= c && c <= lds_cap) { cls = c; break; }
+            int32_t j = i;
+            if (cls) {
+                while (j < end && plan.fronts[j].m <= cls) ++j;
+            } else {
+                j = end;   // sorted by m: everything left in the level is large
+            }
+            MfLaunch L = launch_of_range(plan, MfLaunch{}, i, j - i);
+            L.cls = cls;
+            L.max_m = plan.fronts[j - 1].m;
+            L.tiny = (l == 0 && cls == 16);     // leaves with m <= 16: 16 lanes per front
+            L.inv = (cls == 0 && L.max_m <= BIG_INV_MAX_M && inv_allowed);
+            levels[l].push_back(L);
+            i = j;
+        }
+        if (sw.merge_groups) merge_straggler_groups(plan, levels[l]);
+    }
+    if (plan.iface_front >= 0) split_interface_front(plan, levels, inv_allowed);
+    for (auto& lev : levels)
+        for (auto& L : lev)
+            L.wave = !L.tiny && L.cls && L.cls <= 48 && sw.wave_small && plan.n >= sw.wave_min_n && only_small_children(plan, L);
+    return levels;
+}
+
+// the wave-per-front solve kernels do not depend on the LDS class: one launch per level
+inline LevelLaunches merge_level_solves(const LevelLaunches& levels) {
+    LevelLaunches solves(levels.size());
+    for (size_t l = 0; l < levels.size(); ++l) {
+        MfLaunch S{};
+        for (auto& L : levels[l]) {
+            if (!L.cls || L.tiny) { solves[l].push_back(L); continue; }
+            if (S.count == 0) S = L;
+            else {
+                S.count += L.count;
+                S.max_m = std::max(S.max_m, L.max_m);
+                S.max_k = std::max(S.max_k, L.max_k);
+            }
+        }
+        if (S.count) solves[l].insert(solves[l].begin(), S);
+    }
+    return solves;
+}
+
+// fronts of the large-front launches
+inline std::vector<char> fronts_on_big_path(const MfPlan& plan, const LevelLaunches& levels) {
+    std::vector<char> on_big_path(plan.fronts.size(), 0);
+    for (auto& lev : levels)
+        for (auto& L : lev)
+            if (!L.cls)
+                for (int32_t q = L.first; q < L.first + L.count; ++q) on_big_path[q] = 1;
+    return on_big_path;
+}
+
+// Leaf fronts (m <= 16, the 16-lanes-per-front kernels) as packed lower triangles: m(m+1)/2 contiguous doubles
+// instead of m*m, read back by their parents' extend-add and by the sweeps.  Only when every parent is an LDS
+// front (the large-front assembly kernels read square children).  Whether the leaves of this plan can be packed.
+inline bool leaf_fronts_packable(const MfPlan& plan, const LevelLaunches& levels, const std::vector<char>& on_big_path) {
+    bool any = false;
+    for (auto& lev : levels)
+        for (auto& L : lev)
+            if (L.tiny)
+                for (int32_t q = L.first; q < L.first + L.count; ++q) {
+                    const int32_t par = plan.fronts[q].parent;
+                    if (par >= 0 && on_big_path[par]) return false;
+                    any = true;
+                }
+    return any;
+}
+
+// ---- shape predicates of the launchers ------------------------------------------------------------------------
+enum MfAssembly : int32_t { MF_ASM_NONE = 0, MF_ASM_GATHER = 1, MF_ASM_COLS = 2 };
+enum MfBlock0 : int32_t { MF_B0_NA = 0, MF_B0_GATHER = 1, MF_B0_DIAG0 = 2, MF_B0_STEP0 = 3 };
+enum MfBackward : int32_t { MF_BWD_NA = 0, MF_BWD_K8 = 1, MF_BWD_K16 = 2, MF_BWD_GENERAL = 3 };
+
+// mf_big_gather: for every child the position of each front row in the child's update block
+inline size_t big_gather_lds(const MfLaunch& L) { return (size_t)L.max_child * (size_t)L.max_m * sizeof(int32_t); }
+// Assembly of the fronts of a large-front launch: the gathering kernel when it applies (few children, index table
+// within 40 KB), the column-tiled one otherwise.  LDS fronts assemble inside their factorization kernel.
+inline MfAssembly big_assembly_kind(const MfLaunch& L) {
+    if (L.cls) return MF_ASM_NONE;
+    if (L.max_child < 1 || L.max_child > GATHER_MAX_CHILD || big_gather_lds(L) > 40 * 1024) return MF_ASM_COLS;
+    return MF_ASM_GATHER;
+}
+// Block 0 of the pivot chain on the inverse-based path (`inv`: L.inv and the solver is not in robust mode): an extra
+// workgroup of the gather launch when that kernel applies; otherwise once per front up front (many fronts, or the
+// interface front, whose sum over ranks is only complete after the assembly) or inside every tile of step 0 (few fronts).
+inline MfBlock0 big_block0_kind(const MfLaunch& L, bool inv) {
+    if (L.cls || !inv) return MF_B0_NA;
+    if (!L.iface && big_assembly_kind(L) == MF_ASM_GATHER) return MF_B0_GATHER;
+    return (L.iface || L.count >= BIG_DIAG0_MIN_COUNT) ? MF_B0_DIAG0 : MF_B0_STEP0;
+}
+// Backward sweep of an LDS launch: the register-resident variants for max_k <= 8 / <= 16, 0 = the general one
+// (a 32-column variant holds 143 registers and loses more to occupancy on the 8192-front level than it gains)
+inline int backward_small_kmax(const MfLaunch& L) { return L.max_k <= 8 ? 8 : (L.max_k <= 16 ? 16 : 0); }
+
+// ---- read-only report (mgbhip_solver_launches; mf_host_launches of the CPU checker build) ------------------------
+// One row of MF_LAUNCH_ROW int32 per factorization launch, leaves first:
+//   [0] tree level  [1] first  [2] count  [3] cls  [4] max_m  [5] max_k  [6] max_child
+//   [7] tiny  [8] wave  [9] inv (as factor() runs it)  [10] iface  [11] fronts stored as packed triangles
+//   [12] MfAssembly  [13] MfBlock0  [14] MfBackward of the level's LDS sweep  [15] 0
+// Returns the number of launches; writes at most cap rows.
+constexpr int MF_LAUNCH_ROW = 16;
+inline int64_t launch_rows(const LevelLaunches& levels, const LevelLaunches& solves, bool leaf_packed, bool robust,
+                           int32_t* out, int64_t cap) {
+    int64_t n = 0;
+    for (size_t l = 0; l < levels.size(); ++l) {
+        int32_t bwd = 0;
+        for (auto& S : solves[l])
+            if (S.cls && !S.tiny) { const int km = backward_small_kmax(S); bwd = km == 8 ? MF_BWD_K8 : (km == 16 ? MF_BWD_K16 : MF_BWD_GENERAL); }
+        for (auto& L : levels[l]) {
+            if (n < cap && out) {
+                const bool inv = L.inv && !robust;
+                int32_t* r = out + n * MF_LAUNCH_ROW;
+                r[0] = (int32_t)l; r[1] = L.first; r[2] = L.count; r[3] = L.cls; r[4] = L.max_m; r[5] = L.max_k; r[6] = L.max_child;
+                r[7] = L.tiny; r[8] = L.wave; r[9] = inv; r[10] = L.iface; r[11] = L.tiny && leaf_packed;
+                r[12] = big_assembly_kind(L); r[13] = big_block0_kind(L, inv); r[14] = (L.cls && !L.tiny) ? bwd : (int32_t)MF_BWD_NA; r[15] = 0;
+            }
+            ++n;
+        }
+    }
+    return n;
+}
+
+}  // namespace mgbhip

@@ -11,7 +11,8 @@
 // The kernels and their host launchers live in the family headers, all part of this one translation unit
 // (mf_device.hpp says why): mf_small.hpp (fronts factored out of LDS, m <= lds_cap), mf_big_subst.hpp and
 // mf_big_inv.hpp (the two generations of multi-workgroup kernels for larger fronts).  Here: analyze() turns the
-// symbolic plan into per-level launch lists, factor() / forward_pass() / backward_pass() walk them.
+// symbolic plan into per-level launch lists (the classification itself is host-only code in mf_launch_plan.hpp, shared with
+// the CPU checker build), factor() / forward_pass() / backward_pass() walk them.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -30,32 +31,6 @@ namespace mgbhip {
 
 namespace {
 
-// Environment switches of the launch plan (tools/README.md, switch table), read in one place by analyze().
-struct MfSwitches {
-    bool no_geo;            // MGBHIP_NO_GEO=1: no coordinates for the ordering (BFS level-set bisection)
-    bool old_big;           // MGBHIP_OLD_BIG=1: substitution kernels for every large front
-    bool merge_groups;      // off with MGBHIP_NO_MERGE_GROUPS=1
-    bool packed_leaves;     // off with MGBHIP_NO_PACKED_LEAVES=1
-    bool wave_small;        // off with MGBHIP_NO_WAVE_SMALL=1
-    // Size gates of the two fastest kernel families (A/B switches of tests/test_gpu_solver.py).  Round 2 kept both off
-    // systems of < 1024 unknowns after two creeping solves failed with them.  Round 3: all kernel selections are
-    // equally backward stable on graded matrices (2.9e-13 componentwise) and the 27-problem sweep agrees with the
-    // oracle without any gate (the 37-unknown case that motivated the wave gate: 5356 vs 5355 iterations), so the
-    // one-wave kernel is ungated.  The inverse-based large-front path keeps its gate: without it config 4's phase I
-    // (fem3d L=6, 9 000 iterations hugging the wall on a 145-unknown level) ends in "Initial centering failed" --
-    // applying W = L_jj^{-1} is only forward stable in cond(L_jj), and such systems gain nothing from it.
-    int64_t inv_min_n;      // MGBHIP_INV_MIN_N, default 1024
-    int64_t wave_min_n;     // MGBHIP_WAVE_MIN_N, default 0
-    static MfSwitches from_env() {
-        auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
-        auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-        return {on("MGBHIP_NO_GEO"), on("MGBHIP_OLD_BIG"), !on("MGBHIP_NO_MERGE_GROUPS"), !on("MGBHIP_NO_PACKED_LEAVES"),
-                !on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0)};
-    }
-};
-
-using LevelLaunches = std::vector<std::vector<MfLaunch>>;
-
 // dynamic LDS above 64 KB needs an explicit opt-in: each bound is the kernel's own size function at its cap
 int32_t query_lds_cap() {          // largest front class of mf_factor_small; the 64 KB classes if the opt-in is refused
     if (hipFuncSetAttribute((const void*)mf_factor_small<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -71,140 +46,6 @@ bool query_inv_optin() {           // the single-workgroup solves of the inverse
         return true;
     (void)hipGetLastError();
     return false;
-}
-
-MfLaunch launch_of_range(const MfPlan& plan, MfLaunch L, int32_t first, int32_t count) {     // L's flags over [first, first + count)
-    L.first = first; L.count = count;
-    L.max_m = 0; L.max_k = 0; L.max_child = 0;
-    for (int32_t t = first; t < first + count; ++t) {
-        L.max_m = std::max(L.max_m, plan.fronts[t].m);
-        L.max_k = std::max(L.max_k, plan.fronts[t].k);
-        L.max_child = std::max(L.max_child, plan.fronts[t].nchild);
-    }
-    return L;
-}
-
-// Launches of one level are independent but share a stream: a straggler group (4 fronts of the next
-// smaller class, 60 LDS-sized fronts beside 196 large ones) costs a full, latency-bound launch of
-// 20-30 us.  Fold small groups into their neighbour:
-//   (1) LDS-class fronts of a level whose bulk is on the large-front path join that path (it handles any m);
-//   (2) an LDS class with few fronts joins the next larger LDS class of the level.
-// Fronts are sorted by m inside a level, so a merge just extends the neighbour's range downwards.
-void merge_straggler_groups(const MfPlan& plan, std::vector<MfLaunch>& G) {
-    auto absorb = [&](size_t into, size_t from) {        // from == into - 1
-        MfLaunch& A = G[into];
-        const MfLaunch& B = G[from];
-        A.first = B.first;
-        A.count += B.count;
-        A.max_k = std::max(A.max_k, B.max_k);
-        A.max_child = std::max(A.max_child, B.max_child);
-        G.erase(G.begin() + (long)from);
-    };
-    if (G.size() >= 2 && G.back().cls == 0 && G.back().inv) {
-        int64_t lds_count = 0;
-        bool ok = true;
-        for (size_t g = 0; g + 1 < G.size(); ++g) { lds_count += G[g].count; ok = ok && !G[g].tiny && plan.fronts[G[g].first].m > 32; }
-        if (ok && lds_count <= G.back().count)
-            while (G.size() >= 2) absorb(G.size() - 1, G.size() - 2);
-    }
-    for (size_t g = 0; g + 1 < G.size();) {
-        const bool next_lds = G[g + 1].cls != 0;
-        if (next_lds && !G[g].tiny && (G[g].count < 256 || 4 * (int64_t)G[g].count < G[g + 1].count)) absorb(g + 1, g);
-        else ++g;
-    }
-}
-
-// The interface front gets a launch of its own on the large-front path (assemble / reduce / factor are separate
-// kernels there, whatever its size): the launch that holds it is split around it.
-void split_interface_front(const MfPlan& plan, LevelLaunches& levels, bool inv_allowed) {
-    const int32_t q = plan.iface_front;
-    for (auto& G : levels) {
-        for (size_t g = 0; g < G.size(); ++g) {
-            const MfLaunch L = G[g];
-            if (q < L.first || q >= L.first + L.count) continue;
-            std::vector<MfLaunch> out;
-            if (q > L.first) out.push_back(launch_of_range(plan, L, L.first, q - L.first));
-            MfLaunch I = launch_of_range(plan, L, q, 1);
-            I.cls = 0; I.tiny = false; I.wave = false; I.iface = true;
-            I.inv = (I.max_m <= BIG_INV_MAX_M && inv_allowed);
-            out.push_back(I);
-            if (q + 1 < L.first + L.count) out.push_back(launch_of_range(plan, L, q + 1, L.first + L.count - q - 1));
-            G.erase(G.begin() + (long)g);
-            G.insert(G.begin() + (long)g, out.begin(), out.end());
-            break;
-        }
-    }
-}
-
-// Launches of fronts with m <= 48 whose children are all small (update block <= 8 x 8: the element leaves under a
-// level-1 front, or no children) go to the one-wave-per-front kernel mf_factor_wave; with large children the
-// 256-thread kernel's extend-add is faster and the launch stays there.
-bool only_small_children(const MfPlan& plan, const MfLaunch& L) {
-    for (int32_t q = L.first; q < L.first + L.count; ++q) {
-        const Front& f = plan.fronts[q];
-        for (int32_t c = 0; c < f.nchild; ++c) {
-            const Front& ch = plan.fronts[plan.children[f.child_off + c]];
-            if ((ch.m - ch.k) * (ch.m - ch.k) > 64) return false;
-        }
-    }
-    return true;
-}
-
-// The factorization's launches, per tree level and leaves first: a function of the plan, the LDS cap, whether the
-// inverse-based solves got their LDS (inv_ok) and the switches -- no device call.
-LevelLaunches classify_launches(const MfPlan& plan, int32_t lds_cap, bool inv_ok, const MfSwitches& sw) {
-    static const int32_t classes[] = {16, 32, 48, 64, 88, 128};
-    const bool inv_allowed = inv_ok && !sw.old_big && plan.n >= sw.inv_min_n;
-    const int32_t nlev = (int32_t)plan.level_ptr.size() - 1;
-    LevelLaunches levels(nlev);
-    for (int32_t l = 0; l < nlev; ++l) {
-        int32_t i = plan.level_ptr[l];
-        const int32_t end = plan.level_ptr[l + 1];
-        while (i < end) {
-            const int32_t m = plan.fronts[i].m;
-            int32_t cls = 0;
-            for (int32_t c : classes)
-                if (m <= c && c <= lds_cap) { cls = c; break; }
-            int32_t j = i;
-            if (cls) {
-                while (j < end && plan.fronts[j].m <= cls) ++j;
-            } else {
-                j = end;   // sorted by m: everything left in the level is large
-            }
-            MfLaunch L = launch_of_range(plan, MfLaunch{}, i, j - i);
-            L.cls = cls;
-            L.max_m = plan.fronts[j - 1].m;
-            L.tiny = (l == 0 && cls == 16);     // leaves with m <= 16: 16 lanes per front
-            L.inv = (cls == 0 && L.max_m <= BIG_INV_MAX_M && inv_allowed);
-            levels[l].push_back(L);
-            i = j;
-        }
-        if (sw.merge_groups) merge_straggler_groups(plan, levels[l]);
-    }
-    if (plan.iface_front >= 0) split_interface_front(plan, levels, inv_allowed);
-    for (auto& lev : levels)
-        for (auto& L : lev)
-            L.wave = !L.tiny && L.cls && L.cls <= 48 && sw.wave_small && plan.n >= sw.wave_min_n && only_small_children(plan, L);
-    return levels;
-}
-
-// the wave-per-front solve kernels do not depend on the LDS class: one launch per level
-LevelLaunches merge_level_solves(const LevelLaunches& levels) {
-    LevelLaunches solves(levels.size());
-    for (size_t l = 0; l < levels.size(); ++l) {
-        MfLaunch S{};
-        for (auto& L : levels[l]) {
-            if (!L.cls || L.tiny) { solves[l].push_back(L); continue; }
-            if (S.count == 0) S = L;
-            else {
-                S.count += L.count;
-                S.max_m = std::max(S.max_m, L.max_m);
-                S.max_k = std::max(S.max_k, L.max_k);
-            }
-        }
-        if (S.count) solves[l].insert(solves[l].begin(), S);
-    }
-    return solves;
 }
 
 // update-vector gather lists of the large fronts (forward solve): for every local index the entries of
@@ -236,26 +77,16 @@ void build_gather_lists(const MfPlan& plan, const std::vector<char>& on_big_path
     if (ug_src.empty()) ug_src.push_back(0);
 }
 
-// Leaf fronts (m <= 16, the 16-lanes-per-front kernels) as packed lower triangles: m(m+1)/2 contiguous doubles
-// instead of m*m, read back by their parents' extend-add and by the sweeps.  Only when every parent is an LDS
-// front (the large-front assembly kernels read square children).  Returns whether any front was packed.
+// Leaf fronts as packed lower triangles where the plan allows it (leaf_fronts_packable, mf_launch_plan.hpp): marks them
+// in the device descriptors.  Returns whether any front was packed.
 bool pack_leaf_fronts(const MfPlan& plan, const LevelLaunches& levels, const std::vector<char>& on_big_path,
                       std::vector<FrontDev>& fd) {
-    bool any = false;
+    if (!leaf_fronts_packable(plan, levels, on_big_path)) return false;
     for (auto& lev : levels)
         for (auto& L : lev)
             if (L.tiny)
-                for (int32_t q = L.first; q < L.first + L.count; ++q) {
-                    const int32_t par = plan.fronts[q].parent;
-                    if (par >= 0 && on_big_path[par]) return false;
-                    any = true;
-                }
-    if (any)
-        for (auto& lev : levels)
-            for (auto& L : lev)
-                if (L.tiny)
-                    for (int32_t q = L.first; q < L.first + L.count; ++q) fd[q].packed = 1;
-    return any;
+                for (int32_t q = L.first; q < L.first + L.count; ++q) fd[q].packed = 1;
+    return true;
 }
 
 // a_dst for the kernels that keep the front as a packed LDS triangle.  Leaf fronts with m <= 16 (mf_factor_tiny)
@@ -360,14 +191,12 @@ void MfSolver::analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, 
     level_launches = classify_launches(plan, lds_cap, inv_ok, sw);
     level_solves = merge_level_solves(level_launches);
     uses_inv = false;
-    std::vector<char> on_big_path((size_t)nf, 0);       // fronts of the large-front launches
+    const std::vector<char> on_big_path = fronts_on_big_path(plan, level_launches);
     int32_t max_big = 1;
     for (auto& lev : level_launches)
         for (auto& L : lev) {
             uses_inv = uses_inv || L.inv;
-            if (L.cls) continue;
-            max_big = std::max(max_big, L.count);
-            for (int32_t q = L.first; q < L.first + L.count; ++q) on_big_path[q] = 1;
+            if (!L.cls) max_big = std::max(max_big, L.count);
         }
     d_dscr.alloc((size_t)max_big * 2 * NB * NB);
 
@@ -427,25 +256,22 @@ void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timer
                 // of every front is factored by an extra workgroup of the gather launch when that kernel applies;
                 // otherwise once per front up front (many fronts) or inside every tile of step 0 (few fronts).
                 const bool inv = L.inv && !robust;
-                bool diag_done;
+                const MfBlock0 b0 = big_block0_kind(L, inv);       // never the gather workgroup for the interface front
+                MGB_REQUIRE(!L.iface || (bool)iface_reduce, "MfSolver: interface front without a reduction hook");
+                launch_big_assemble(a, L, b0 == MF_B0_GATHER);
                 if (L.iface) {
-                    // assemble this rank's contribution, sum over ranks, then factor the complete front (every rank the same)
-                    MGB_REQUIRE((bool)iface_reduce, "MfSolver: interface front without a reduction hook");
+                    // this rank's contribution is assembled: sum over ranks, then factor the complete front (every rank the same)
                     const Front& fi = plan.fronts[L.first];
-                    launch_big_assemble(a, L, false);
                     // sum the lower triangle over ranks: (m + 1) m / 2 doubles instead of m^2
                     const int64_t tri = (int64_t)fi.m * (fi.m + 1) / 2;
                     d_ifpack.ensure((size_t)tri);
                     launch_tri_pack(fi.m, d_arena.p + fi.F_off, d_ifpack.p, false, st);
                     iface_reduce(d_ifpack.p, tri);
                     launch_tri_pack(fi.m, d_arena.p + fi.F_off, d_ifpack.p, true, st);
-                    diag_done = false;      // the sum is not factored yet
-                } else
-                    diag_done = launch_big_assemble(a, L, inv);
+                }
                 if (inv) {
-                    const bool pre_diag = diag_done || L.iface || L.count >= 24;
-                    if (pre_diag && !diag_done) launch_big_diag0(a, L, L.count);
-                    launch_inv_steps(a, L, L.count, !pre_diag);
+                    if (b0 == MF_B0_DIAG0) launch_big_diag0(a, L, L.count);
+                    launch_inv_steps(a, L, L.count, b0 == MF_B0_STEP0);
                 } else
                     launch_subst_steps(a, L, L.count);
             }
@@ -556,6 +382,10 @@ void MfSolver::chain_stats(double* out) const {
             if (L.count) bwd += 1;
     out[0] = blocks; out[1] = big_levels; out[2] = fac; out[3] = bwd;
     out[4] = (double)plan.arena_doubles; out[5] = (double)plan.factor_flops; out[6] = extra; out[7] = 0.0;
+}
+
+int64_t MfSolver::launches(int32_t* out, int64_t cap) const {
+    return launch_rows(level_launches, level_solves, leaf_packed, robust, out, cap);
 }
 
 void MfSolver::status_async(int32_t* h_dst2, hipStream_t st) const {

@@ -738,9 +738,9 @@ inline void launch_backward_small_k(const SolveArgs& a, const MfLaunch& L) {
                        a.arena, a.y, a.x);
 }
 inline void launch_backward_small(const SolveArgs& a, const MfLaunch& L) {
-    // (a 32-column variant holds 143 registers and loses more to occupancy on the 8192-front level than it gains)
-    if (L.max_k <= 8) launch_backward_small_k<8>(a, L);
-    else if (L.max_k <= 16) launch_backward_small_k<16>(a, L);
+    const int kmax = backward_small_kmax(L);        // mf_launch_plan.hpp
+    if (kmax == 8) launch_backward_small_k<8>(a, L);
+    else if (kmax == 16) launch_backward_small_k<16>(a, L);
     else launch_backward_small_k<0>(a, L);
 }
 

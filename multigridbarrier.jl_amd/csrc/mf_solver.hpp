@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 #include "mf_analysis.hpp"
+#include "mf_launch_plan.hpp"     // MfLaunch and the launch plan (host only)
 #include "kernels.hpp"
 
 namespace mgbhip {
@@ -19,18 +20,6 @@ struct FrontDev {
     int64_t ug_off;        // large fronts: offset of the update-vector gather list (m + 1 pointers), -1 otherwise
     int32_t packed;        // leaf fronts (m <= 16) stored as a packed lower triangle: column c at c*m - c(c-1)/2, rows c..m-1
     int32_t pad_;
-};
-
-struct MfLaunch {          // one kernel launch: a contiguous range of fronts of one size class
-    int32_t first, count;
-    int32_t cls;           // LDS working size (0 = large-front multi-workgroup path)
-    int32_t max_m, max_k;  // largest front / pivot block in the range
-    int32_t max_child = 0; // most children of a front in the range
-    bool tiny = false;     // leaf fronts with m <= 16: 16-lanes-per-front kernels
-    bool wave = false;     // m <= 48 and only small children: one wave per front (mf_factor_wave), packed LDS triangle
-    bool inv = false;      // large fronts on the inverse-based path (W_j = L_jj^{-1} in the arena, pivots in dvec)
-    bool iface = false;    // the interface front of a domain-decomposed system, alone in its launch: assembled, summed
-                           // over ranks (MfSolver::iface_reduce), then factored redundantly on every rank
 };
 
 // Device arrays of the factorization in progress / of one triangular sweep, as the launchers beside the kernels
@@ -105,6 +94,9 @@ class MfSolver {
     // [4] doubles of the frontal arena, [5] factorization flops, [6] doubles the large fronts' trailing updates read + write
     // beyond one pass over the arena (the re-reads a tile-resident factorization would not make), [7] reserved
     void chain_stats(double* out8) const;
+    // The factorization launches as the last analyze() planned them and factor() runs them (mgbhip_solver_launches):
+    // rows of MF_LAUNCH_ROW int32 (launch_rows, mf_launch_plan.hpp), leaves first.  Returns the number of launches.
+    int64_t launches(int32_t* out, int64_t cap) const;
     int status(hipStream_t st);     // synchronises; MGBHIP_OK or MGBHIP_ERR_NOT_SPD
     // enqueue the copy of the flag only (pinned destination); interpret it after the caller's sync
     void status_async(int32_t* h_dst, hipStream_t st) const;

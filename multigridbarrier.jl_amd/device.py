@@ -115,7 +115,7 @@ EXPORTS = [
     "mgbhip_vec_alloc", "mgbhip_vec_free", "mgbhip_vec_len", "mgbhip_vec_upload", "mgbhip_vec_download",
     "mgbhip_vec_fill", "mgbhip_vec_copy", "mgbhip_vec_axpy", "mgbhip_vec_scale", "mgbhip_vec_dot",
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
-    "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_interpolate", "mgbhip_interpolate_grad",
+    "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_solver_launches", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy",
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
@@ -173,6 +173,8 @@ def load_library():
     lib.mgbhip_solver_stats.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.mgbhip_solver_chain.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.mgbhip_level_plan.argtypes = [C.c_void_p, C.c_int32, _ip]
+    lib.mgbhip_solver_launches.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int64]
+    lib.mgbhip_solver_launches.restype = C.c_int64
     vp = C.c_void_p
     lib.mgbhip_vec_alloc.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     lib.mgbhip_vec_free.argtypes = [vp]
@@ -662,6 +664,36 @@ class DeviceProblem:
         for k in ("R_unit", "R_long", "T_long", "acc", "long_lists", "planned"):
             d[k] = bool(d[k])
         return d
+
+    LAUNCH_KEYS = ("level", "first", "count", "cls", "max_m", "max_k", "max_child", "tiny", "wave", "inv", "iface", "packed",
+                   "assembly", "block0", "backward")
+    ASSEMBLY = ("none", "gather", "columns")
+    BLOCK0 = ("n/a", "gather", "diag0", "step0")
+    BACKWARD = ("n/a", "k8", "k16", "general")
+
+    @classmethod
+    def launch_rows(cls, raw) -> list:
+        """Rows of `mgbhip_solver_launches` (an int array of 16 columns) as dicts."""
+        rows = []
+        for r in np.asarray(raw, dtype=np.int64).reshape(-1, 16):
+            d = dict(zip(cls.LAUNCH_KEYS, (int(v) for v in r)))
+            for k in ("tiny", "wave", "inv", "iface", "packed"):
+                d[k] = bool(d[k])
+            d["assembly"], d["block0"], d["backward"] = cls.ASSEMBLY[d["assembly"]], cls.BLOCK0[d["block0"]], cls.BACKWARD[d["backward"]]
+            rows.append(d)
+        return rows
+
+    def solver_launches(self, level: int) -> list:
+        """The factorization launches of `level`, leaves first (`mgbhip_solver_launches`): which kernel every range of fronts
+        takes.  Read-only; valid after the level's first solve."""
+        n = self.lib.mgbhip_solver_launches(self.handle, level, None, 0)
+        if n < 0:
+            _check(self.lib, int(-n))
+        out = (C.c_int32 * (16 * max(int(n), 1)))()
+        n = self.lib.mgbhip_solver_launches(self.handle, level, out, n)
+        if n < 0:
+            _check(self.lib, int(-n))
+        return self.launch_rows(np.frombuffer(out, dtype=np.int32)[:16 * int(n)])
 
     def close(self):
         if self.handle:

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../multigridbarrier.jl_amd/csrc/mf_analysis.hpp"
+#include "../../multigridbarrier.jl_amd/csrc/mf_launch_plan.hpp"
 #include <map>
 #include <memory>
 
@@ -256,4 +257,38 @@ extern "C" uint64_t mf_host_plan_hash(int64_t n, const int32_t* rowptr, const in
     mix(plan.a_colptr.data(), plan.a_colptr.size() * sizeof(int32_t));
     mix(plan.level_ptr.data(), plan.level_ptr.size() * sizeof(plan.level_ptr[0]));
     return h ? h : 1;
+}
+
+
+// The launch plan the device would give this pattern (tests/solver_gate_cases.py): mf_analyze with the options of
+// MfSolver::analyze (border, protect_peeled, the coordinate hint), then classify_launches with the switches of the environment.
+// lds_cap / inv_ok are what the device queries (128 / true on gfx950).  Rows as mgbhip_solver_launches; fronts4 (optional,
+// cap_fronts rows): (level, m, k, nchild) per front; order (optional, n + 1 entries): the unknowns in elimination order,
+// front by front (the pivots of front 0, then of front 1, ...; the border unknown n last).  Returns the number of launches, -1 on an analysis error.
+extern "C" int64_t mf_host_launches(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* coords, int32_t dim,
+                                    int32_t protect_peeled, int32_t lds_cap, int32_t inv_ok, int32_t* out, int64_t cap,
+                                    int32_t* fronts4, int64_t cap_fronts, int64_t* nfronts, int32_t* order) {
+    const MfSwitches sw = MfSwitches::from_env();
+    MfPlan plan;
+    MfOptions opt;
+    opt.protect_peeled = protect_peeled != 0;
+    opt.border = true;
+    try {
+        mf_analyze(n, rowptr, colidx, opt, plan, (sw.no_geo || !coords) ? nullptr : coords, dim);
+    } catch (const std::exception&) {
+        return -1;
+    }
+    const LevelLaunches levels = classify_launches(plan, lds_cap, inv_ok != 0 && !sw.old_big, sw);
+    const bool packed = sw.packed_leaves && leaf_fronts_packable(plan, levels, fronts_on_big_path(plan, levels));
+    if (nfronts) *nfronts = (int64_t)plan.fronts.size();
+    for (int64_t i = 0; fronts4 && i < (int64_t)plan.fronts.size() && i < cap_fronts; ++i) {
+        const Front& f = plan.fronts[i];
+        fronts4[4 * i + 0] = f.level; fronts4[4 * i + 1] = f.m; fronts4[4 * i + 2] = f.k; fronts4[4 * i + 3] = f.nchild;
+    }
+    if (order) {
+        int64_t t = 0;
+        for (const Front& f : plan.fronts)
+            for (int32_t j = 0; j < f.k && t <= n; ++j) order[t++] = plan.front_idx[f.idx_off + j];
+    }
+    return launch_rows(levels, merge_level_solves(levels), packed, false, out, cap);
 }
