@@ -459,6 +459,44 @@ int mgbhip_surface_shade(mgbhip_surface* s, int64_t R, int32_t K, const double* 
                          double* layer /* R x K x 4 */);
 int mgbhip_surface_destroy(mgbhip_surface* s); /* NULL is a no-op */
 
+/* ---- field lines: the lines of a vector field traced through the mesh ----------------------------------------------
+ * The field is v = (z[:, 0], .., z[:, d-1]) [field = VECTOR: z is (p*N) x d row-major, the element-space functions of
+ * the components] or v = grad u [field = GRADIENT: z is the p*N values of u].  v(y) is evaluated as
+ * mgbhip_interpolate [VECTOR] / mgbhip_interpolate_grad [GRADIENT] evaluate it and is bitwise what they return: the
+ * lowest-index element of the candidate list of y's cell that contains y, never a warm start from the previous element.
+ * create uploads the mesh, builds the location grid and keeps both on the device with z; set_field replaces z alone [the
+ * same shape].  trace follows S lines from seeds [S x d; a non-finite seed is outside the mesh] by the classical
+ * Runge-Kutta scheme with the signed step h [finite, != 0], without fused multiply-add:
+ *     k1 = v(x);  k2 = v(x + (0.5 h) k1);  k3 = v(x + (0.5 h) k2);  k4 = v(x + h k3);
+ *     x <- x + (h / 6) (((k1 + 2 k2) + 2 k3) + k4).
+ * Every stage forms speed = sqrt(v . v) [squares added in axis order]; with normalize != 0 the stage velocity is
+ * v / speed, so |h| is arc length.  A stage point without an element ends the line at the current x with LEFT [OUTSIDE
+ * when it is the seed itself: the line then has no point]; !(speed > min_speed) ends it with STALLED [also for NaN, and
+ * for 0 / 0 under normalize]; otherwise it ends after max_steps [>= 1] steps.  min_speed is finite and >= 0.
+ *  - points [S x (max_steps + 1) x d]: row 0 of a line is its seed, row i the point after i steps, NaN from row n on.
+ *  - n [S]: the number of points of the line, 0 for a seed in no element.  status [S]: MGBHIP_STREAM_*.
+ *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1 and P2
+ *    [straight elements] are accepted.  S = 0 is a no-op; S (max_steps + 1) d >= 2^31 is MGBHIP_ERR_INVALID before
+ *    anything is allocated.
+ * One lane traces one line and stores by seed index: two calls return bitwise equal arrays.  The handle belongs to the
+ * context it was created from and must be destroyed before it.  Host pointers; the work runs on ctx's stream and is
+ * complete on return.                                                                                               */
+#define MGBHIP_STREAM_VECTOR 0
+#define MGBHIP_STREAM_GRADIENT 1
+#define MGBHIP_STREAM_MAX_STEPS 0
+#define MGBHIP_STREAM_LEFT 1
+#define MGBHIP_STREAM_STALLED 2
+#define MGBHIP_STREAM_OUTSIDE 3
+typedef struct mgbhip_stream mgbhip_stream;
+int mgbhip_stream_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                         const double* x, const double* table, int32_t field, const double* z,
+                         mgbhip_stream** out);
+int mgbhip_stream_set_field(mgbhip_stream* s, const double* z /* (p*N) x d or p*N */);
+int mgbhip_stream_trace(mgbhip_stream* s, int64_t S, const double* seeds /* S x d */, double h, int32_t max_steps,
+                        int32_t normalize, double min_speed, double* points /* S x (max_steps + 1) x d */,
+                        int32_t* n /* S */, int32_t* status /* S */);
+int mgbhip_stream_destroy(mgbhip_stream* s); /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

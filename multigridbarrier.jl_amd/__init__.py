@@ -29,5 +29,6 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .contour import isocontour, Contour
     from .raycast import RayCaster, camera_rays, render_volume
     from .surface import TriangleCaster, Hits, render_surfaces, render_figure
+    from .streamlines import StreamTracer, Streamlines, streamlines
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

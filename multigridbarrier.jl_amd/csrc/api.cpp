@@ -13,6 +13,7 @@
 #include "interpolate.hpp"
 #include "problem.hpp"
 #include "raycast.hpp"
+#include "stream.hpp"
 #include "surface.hpp"
 
 using namespace mgbhip;
@@ -73,6 +74,13 @@ struct mgbhip_surface {
     Surface sf;
 };
 static int dev_of(const mgbhip_surface* s) { return (s && s->ctx) ? s->ctx->device : -1; }
+
+// a field-line tracer (stream.hpp) and the context it lives in
+struct mgbhip_stream {
+    mgbhip_ctx* ctx = nullptr;
+    StreamTracer tr;
+};
+static int dev_of(const mgbhip_stream* s) { return (s && s->ctx) ? s->ctx->device : -1; }
 
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
@@ -1010,6 +1018,63 @@ int mgbhip_raycast_render_layers(mgbhip_raycast* rc, const double* u, int32_t K,
                 MGB_REQUIRE(std::isfinite(layer[(r * nhits + k) * 4 + c]), "raycast: every layer entry must be finite");
         }
     raycast_render_layers(rc->rc, u, K, transfer, lo, hi, nhits, t_hit, layer, out, rc->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_stream_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                         const double* table, int32_t field, const double* z, mgbhip_stream** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
+                "stream: only the Q_k (d = 2, 3), P1 and P2 families are traced");
+    MGB_REQUIRE(N > 0, "stream: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1 && (int64_t)p * N * 3 < (int64_t)INT32_MAX, "stream: bad sizes");
+    MGB_REQUIRE(field == MGBHIP_STREAM_VECTOR || field == MGBHIP_STREAM_GRADIENT, "stream: unknown field kind");
+    MGB_REQUIRE(z != nullptr, "null argument");
+    InterpIn geo;
+    geo.family = family; geo.d = d; geo.k = k; geo.p = p; geo.N = N; geo.x = x; geo.table = table;
+    interpolate_check_geometry(geo);
+    for (int64_t i = 0; i < (int64_t)p * N * d; ++i) MGB_REQUIRE(std::isfinite(x[i]), "stream: non-finite node coordinates");
+    std::unique_ptr<mgbhip_stream> s(new mgbhip_stream());
+    s->ctx = ctx;
+    stream_build(s->tr, geo, field, z, ctx->stream);
+    *out = s.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_stream_set_field(mgbhip_stream* s, const double* z) {
+    MGB_API_BEGIN_ON(s)
+    MGB_REQUIRE(s != nullptr, "null stream tracer");
+    MGB_REQUIRE(z != nullptr, "null argument");
+    stream_set_field(s->tr, z, s->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_stream_trace(mgbhip_stream* s, int64_t S, const double* seeds, double h, int32_t max_steps, int32_t normalize,
+                        double min_speed, double* points, int32_t* n, int32_t* status) {
+    MGB_API_BEGIN_ON(s)
+    MGB_REQUIRE(s != nullptr, "null stream tracer");
+    MGB_REQUIRE(S >= 0 && max_steps >= 1, "stream: bad sizes (S >= 0, max_steps >= 1)");
+    MGB_REQUIRE(std::isfinite(h) && h != 0.0, "stream: the step must be finite and non-zero");
+    MGB_REQUIRE(std::isfinite(min_speed) && min_speed >= 0.0, "stream: min_speed must be finite and >= 0");
+    // by count, in a type that cannot overflow: S (max_steps + 1) d < 2^31
+    MGB_REQUIRE((long double)S * ((long double)max_steps + 1.0L) * (long double)s->tr.d < 2147483648.0L,
+                "stream: S * (max_steps + 1) * d exceeds 32-bit indexing");
+    MGB_REQUIRE(S == 0 || (seeds != nullptr && points != nullptr && n != nullptr && status != nullptr), "null argument");
+    stream_trace(s->tr, S, seeds, h, max_steps, normalize != 0, min_speed, points, n, status, s->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_stream_destroy(mgbhip_stream* s) {
+    MGB_API_BEGIN_ON(s)
+    if (!s) return MGBHIP_OK;
+    (void)hipStreamSynchronize(s->ctx->stream);
+    delete s;
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -21,6 +21,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "interp_device.hpp"      // the locate and evaluate device functions and their constants (shared with stream.hip)
 #include "interpolate.hpp"
 
 // No fused multiply-adds in this file: the 1-D path reproduces the reference's bisection operation for operation, so
@@ -30,34 +31,6 @@
 namespace mgbhip {
 
 namespace {
-
-constexpr int BLOCK = 256;
-constexpr int NEWTON_MAXIT = 32;
-constexpr int BISECT_MAXIT = 128;
-constexpr double ACCEPT_TOL = 1e-11;       // containment tolerance in reference coordinates (at least)
-constexpr double NEWTON_STEP_TOL = 1e-13;  // converged once max |dxi| falls below this (at least)
-// Rounding level of a reference coordinate: x(xi) - q carries an error of about eps * max|x|, which moves xi by that
-// much times |J^{-1}|.  On a small or far-translated element this exceeds the fixed tolerances above, so both the
-// Newton stopping test and the containment test use max(fixed tolerance, ROUND_FACTOR * eps * max|x| * |J^{-1}|_inf).
-constexpr double ROUND_FACTOR = 64.0;
-constexpr double EPS = 2.220446049250313e-16;
-constexpr double QK_BOX_PAD = 0.125;       // a curved Q_k image can leave its nodes' box: pad by 1/8 of the extent
-
-__device__ inline double dnan() { return __builtin_nan(""); }
-
-// cell index of a scaled coordinate u = (v - lo) * inv; the caller has checked that v is finite and in the grid box
-__device__ inline int32_t cell_axis(double u, int32_t n) {
-    if (!(u >= 0.0)) return 0;
-    if (u >= (double)n) return n - 1;
-    const int32_t c = (int32_t)u;
-    return c < n - 1 ? c : n - 1;
-}
-
-struct Grid {
-    double lo[3], hi[3], inv[3];
-    int32_t n[3];
-    int64_t ncell;
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // location grid (2-D and 3-D FEM)
@@ -166,216 +139,9 @@ __global__ void cell_starts(int64_t P, int64_t ncell, const uint32_t* __restrict
     for (int64_t c = a + 1; c <= b; ++c) start[c] = (int32_t)i;
 }
 
-// cell of a point, or -1 if it is not finite or outside the grid box
-template <int D>
-__device__ inline int64_t point_cell(const Grid& g, const double* q) {
-    for (int a = 0; a < D; ++a)
-        if (!(q[a] >= g.lo[a] && q[a] <= g.hi[a])) return -1;     // also false for NaN; +-Inf is outside the box
-    int64_t c = 0;
-    for (int a = D - 1; a >= 0; --a) c = c * g.n[a] + cell_axis((q[a] - g.lo[a]) * g.inv[a], g.n[a]);
-    return c;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// element maps
-// ---------------------------------------------------------------------------------------------------------------
-
-// 1-D Lagrange basis on S nodes, in the reference's operation order (src/TensorFEM.jl:162-176)
-template <int S>
-__device__ inline void lagrange(const double* nodes, double xv, double* L) {
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-        double num = 1.0, den = 1.0;
-#pragma unroll
-        for (int j = 0; j < S; ++j)
-            if (i != j) {
-                num *= xv - nodes[j];
-                den *= nodes[i] - nodes[j];
-            }
-        L[i] = num / den;
-    }
-}
-
-template <int S>
-__device__ inline void lagrange_d(const double* nodes, double xv, double* L, double* dL) {
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-        double num = 1.0, den = 1.0, dnum = 0.0;
-#pragma unroll
-        for (int j = 0; j < S; ++j)
-            if (i != j) {
-                dnum = dnum * (xv - nodes[j]) + num;      // product rule, one factor at a time
-                num *= xv - nodes[j];
-                den *= nodes[i] - nodes[j];
-            }
-        L[i] = num / den;
-        dL[i] = dnum / den;
-    }
-}
-
-// L[j] of a runtime index j < S without indexing a register array at run time (which would put it in scratch)
-template <int S>
-__device__ inline double pick(const double (&L)[S], int j) {
-    double v = 0.0;
-#pragma unroll
-    for (int i = 0; i < S; ++i)
-        if (i == j) v = L[i];
-    return v;
-}
-
-// inverse Jacobian (adjugate / det); false if the determinant is zero or not finite
-template <int D>
-__device__ inline bool jac_inverse(const double (&J)[D][D], double (&Ji)[D][D]) {
-    if constexpr (D == 2) {
-        const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        if (!(det != 0.0) || !isfinite(det)) return false;
-        Ji[0][0] = J[1][1] / det;
-        Ji[0][1] = -J[0][1] / det;
-        Ji[1][0] = -J[1][0] / det;
-        Ji[1][1] = J[0][0] / det;
-    } else {
-        const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-        const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-        const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-        if (!(det != 0.0) || !isfinite(det)) return false;
-        Ji[0][0] = c00 / det;
-        Ji[1][0] = c01 / det;
-        Ji[2][0] = c02 / det;
-        Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-        Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
-        Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-        Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
-        Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-        Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / det;
-    }
-    return true;
-}
-
-// Q_k element e: Newton on sum_i phi_i(xi) x_i = q from xi = 0; returns true (and the basis factors at xi) when it
-// converges to a point of [-1, 1]^D within the containment tolerance; xi is that point.  Node lin = i0 + S i1 (+ S^2 i2),
-// axis 0 fastest; axis 0 is unrolled, the outer axes are loops that pick their basis factor without run-time register
-// indexing.
-template <int D, int S>
-__device__ bool qk_locate(const double* __restrict__ x, int64_t e, const double* nodes, const double* q,
-                          double (&L)[D][S], double (&xi)[D]) {
-    constexpr int P = D == 2 ? S * S : S * S * S;
-    double dL[D][S];
-    for (int a = 0; a < D; ++a) xi[a] = 0.0;
-    const double* xe = x + e * P * D;
-    bool conv = false;
-    double xs = 0.0, tol = NEWTON_STEP_TOL;
-    for (int a = 0; a < D; ++a) xs = fmax(xs, fabs(q[a]));
-    for (int it = 0; it < NEWTON_MAXIT && !conv; ++it) {
-#pragma unroll
-        for (int a = 0; a < D; ++a) lagrange_d<S>(nodes, xi[a], L[a], dL[a]);
-        double F[D], J[D][D];
-        for (int a = 0; a < D; ++a) {
-            F[a] = -q[a];
-            for (int b = 0; b < D; ++b) J[a][b] = 0.0;
-        }
-        const int n2 = D == 3 ? S : 1;
-#pragma unroll 1
-        for (int i2 = 0; i2 < n2; ++i2) {
-            double l2 = 1.0, d2 = 0.0;
-            if constexpr (D == 3) {
-                l2 = pick<S>(L[D - 1], i2);
-                d2 = pick<S>(dL[D - 1], i2);
-            }
-#pragma unroll 1
-            for (int i1 = 0; i1 < S; ++i1) {
-                const double l1 = pick<S>(L[1], i1), d1 = pick<S>(dL[1], i1);
-#pragma unroll
-                for (int i0 = 0; i0 < S; ++i0) {
-                    const int lin = i0 + S * i1 + S * S * i2;
-                    double phi, dphi[D];
-                    if constexpr (D == 2) {
-                        phi = L[0][i0] * l1;
-                        dphi[0] = dL[0][i0] * l1;
-                        dphi[1] = L[0][i0] * d1;
-                    } else {
-                        phi = L[0][i0] * l1 * l2;
-                        dphi[0] = dL[0][i0] * l1 * l2;
-                        dphi[1] = L[0][i0] * d1 * l2;
-                        dphi[D - 1] = L[0][i0] * l1 * d2;
-                    }
-                    for (int a = 0; a < D; ++a) {
-                        const double xa = xe[lin * D + a];
-                        if (it == 0) xs = fmax(xs, fabs(xa));
-                        F[a] += phi * xa;
-                        for (int b = 0; b < D; ++b) J[a][b] += dphi[b] * xa;
-                    }
-                }
-            }
-        }
-        double Ji[D][D];
-        if (!jac_inverse<D>(J, Ji)) return false;
-        double step = 0.0, big = 0.0, ninv = 0.0;
-        for (int a = 0; a < D; ++a) {
-            double dx = 0.0, row = 0.0;
-            for (int b = 0; b < D; ++b) {
-                dx += Ji[a][b] * F[b];
-                row += fabs(Ji[a][b]);
-            }
-            xi[a] -= dx;
-            step = fmax(step, fabs(dx));
-            big = fmax(big, fabs(xi[a]));
-            ninv = fmax(ninv, row);
-        }
-        if (!(big <= 8.0)) return false;         // diverging (or NaN): not this element
-        tol = fmax(NEWTON_STEP_TOL, ROUND_FACTOR * EPS * xs * ninv);
-        conv = step <= tol;
-    }
-    if (!conv) return false;
-    const double acc = fmax(ACCEPT_TOL, tol);
-    for (int a = 0; a < D; ++a)
-        if (!(fabs(xi[a]) <= 1.0 + acc)) return false;
-#pragma unroll
-    for (int a = 0; a < D; ++a) lagrange<S>(nodes, xi[a], L[a]);
-    return true;
-}
-
-// P1 / P2: (l1, l2) with q = l1 c0 + l2 c1 + (1 - l1 - l2) c2 from the three corner slots
-template <int FAM>
-__device__ inline bool simplex_locate(const double* __restrict__ x, int64_t e, int32_t p, const double* q, double& l1,
-                                      double& l2) {
-    constexpr int s0 = 0, s1 = FAM == MGBHIP_INTERP_P1 ? 1 : 2, s2 = FAM == MGBHIP_INTERP_P1 ? 2 : 4;
-    const double* xe = x + e * p * 2;
-    const double ox = xe[2 * s2], oy = xe[2 * s2 + 1];
-    const double ax = xe[2 * s0] - ox, ay = xe[2 * s0 + 1] - oy;
-    const double bx = xe[2 * s1] - ox, by = xe[2 * s1 + 1] - oy;
-    const double rx = q[0] - ox, ry = q[1] - oy;
-    const double det = ax * by - ay * bx;
-    if (!(det != 0.0)) return false;
-    l1 = (rx * by - ry * bx) / det;
-    l2 = (ax * ry - ay * rx) / det;
-    // the differences above carry an error of about eps * max|x|, which the inverse map scales by |J^{-1}|_inf
-    const double xs = fmax(fmax(fmax(fabs(ox), fabs(oy)), fmax(fabs(q[0]), fabs(q[1]))),
-                           fmax(fmax(fabs(xe[2 * s0]), fabs(xe[2 * s0 + 1])), fmax(fabs(xe[2 * s1]), fabs(xe[2 * s1 + 1]))));
-    const double ninv = fmax(fabs(by) + fabs(bx), fabs(ay) + fabs(ax)) / fabs(det);
-    const double tol = fmax(ACCEPT_TOL, ROUND_FACTOR * EPS * xs * ninv);
-    return l1 >= -tol && l2 >= -tol && 1.0 - l1 - l2 >= -tol;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // query, locate and evaluate kernels: one lane per point
 // ---------------------------------------------------------------------------------------------------------------
-
-struct QueryArgs {
-    int64_t M;
-    int32_t p, ncomp;
-    const double* x;
-    const double* table;
-    const double* z;
-    const double* pts;
-    const int32_t* start;
-    const int32_t* cand;
-    const double* box;         // 2-D / 3-D FEM: the padded element boxes (lo then hi per element)
-    const int32_t* order;      // located families: the point processed by lane i (points sorted by cell)
-    double* out;
-    double* grad;              // M x ncomp x D (GRAD kernels only)
-    int32_t* elem;
-};
 
 // What a locate kernel leaves behind for the evaluate kernels of a point locator, per lane i (the stored cell order of
 // the located families, the point index otherwise): the element (-1: none) and the reference coordinates the fused
@@ -399,117 +165,6 @@ __device__ inline void write_nan(const QueryArgs& a, int64_t q) {
     if constexpr (GRAD)
         for (int c = 0; c < a.ncomp * D; ++c) a.grad[q * a.ncomp * D + c] = dnan();
     if (a.elem) a.elem[q] = -1;
-}
-
-// Q_k locate: the lowest-index candidate of the point's cell whose element map inverts to a point of the reference
-// cube; on success L holds the basis factors at xi (as qk_locate leaves them) and nodes the reference nodes of the
-// table.  -1: no element.
-template <int D, int S>
-__device__ inline int64_t qk_find(const QueryArgs& a, const Grid& g, const double (&pt)[D], double (&nodes)[S],
-                                  double (&L)[D][S], double (&xi)[D]) {
-    const int64_t cell = point_cell<D>(g, pt);
-    if (cell < 0) return -1;
-    for (int j = 0; j < S; ++j) nodes[j] = a.table[j];
-    const int32_t j1 = a.start[cell + 1];
-    for (int32_t j = a.start[cell]; j < j1; ++j) {
-        const int64_t e = a.cand[j];
-        bool inbox = true;             // a point outside the element's padded box is not in the element: skip Newton
-        for (int d = 0; d < D; ++d)
-            inbox = inbox && pt[d] >= a.box[e * 2 * D + d] && pt[d] <= a.box[e * 2 * D + D + d];
-        if (inbox && qk_locate<D, S>(a.x, e, nodes, pt, L, xi)) return e;
-    }
-    return -1;
-}
-
-// Q_k evaluate at xi of element `found`; L holds lagrange<S>(nodes, xi[d]) on entry.  False (nothing written) when the
-// Jacobian at xi cannot be inverted (GRAD only).
-// GRAD: the Jacobian J[a][b] = sum_i dphi_i/dxi_b x_i[a] at the located xi in one pass over the element's nodes,
-// then per component gxi[b] = sum_i dphi_i/dxi_b z_i next to the value sum and grad = J^{-T} gxi.  The live state
-// is that of a Newton step (L, dL, a D x D matrix, D sums), so no variant needs more registers than qk_locate.
-template <int D, int S, bool GRAD>
-__device__ inline bool qk_evaluate(const QueryArgs& a, int64_t q, int64_t found, const double (&nodes)[S],
-                                   double (&L)[D][S], const double (&xi)[D]) {
-    constexpr int P = D == 2 ? S * S : S * S * S;
-    const int n2 = D == 3 ? S : 1;
-    double dL[GRAD ? D : 1][S], Ji[D][D];
-    if constexpr (GRAD) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) lagrange_d<S>(nodes, xi[d], L[d], dL[d]);
-        double J[D][D];
-        for (int r = 0; r < D; ++r)
-            for (int b = 0; b < D; ++b) J[r][b] = 0.0;
-        const double* xe = a.x + found * P * D;
-#pragma unroll 1
-        for (int i2 = 0; i2 < n2; ++i2) {
-            double l2 = 1.0, d2 = 0.0;
-            if constexpr (D == 3) {
-                l2 = pick<S>(L[D - 1], i2);
-                d2 = pick<S>(dL[D - 1], i2);
-            }
-#pragma unroll 1
-            for (int i1 = 0; i1 < S; ++i1) {
-                const double l1 = pick<S>(L[1], i1), d1 = pick<S>(dL[1], i1);
-#pragma unroll
-                for (int i0 = 0; i0 < S; ++i0) {
-                    const int lin = i0 + S * i1 + S * S * i2;
-                    double dphi[D];
-                    if constexpr (D == 2) {
-                        dphi[0] = dL[0][i0] * l1;
-                        dphi[1] = L[0][i0] * d1;
-                    } else {
-                        dphi[0] = dL[0][i0] * l1 * l2;
-                        dphi[1] = L[0][i0] * d1 * l2;
-                        dphi[D - 1] = L[0][i0] * l1 * d2;
-                    }
-                    for (int r = 0; r < D; ++r)
-                        for (int b = 0; b < D; ++b) J[r][b] += dphi[b] * xe[lin * D + r];
-                }
-            }
-        }
-        if (!jac_inverse<D>(J, Ji)) return false;
-    }
-    const double* ze = a.z + found * P * a.ncomp;
-    for (int c = 0; c < a.ncomp; ++c) {
-        double v = 0.0, gxi[D];
-        for (int b = 0; b < D; ++b) gxi[b] = 0.0;
-#pragma unroll 1
-        for (int i2 = 0; i2 < n2; ++i2) {
-            const double l2 = D == 3 ? pick<S>(L[D - 1], i2) : 1.0;
-            double d2 = 0.0;
-            if constexpr (GRAD && D == 3) d2 = pick<S>(dL[D - 1], i2);
-#pragma unroll 1
-            for (int i1 = 0; i1 < S; ++i1) {
-                const double l1 = pick<S>(L[1], i1);
-                double d1 = 0.0;
-                if constexpr (GRAD) d1 = pick<S>(dL[1], i1);
-#pragma unroll
-                for (int i0 = 0; i0 < S; ++i0) {
-                    const int lin = i0 + S * i1 + S * S * i2;
-                    const double phi = D == 2 ? L[0][i0] * l1 : L[0][i0] * l1 * l2;
-                    const double zv = ze[lin * a.ncomp + c];
-                    v += phi * zv;
-                    if constexpr (GRAD) {
-                        if constexpr (D == 2) {
-                            gxi[0] += dL[0][i0] * l1 * zv;
-                            gxi[1] += L[0][i0] * d1 * zv;
-                        } else {
-                            gxi[0] += dL[0][i0] * l1 * l2 * zv;
-                            gxi[1] += L[0][i0] * d1 * l2 * zv;
-                            gxi[D - 1] += L[0][i0] * l1 * d2 * zv;
-                        }
-                    }
-                }
-            }
-        }
-        a.out[q * a.ncomp + c] = v;
-        if constexpr (GRAD)
-            for (int r = 0; r < D; ++r) {
-                double s = 0.0;
-                for (int b = 0; b < D; ++b) s += Ji[b][r] * gxi[b];
-                a.grad[(q * a.ncomp + c) * D + r] = s;
-            }
-    }
-    return true;
 }
 
 template <int D, int S, bool GRAD>
@@ -553,73 +208,6 @@ __global__ void __launch_bounds__(BLOCK) eval_qk(QueryArgs a, LocArgs l) {
 #pragma unroll
     for (int d = 0; d < D; ++d) lagrange<S>(nodes, xi[d], L[d]);
     if (!qk_evaluate<D, S, GRAD>(a, q, found, nodes, L, xi)) write_nan<D, GRAD>(a, q);
-}
-
-// P1 / P2 locate: the lowest-index candidate of the point's cell that contains it, with its barycentric pair
-template <int FAM>
-__device__ inline int64_t simplex_find(const QueryArgs& a, const Grid& g, const double (&pt)[2], double& l1, double& l2) {
-    const int64_t cell = point_cell<2>(g, pt);
-    if (cell < 0) return -1;
-    const int32_t j1 = a.start[cell + 1];
-    for (int32_t j = a.start[cell]; j < j1; ++j) {
-        const int64_t e = a.cand[j];
-        if (simplex_locate<FAM>(a.x, e, a.p, pt, l1, l2)) return e;
-    }
-    return -1;
-}
-
-template <int FAM, bool GRAD>
-__device__ inline void simplex_evaluate(const QueryArgs& a, int64_t q, int64_t found, double l1, double l2) {
-    const double mono[10] = {1.0, l1, l2, l1 * l1, l1 * l2, l2 * l2, l1 * l1 * l1, l1 * l1 * l2, l1 * l2 * l2, l2 * l2 * l2};
-    constexpr int PMAX = 7;
-    double phi[PMAX];
-    for (int j = 0; j < PMAX; ++j) {
-        double v = 0.0;
-        if (j < a.p)
-            for (int m = 0; m < 10; ++m) v += a.table[j * 10 + m] * mono[m];
-        phi[j] = v;
-    }
-    const double* ze = a.z + found * a.p * a.ncomp;
-    for (int c = 0; c < a.ncomp; ++c) {
-        double v = 0.0;
-        for (int j = 0; j < PMAX; ++j)
-            if (j < a.p) v += phi[j] * ze[j * a.ncomp + c];
-        a.out[q * a.ncomp + c] = v;
-    }
-    if constexpr (GRAD) {
-        // the ten monomials differentiated in l1 and l2; x = c2 + l1 (c0 - c2) + l2 (c1 - c2), so with the edge vectors
-        // ea, eb of simplex_locate the gradient is [ea eb]^{-T} (du/dl1, du/dl2)
-        const double m1[10] = {0.0, 1.0, 0.0, 2 * l1, l2, 0.0, 3 * (l1 * l1), 2 * (l1 * l2), l2 * l2, 0.0};
-        const double m2[10] = {0.0, 0.0, 1.0, 0.0, l1, 2 * l2, 0.0, l1 * l1, 2 * (l1 * l2), 3 * (l2 * l2)};
-        double p1[PMAX], p2[PMAX];
-        for (int j = 0; j < PMAX; ++j) {
-            double v1 = 0.0, v2 = 0.0;
-            if (j < a.p)
-                for (int m = 1; m < 10; ++m) {
-                    v1 += a.table[j * 10 + m] * m1[m];
-                    v2 += a.table[j * 10 + m] * m2[m];
-                }
-            p1[j] = v1;
-            p2[j] = v2;
-        }
-        constexpr int s0 = 0, s1 = FAM == MGBHIP_INTERP_P1 ? 1 : 2, s2 = FAM == MGBHIP_INTERP_P1 ? 2 : 4;
-        const double* xe = a.x + found * a.p * 2;
-        const double ox = xe[2 * s2], oy = xe[2 * s2 + 1];
-        const double ax = xe[2 * s0] - ox, ay = xe[2 * s0 + 1] - oy;
-        const double bx = xe[2 * s1] - ox, by = xe[2 * s1 + 1] - oy;
-        const double det = ax * by - ay * bx;
-        for (int c = 0; c < a.ncomp; ++c) {
-            double g1 = 0.0, g2 = 0.0;
-            for (int j = 0; j < PMAX; ++j)
-                if (j < a.p) {
-                    const double zv = ze[j * a.ncomp + c];
-                    g1 += p1[j] * zv;
-                    g2 += p2[j] * zv;
-                }
-            a.grad[(q * a.ncomp + c) * 2] = (by * g1 - ay * g2) / det;
-            a.grad[(q * a.ncomp + c) * 2 + 1] = (ax * g2 - bx * g1) / det;
-        }
-    }
 }
 
 template <int FAM, bool GRAD>
@@ -1126,6 +714,13 @@ void run_located(const InterpIn& in, Pass pass, QueryArgs a, const LocArgs& l, c
 }
 
 }  // namespace
+
+void location_grid_build(LocationGrid& G, const InterpIn& in, const double* d_x, hipStream_t st) {
+    MGB_REQUIRE(in.d == 2 || in.d == 3, "interpolate: a location grid needs d = 2 or 3");
+    if (in.d == 2) build_grid<2>(in, d_x, st, G.g, G.start, G.cand, G.box);
+    else build_grid<3>(in, d_x, st, G.g, G.start, G.cand, G.box);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
 
 void interpolate_run(const InterpIn& in, hipStream_t st) {
     if (in.M == 0) return;

@@ -24,6 +24,25 @@ struct InterpIn {
     int32_t* elem = nullptr;      // host M, or NULL
 };
 
+// the uniform grid of cells over the union of the padded element boxes (2-D and 3-D FEM): kernels take it by value
+struct Grid {
+    double lo[3], hi[3], inv[3];
+    int32_t n[3];
+    int64_t ncell;
+};
+
+// A location grid that stays resident: the cells, per cell its candidate elements in ascending element order (cell c
+// owns cand[start[c] .. start[c+1]-1]) and the padded element boxes (lo then hi per element).  interpolate_run and
+// locator_build free theirs once the points are located; a field-line tracer (stream.hpp) keeps one for its lifetime.
+struct LocationGrid {
+    Grid g{};
+    DevBuf<int32_t> start, cand;
+    DevBuf<double> box;
+};
+
+// in: family, d (2 or 3), k, p, N; d_x the node coordinates on the device ((p*N) x d); complete on return
+void location_grid_build(LocationGrid& G, const InterpIn& in, const double* d_x, hipStream_t st);
+
 // one launch sequence on st; complete (results on the host) on return
 void interpolate_run(const InterpIn& in, hipStream_t st);
 

@@ -121,6 +121,7 @@ EXPORTS = [
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
     "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy", "mgbhip_raycast_render_layers",
     "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
+    "mgbhip_stream_create", "mgbhip_stream_set_field", "mgbhip_stream_trace", "mgbhip_stream_destroy",
 ]
 
 
@@ -222,6 +223,11 @@ def load_library():
     lib.mgbhip_surface_shade.argtypes = [vp, C.c_int64, C.c_int32, _dp, _ip, _dp, _dp, _dp, C.c_int32, _dp, C.c_double,
                                          C.c_double, C.c_double, _dp]
     lib.mgbhip_surface_destroy.argtypes = [vp]
+    lib.mgbhip_stream_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp,
+                                         C.POINTER(vp)]
+    lib.mgbhip_stream_set_field.argtypes = [vp, _dp]
+    lib.mgbhip_stream_trace.argtypes = [vp, C.c_int64, _dp, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp, _ip, _ip]
+    lib.mgbhip_stream_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 

@@ -21,7 +21,7 @@ from .interpolate import P1, P2, QK, _c_f64, _columns, _plan
 from .multigrid import Geometry
 from .tensorfem import TensorFEM
 
-QK_BOX_PAD = 0.125      # csrc/interpolate.hip QK_BOX_PAD: a curved Q_k image can leave its nodes' box
+QK_BOX_PAD = 0.125      # csrc/interp_device.hpp QK_BOX_PAD: a curved Q_k image can leave its nodes' box
 
 
 def _raycast_plan(geom: Geometry, who: str = "RayCaster"):
