@@ -372,9 +372,9 @@ int mgbhip_locator_destroy(mgbhip_locator* loc); /* NULL is a no-op */
  * Order of the simplices: element, lattice cell, simplex of the cell, level index, triangle of a 2-2 split of a
  * tetrahedron.  It is produced by a count pass, an exclusive scan and an emit pass, without atomics: two calls return
  * bitwise equal arrays.  create leaves the result on the device and reports S; fetch copies it out: points S x d x d
- * [simplex, vertex, coordinate], level S [index into levels], element S, carried S x d x (nfield - 1) or NULL.  The
- * handle belongs to the context it was created from and must be destroyed before it.  Host pointers; the work runs
- * on ctx's stream and is complete on return.                                                                       */
+ * [simplex, vertex, coordinate; S x d x e after mgbhip_contour_create_embedded], level S [index into levels],
+ * element S, carried S x d x (nfield - 1) or NULL.  The handle belongs to the context it was created from and must be
+ * destroyed before it.  Host pointers; the work runs on ctx's stream and is complete on return.                     */
 typedef struct mgbhip_contour mgbhip_contour;
 int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
                           const double* x, const double* table, int32_t nfield /* 1 + ncarry */, const double* fields,
@@ -383,6 +383,46 @@ int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
 int mgbhip_contour_fetch(const mgbhip_contour* c, double* points, int32_t* level, int32_t* element,
                          double* carried /* or NULL */);
 int mgbhip_contour_destroy(mgbhip_contour* c); /* NULL is a no-op */
+
+/* ---- level curves on a surface: the same cut for a Q_k 2-D mesh embedded in R^3 ------------------------------------
+ * mgbhip_contour_create_embedded is mgbhip_contour_create with the ambient dimension e of the node coordinates given:
+ * x is (p*N) x e.  It accepts what mgbhip_contour_create accepts, with e == d, and family = QK, d = 2, e = 3 [a surface:
+ * the elements are the images of the reference square in R^3].  mgbhip_contour_create is this entry with e = d.  The
+ * lattice, the triangles, the classification and the one t = (c - v_a) / (v_b - v_a) of a crossing are those of the
+ * block above; the lattice carries e position coordinates, each its own sum of p products in ascending node order, and
+ * a crossing is x[c] = x_a[c] + t (x_b[c] - x_a[c]) per coordinate.  So a surface whose third coordinate is 0.0
+ * everywhere returns in the first two coordinates the bits of the d = e = 2 call, and 0.0 in the third.
+ * mgbhip_contour_fetch writes points as S x d x e [simplex, vertex, coordinate]; order, level, element and carried are
+ * unchanged.                                                                                                         */
+int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p,
+                                   int64_t N, const double* x /* (p*N) x e */, const double* table,
+                                   int32_t nfield /* 1 + ncarry */, const double* fields, int32_t nlevels,
+                                   const double* levels, int32_t refine, mgbhip_contour** out, int64_t* nsimplices);
+
+/* ---- tessellation: the lattice triangles of a 2-D mesh, flat or a surface in R^3 -----------------------------------
+ * Every element is sampled on the lattice of the level-set block above [the same device code: positions and fields are
+ * the sums the contour kernel forms] and every lattice triangle is emitted instead of its cuts: per lattice square the
+ * triangles ([i, j], [i+1, j], [i+1, j+1]) and ([i, j], [i, j+1], [i+1, j+1]), i fastest [Q_k: 2 refine^2 per element];
+ * per row j and cell i of the barycentric lattice the upright triangle ([i, j], [i+1, j], [i, j+1]) and then, unless
+ * the cell is the last of its row, the inverted one ([i+1, j], [i, j+1], [i+1, j+1]) [P1 / P2: refine^2 per element].
+ * The vertices of a triangle are in ascending lattice index.  Triangle i of element n is triangle n * ntri + i of the
+ * result: T = N * ntri is known from N and refine, there is no count pass, no scan and there are no atomics; two calls
+ * return bitwise equal arrays.
+ *  - family, d, k, p, N, table are those of the interpolate entry point above; only QK [d = 2; e = 2 or 3], P1 and P2
+ *    [d = e = 2, straight elements] are accepted.  x is (p*N) x e.
+ *  - fields is (p*N) x nfield row-major, 0 <= nfield <= 5 [NULL when nfield = 0]: every column is interpolated to every
+ *    lattice point like the position.
+ *  - refine: 1..16.  T x 3 > 2^31 - 1 vertices is MGBHIP_ERR_INVALID before anything is allocated.
+ * create leaves the result on the device and reports T; fetch copies it out: points T x 3 x e [triangle, vertex,
+ * coordinate], element T, values T x 3 x nfield or NULL.  The handle belongs to the context it was created from and
+ * must be destroyed before it.  Host pointers; the work runs on ctx's stream and is complete on return.            */
+typedef struct mgbhip_tessellation mgbhip_tessellation;
+int mgbhip_tessellate_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
+                             const double* x /* (p*N) x e */, const double* table, int32_t nfield /* 0..5 */,
+                             const double* fields, int32_t refine, mgbhip_tessellation** out, int64_t* ntriangles);
+int mgbhip_tessellate_fetch(const mgbhip_tessellation* t, double* points, int32_t* element,
+                            double* values /* or NULL */);
+int mgbhip_tessellate_destroy(mgbhip_tessellation* t); /* NULL is a no-op */
 
 /* ---- ray casting: line integrals and volume rendering of an element-space function --------------------------------
  * R rays x = origin + t dir [R x d each, row-major; dir of unit length, so t is arc length] are clipped to

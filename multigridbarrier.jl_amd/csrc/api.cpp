@@ -61,6 +61,13 @@ struct mgbhip_contour {
 };
 static int dev_of(const mgbhip_contour* c) { return (c && c->ctx) ? c->ctx->device : -1; }
 
+// the lattice triangles of a 2-D mesh (contour.hpp) and the context they live in
+struct mgbhip_tessellation {
+    mgbhip_ctx* ctx = nullptr;
+    Tessellation tes;
+};
+static int dev_of(const mgbhip_tessellation* t) { return (t && t->ctx) ? t->ctx->device : -1; }
+
 // a ray caster (raycast.hpp) and the context it lives in
 struct mgbhip_raycast {
     mgbhip_ctx* ctx = nullptr;
@@ -854,9 +861,10 @@ int mgbhip_locator_destroy(mgbhip_locator* loc) {
     MGB_API_END
 }
 
-int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
-                          const double* table, int32_t nfield, const double* fields, int32_t nlevels,
-                          const double* levels, int32_t refine, mgbhip_contour** out, int64_t* nsimplices) {
+int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
+                                   const double* x, const double* table, int32_t nfield, const double* fields,
+                                   int32_t nlevels, const double* levels, int32_t refine, mgbhip_contour** out,
+                                   int64_t* nsimplices) {
     MGB_API_BEGIN_ON(ctx)
     MGB_REQUIRE(ctx != nullptr, "null context");
     MGB_REQUIRE(out != nullptr && nsimplices != nullptr, "null output pointer");
@@ -869,11 +877,13 @@ int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
     InterpIn geo;
     geo.family = family; geo.d = d; geo.k = k; geo.p = p; geo.N = N; geo.x = x; geo.table = table;
     interpolate_check_geometry(geo);
+    MGB_REQUIRE(e == d || (family == MGBHIP_INTERP_QK && d == 2 && e == 3),
+                "contour_create_embedded: e must be d, or 3 for Q_k with d = 2 (a surface in R^3)");
     MGB_REQUIRE(refine >= 1 && refine <= (d == 3 ? CONTOUR_MAX_REFINE_3D : CONTOUR_MAX_REFINE_2D),
                 d == 3 ? "contour: refine must be 1..8 for d = 3" : "contour: refine must be 1..16 for d = 2");
     for (int32_t l = 0; l < nlevels; ++l) MGB_REQUIRE(std::isfinite(levels[l]), "contour: a level is not finite");
     ContourIn in;
-    in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.nfield = nfield; in.nlevels = nlevels;
+    in.family = family; in.d = d; in.e = e; in.k = k; in.p = p; in.N = N; in.nfield = nfield; in.nlevels = nlevels;
     in.refine = refine; in.x = x; in.table = table; in.fields = fields; in.levels = levels;
     std::unique_ptr<mgbhip_contour> c(new mgbhip_contour());
     c->ctx = ctx;
@@ -882,6 +892,13 @@ int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
     *out = c.release();
     return MGBHIP_OK;
     MGB_API_END
+}
+
+int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                          const double* table, int32_t nfield, const double* fields, int32_t nlevels,
+                          const double* levels, int32_t refine, mgbhip_contour** out, int64_t* nsimplices) {
+    return mgbhip_contour_create_embedded(ctx, family, d, d, k, p, N, x, table, nfield, fields, nlevels, levels, refine, out,
+                                          nsimplices);
 }
 
 int mgbhip_contour_fetch(const mgbhip_contour* c, double* points, int32_t* level, int32_t* element, double* carried) {
@@ -898,6 +915,59 @@ int mgbhip_contour_destroy(mgbhip_contour* c) {
     if (!c) return MGBHIP_OK;
     (void)hipStreamSynchronize(c->ctx->stream);
     delete c;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tessellate_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
+                             const double* x, const double* table, int32_t nfield, const double* fields, int32_t refine,
+                             mgbhip_tessellation** out, int64_t* ntriangles) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr && ntriangles != nullptr, "null output pointer");
+    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
+                "tessellate: only the Q_k (d = 2), P1 and P2 families are tessellated");
+    MGB_REQUIRE(d == 2, "tessellate: d must be 2 (the lattice triangles of 2-D elements)");
+    MGB_REQUIRE(N > 0, "tessellate: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1, "tessellate: bad sizes");
+    MGB_REQUIRE(nfield >= 0 && nfield <= CONTOUR_MAX_FIELDS, "tessellate: nfield must be 0..5");
+    MGB_REQUIRE(nfield == 0 || fields != nullptr, "tessellate: null fields");
+    InterpIn geo;
+    geo.family = family; geo.d = d; geo.k = k; geo.p = p; geo.N = N; geo.x = x; geo.table = table;
+    interpolate_check_geometry(geo);
+    MGB_REQUIRE(e == 2 || (family == MGBHIP_INTERP_QK && e == 3),
+                "tessellate: e must be 2, or 3 for Q_k (a surface in R^3)");
+    MGB_REQUIRE(refine >= 1 && refine <= CONTOUR_MAX_REFINE_2D, "tessellate: refine must be 1..16");
+    ContourIn in;
+    in.family = family; in.d = d; in.e = e; in.k = k; in.p = p; in.N = N; in.nfield = nfield; in.refine = refine;
+    in.x = x; in.table = table; in.fields = fields;
+    const int64_t T = tessellate_count(in);      // N < 2^31 / p and refine <= 16: no overflow
+    if (T > (int64_t)INT32_MAX / 3)
+        throw InvalidArgument("tessellate: T = " + std::to_string(T) + " triangles have more than 2^31 - 1 vertices: use a "
+                              "smaller refine");
+    std::unique_ptr<mgbhip_tessellation> t(new mgbhip_tessellation());
+    t->ctx = ctx;
+    tessellate_build(t->tes, in, ctx->stream);
+    *ntriangles = t->tes.T;
+    *out = t.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tessellate_fetch(const mgbhip_tessellation* t, double* points, int32_t* element, double* values) {
+    MGB_API_BEGIN_ON(t)
+    MGB_REQUIRE(t != nullptr, "tessellate_fetch: null tessellation");
+    MGB_REQUIRE(points != nullptr && element != nullptr, "tessellate_fetch: null argument");
+    tessellate_fetch(t->tes, points, element, values, t->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tessellate_destroy(mgbhip_tessellation* t) {
+    MGB_API_BEGIN_ON(t)
+    if (!t) return MGBHIP_OK;
+    (void)hipStreamSynchronize(t->ctx->stream);
+    delete t;
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -15,6 +15,13 @@
 // forms the full lattice and writes the simplices.  Inside an element every thread owns a contiguous run of simplices
 // and a block scan of the per-thread counts places the runs, so the output order (element, cell, simplex of the cell,
 // level, triangle of a 2-2 split) does not depend on the launch: there are no atomics.
+//
+// A Q_k 2-D mesh may sit in R^3 (a surface): the lattice then has E = 3 position slots, each coordinate the same sum as
+// the two of a flat mesh, and the level curves are segments in R^3.
+//
+// mgbhip_tessellate_* emits the lattice triangles themselves instead of their cuts (tessellate_kernel): the same lattice
+// (form_lattice is the one copy of the sampling), the same enumeration, triangle i of element e at e * ntri + i.  The
+// count is a function of N and refine alone, so there is no count pass, no scan and nothing to place.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,6 +41,8 @@ namespace {
 
 constexpr int MAX_BLOCK = 256;
 constexpr int KIND_Q2 = 0, KIND_Q3 = 1, KIND_TRI = 2;
+// what form_lattice samples: the contoured value alone; value, position, carried fields; position, fields
+constexpr int MODE_COUNT = 0, MODE_EMIT = 1, MODE_TESS = 2;
 
 struct ContourArgs {
     int64_t N, S;
@@ -49,6 +58,7 @@ struct ContourArgs {
     int32_t* level;
     int32_t* element;
     double* carried;
+    double* values;            // tessellation: T x 3 x nfield
 };
 
 // first lattice index of row j of the barycentric lattice of the r-fold subdivision (row j holds r + 1 - j points)
@@ -98,39 +108,32 @@ __device__ inline void simplex_vertices(int s, int r, int (&v)[KIND == KIND_Q3 ?
     }
 }
 
-// EMIT = false: a.count[e] = simplices of element e.  EMIT = true: the simplices of element e from a.off[e] on.
-// LDS: the lattice, slot-major (slot 0 the contoured value; EMIT: slots 1..D the position, slot D + c carried field c),
-// then the table.
-template <int KIND, bool EMIT>
-__global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
-    constexpr int D = KIND == KIND_Q3 ? 3 : 2;
-    constexpr int NSLOT = EMIT ? 1 + D + (CONTOUR_MAX_FIELDS - 1) : 1;
-    extern __shared__ double lds[];
-    __shared__ int64_t sc[MAX_BLOCK];
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int64_t e = blockIdx.x;
+// The lattice of element e into LDS, slot-major, E position slots (E = 3 > D: a Q_k 2-D surface in R^3).
+// MODE_COUNT: slot 0, the contoured value.  MODE_EMIT: slot 0 the contoured value, slots 1..E the position, slot E + c
+// carried field c (field column c, c >= 1).  MODE_TESS: slots 0..E-1 the position, slot E + c field column c (c >= 0).
+// Every slot is its own sum of p products in ascending node order.  The caller synchronises before and after.
+template <int KIND, int E, int MODE>
+__device__ __forceinline__ void form_lattice(const ContourArgs& a, int64_t e, double* lat, const double* tab, int tid,
+                                             int nthr) {
+    constexpr int NSLOT = MODE == MODE_COUNT ? 1 : E + CONTOUR_MAX_FIELDS;
+    constexpr int P0 = MODE == MODE_EMIT ? 1 : 0;      // first position slot
+    constexpr int F0 = MODE == MODE_EMIT ? 1 : 0;      // first field column that goes to slot E + column
     const int npts = a.npts, r = a.r, nf = a.nfield;
-    const int nslot = EMIT ? D + nf : 1;
-    double* lat = lds;
-    double* tab = lds + (size_t)nslot * npts;
-    for (int i = tid; i < a.table_len; i += nthr) tab[i] = a.table[i];
-    __syncthreads();
-
-    // ---- the lattice of this element
+    const int nslot = MODE == MODE_COUNT ? 1 : E + nf;
     const double* fe = a.fields + e * a.p * nf;
-    const double* xe = a.x + e * a.p * D;
+    const double* xe = a.x + e * a.p * E;
     for (int pt = tid; pt < npts; pt += nthr) {
         double acc[NSLOT];
 #pragma unroll
         for (int f = 0; f < NSLOT; ++f) acc[f] = 0.0;
         auto add = [&](double phi, int node) {
-            acc[0] += phi * fe[node * nf];
-            if constexpr (EMIT) {
+            if constexpr (MODE != MODE_TESS) acc[0] += phi * fe[node * nf];
+            if constexpr (MODE != MODE_COUNT) {
 #pragma unroll
-                for (int c = 0; c < D; ++c) acc[1 + c] += phi * xe[node * D + c];
+                for (int c = 0; c < E; ++c) acc[P0 + c] += phi * xe[node * E + c];
 #pragma unroll
-                for (int c = 1; c < CONTOUR_MAX_FIELDS; ++c)
-                    if (c < nf) acc[D + c] += phi * fe[node * nf + c];
+                for (int c = F0; c < CONTOUR_MAX_FIELDS; ++c)
+                    if (c < nf) acc[E + c] += phi * fe[node * nf + c];
             }
         };
         if constexpr (KIND == KIND_TRI) {
@@ -146,6 +149,7 @@ __global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
                 add(phi, node);
             }
         } else {
+            constexpr int D = KIND == KIND_Q3 ? 3 : 2;
             const int n1 = r + 1, S = a.k + 1;
             const double* b0 = tab + (pt % n1) * S;
             const double* b1 = tab + ((pt / n1) % n1) * S;
@@ -163,6 +167,27 @@ __global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
         for (int f = 0; f < NSLOT; ++f)
             if (f < nslot) lat[f * npts + pt] = acc[f];
     }
+}
+
+// EMIT = false: a.count[e] = simplices of element e.  EMIT = true: the simplices of element e from a.off[e] on.
+// LDS: the lattice of form_lattice (MODE_COUNT / MODE_EMIT), then the table.  E = D but for a Q_k 2-D surface (E = 3).
+template <int KIND, int E, bool EMIT>
+__global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
+    constexpr int D = KIND == KIND_Q3 ? 3 : 2;
+    constexpr int NSLOT = EMIT ? E + CONTOUR_MAX_FIELDS : 1;
+    extern __shared__ double lds[];
+    __shared__ int64_t sc[MAX_BLOCK];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int64_t e = blockIdx.x;
+    const int npts = a.npts, r = a.r, nf = a.nfield;
+    const int nslot = EMIT ? E + nf : 1;
+    double* lat = lds;
+    double* tab = lds + (size_t)nslot * npts;
+    for (int i = tid; i < a.table_len; i += nthr) tab[i] = a.table[i];
+    __syncthreads();
+
+    // ---- the lattice of this element
+    form_lattice<KIND, E, EMIT ? MODE_EMIT : MODE_COUNT>(a, e, lat, tab, tid, nthr);
     __syncthreads();
 
     // ---- the simplices of this thread: [s0, s1)
@@ -228,13 +253,13 @@ __global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
                                 if (f >= nslot) continue;
                                 const double fa = lat[f * npts + v[qa]], fb = lat[f * npts + v[qb]];
                                 const double w = fa + t * (fb - fa);
-                                if (f <= D) {
-                                    a.points[(t0 * D + c0) * D + (f - 1)] = w;
-                                    if (t1 >= 0) a.points[(t1 * D + c1) * D + (f - 1)] = w;
+                                if (f <= E) {
+                                    a.points[(t0 * D + c0) * E + (f - 1)] = w;
+                                    if (t1 >= 0) a.points[(t1 * D + c1) * E + (f - 1)] = w;
                                 } else {
                                     const int nc = nf - 1;
-                                    a.carried[(t0 * D + c0) * nc + (f - D - 1)] = w;
-                                    if (t1 >= 0) a.carried[(t1 * D + c1) * nc + (f - D - 1)] = w;
+                                    a.carried[(t0 * D + c0) * nc + (f - E - 1)] = w;
+                                    if (t1 >= 0) a.carried[(t1 * D + c1) * nc + (f - E - 1)] = w;
                                 }
                             }
                             ++n;
@@ -259,6 +284,36 @@ __global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
     }
 }
 
+// Every lattice triangle of element e: triangle s goes to e * a.nsimp + s, its vertices in ascending lattice index.
+// LDS: the lattice of form_lattice (MODE_TESS), then the table.  KIND_Q2 (E = 2 or 3) and KIND_TRI.
+template <int KIND, int E>
+__global__ void __launch_bounds__(MAX_BLOCK) tessellate_kernel(ContourArgs a) {
+    static_assert(KIND != KIND_Q3, "a tessellation is of 2-D elements");
+    extern __shared__ double lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int64_t e = blockIdx.x;
+    const int npts = a.npts, nf = a.nfield;
+    double* lat = lds;
+    double* tab = lds + (size_t)(E + nf) * npts;
+    for (int i = tid; i < a.table_len; i += nthr) tab[i] = a.table[i];
+    __syncthreads();
+    form_lattice<KIND, E, MODE_TESS>(a, e, lat, tab, tid, nthr);
+    __syncthreads();
+
+    for (int s = tid; s < a.nsimp; s += nthr) {
+        int v[3];
+        simplex_vertices<KIND>(s, a.r, v);
+        const int64_t t = e * a.nsimp + s;
+        a.element[t] = (int32_t)e;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+#pragma unroll
+            for (int c = 0; c < E; ++c) a.points[(t * 3 + q) * E + c] = lat[c * npts + v[q]];
+            for (int c = 0; c < nf; ++c) a.values[(t * 3 + q) * nf + c] = lat[(E + c) * npts + v[q]];
+        }
+    }
+}
+
 // 1-D Lagrange basis on S nodes at xv, in the operation order of interpolate.hip's `lagrange`
 void lagrange_host(int S, const double* nodes, double xv, double* L) {
     for (int i = 0; i < S; ++i) {
@@ -272,44 +327,62 @@ void lagrange_host(int S, const double* nodes, double xv, double* L) {
     }
 }
 
-template <int KIND>
+template <int KIND, int E>
 void launch(bool emit, unsigned block, size_t lds_bytes, const ContourArgs& a, hipStream_t st) {
     const dim3 gr((unsigned)a.N), bl(block);
-    if (emit) hipLaunchKernelGGL((contour_kernel<KIND, true>), gr, bl, lds_bytes, st, a);
-    else hipLaunchKernelGGL((contour_kernel<KIND, false>), gr, bl, lds_bytes, st, a);
+    if (emit) hipLaunchKernelGGL((contour_kernel<KIND, E, true>), gr, bl, lds_bytes, st, a);
+    else hipLaunchKernelGGL((contour_kernel<KIND, E, false>), gr, bl, lds_bytes, st, a);
     MGB_HIP_CHECK(hipGetLastError());
 }
 
-void launch_kind(int kind, bool emit, unsigned block, size_t lds_bytes, const ContourArgs& a, hipStream_t st) {
-    if (kind == KIND_Q2) launch<KIND_Q2>(emit, block, lds_bytes, a, st);
-    else if (kind == KIND_Q3) launch<KIND_Q3>(emit, block, lds_bytes, a, st);
-    else launch<KIND_TRI>(emit, block, lds_bytes, a, st);
+void launch_kind(int kind, int e, bool emit, unsigned block, size_t lds_bytes, const ContourArgs& a, hipStream_t st) {
+    if (kind == KIND_Q2 && e == 3) launch<KIND_Q2, 3>(emit, block, lds_bytes, a, st);
+    else if (kind == KIND_Q2) launch<KIND_Q2, 2>(emit, block, lds_bytes, a, st);
+    else if (kind == KIND_Q3) launch<KIND_Q3, 3>(emit, block, lds_bytes, a, st);
+    else launch<KIND_TRI, 2>(emit, block, lds_bytes, a, st);
+}
+
+template <int KIND, int E>
+void launch_tess(unsigned block, size_t lds_bytes, const ContourArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((tessellate_kernel<KIND, E>), dim3((unsigned)a.N), dim3(block), lds_bytes, st, a);
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
+// the table the kernels read: the Q_k basis depends only on (k, r), so it is tabulated on the host, once per call
+std::vector<double> lattice_table(const ContourIn& in) {
+    std::vector<double> table;
+    if (in.family == MGBHIP_INTERP_QK) {
+        const int S = in.k + 1, r = in.refine;
+        table.resize((size_t)(r + 1) * S);
+        for (int i = 0; i <= r; ++i) lagrange_host(S, in.table, -1.0 + (2.0 * i) / r, table.data() + (size_t)i * S);
+    } else {
+        table.assign(in.table, in.table + (size_t)in.p * 10);
+    }
+    return table;
+}
+
+// lattice points and lattice simplices of one element
+void lattice_sizes(int kind, int r, ContourArgs& a) {
+    a.npts = kind == KIND_TRI ? (r + 1) * (r + 2) / 2 : (kind == KIND_Q2 ? (r + 1) * (r + 1) : (r + 1) * (r + 1) * (r + 1));
+    a.nsimp = kind == KIND_TRI ? r * r : (kind == KIND_Q2 ? 2 * r * r : 6 * r * r * r);
 }
 
 }  // namespace
 
 void contour_build(Contour& C, const ContourIn& in, hipStream_t st) {
     C.d = in.d;
+    C.e = in.e;
     C.ncarry = in.nfield - 1;
     C.S = 0;
     if (in.nlevels == 0) return;
     const int64_t rows = (int64_t)in.p * in.N;
-    const int r = in.refine, d = in.d;
+    const int r = in.refine, d = in.d, e = in.e;
     const bool qk = in.family == MGBHIP_INTERP_QK;
     const int kind = qk ? (d == 3 ? KIND_Q3 : KIND_Q2) : KIND_TRI;
-
-    // the table the kernels read: the Q_k basis depends only on (k, r), so it is tabulated here, once per call
-    std::vector<double> table;
-    if (qk) {
-        const int S = in.k + 1;
-        table.resize((size_t)(r + 1) * S);
-        for (int i = 0; i <= r; ++i) lagrange_host(S, in.table, -1.0 + (2.0 * i) / r, table.data() + (size_t)i * S);
-    } else {
-        table.assign(in.table, in.table + (size_t)in.p * 10);
-    }
+    const std::vector<double> table = lattice_table(in);
 
     DevBuf<double> d_x, d_table, d_fields, d_levels;
-    d_x.upload(in.x, (size_t)rows * d, st);
+    d_x.upload(in.x, (size_t)rows * e, st);
     d_table.upload(table, st);
     d_fields.upload(in.fields, (size_t)rows * in.nfield, st);
     d_levels.upload(in.levels, (size_t)in.nlevels, st);
@@ -320,15 +393,14 @@ void contour_build(Contour& C, const ContourIn& in, hipStream_t st) {
     ContourArgs a{};
     a.N = in.N;
     a.p = in.p; a.k = in.k; a.r = r; a.nfield = in.nfield; a.nlevels = in.nlevels;
-    a.npts = kind == KIND_TRI ? (r + 1) * (r + 2) / 2 : (kind == KIND_Q2 ? (r + 1) * (r + 1) : (r + 1) * (r + 1) * (r + 1));
-    a.nsimp = kind == KIND_TRI ? r * r : (kind == KIND_Q2 ? 2 * r * r : 6 * r * r * r);
+    lattice_sizes(kind, r, a);
     a.table_len = (int32_t)table.size();
     // one wave for an element of few simplices, a workgroup of four otherwise
     const unsigned block = a.nsimp <= 128 ? 64 : MAX_BLOCK;
     a.chunk = (a.nsimp + (int)block - 1) / (int)block;
     a.x = d_x.p; a.table = d_table.p; a.fields = d_fields.p; a.levels = d_levels.p;
     a.count = count.p;
-    launch_kind(kind, false, block, ((size_t)a.npts + table.size()) * sizeof(double), a, st);
+    launch_kind(kind, e, false, block, ((size_t)a.npts + table.size()) * sizeof(double), a, st);
 
     size_t scan_bytes = 0;
     MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, count.p, off.p, (int64_t)0, (size_t)in.N,
@@ -345,14 +417,14 @@ void contour_build(Contour& C, const ContourIn& in, hipStream_t st) {
     MGB_REQUIRE(S >= 0 && S < (int64_t)INT32_MAX, "contour: the number of simplices exceeds 32-bit indexing");
     if (S == 0) return;
 
-    C.points.alloc((size_t)S * d * d);
+    C.points.alloc((size_t)S * d * e);
     C.level.alloc((size_t)S);
     C.element.alloc((size_t)S);
     if (C.ncarry) C.carried.alloc((size_t)S * d * C.ncarry);
     a.S = S;
     a.off = off.p;
     a.points = C.points.p; a.level = C.level.p; a.element = C.element.p; a.carried = C.carried.p;
-    launch_kind(kind, true, block, ((size_t)a.npts * (d + in.nfield) + table.size()) * sizeof(double), a, st);
+    launch_kind(kind, e, true, block, ((size_t)a.npts * (e + in.nfield) + table.size()) * sizeof(double), a, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     C.S = S;
     // the inputs and the scan buffers are freed at scope exit; hipFree waits for the work that uses them
@@ -360,10 +432,57 @@ void contour_build(Contour& C, const ContourIn& in, hipStream_t st) {
 
 void contour_fetch(const Contour& C, double* points, int32_t* level, int32_t* element, double* carried, hipStream_t st) {
     if (C.S == 0) return;
-    C.points.download(points, (size_t)C.S * C.d * C.d, st);
+    C.points.download(points, (size_t)C.S * C.d * C.e, st);
     C.level.download(level, (size_t)C.S, st);
     C.element.download(element, (size_t)C.S, st);
     if (carried && C.ncarry) C.carried.download(carried, (size_t)C.S * C.d * C.ncarry, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+int64_t tessellate_count(const ContourIn& in) {
+    const int64_t r = in.refine;
+    return in.N * (in.family == MGBHIP_INTERP_QK ? 2 * r * r : r * r);
+}
+
+void tessellate_build(Tessellation& T, const ContourIn& in, hipStream_t st) {
+    T.e = in.e;
+    T.nfield = in.nfield;
+    T.T = tessellate_count(in);
+    const int64_t rows = (int64_t)in.p * in.N;
+    const int r = in.refine, e = in.e;
+    const int kind = in.family == MGBHIP_INTERP_QK ? KIND_Q2 : KIND_TRI;
+    const std::vector<double> table = lattice_table(in);
+
+    DevBuf<double> d_x, d_table, d_fields;
+    d_x.upload(in.x, (size_t)rows * e, st);
+    d_table.upload(table, st);
+    if (in.nfield) d_fields.upload(in.fields, (size_t)rows * in.nfield, st);
+    T.points.alloc((size_t)T.T * 3 * e);
+    T.element.alloc((size_t)T.T);
+    if (in.nfield) T.values.alloc((size_t)T.T * 3 * in.nfield);
+
+    ContourArgs a{};
+    a.N = in.N;
+    a.p = in.p; a.k = in.k; a.r = r; a.nfield = in.nfield;
+    lattice_sizes(kind, r, a);
+    a.table_len = (int32_t)table.size();
+    a.x = d_x.p; a.table = d_table.p; a.fields = d_fields.p;
+    a.points = T.points.p; a.element = T.element.p; a.values = T.values.p;
+    // the launch shape of the contour kernels: one wave for an element of few triangles, a workgroup of four otherwise
+    const unsigned block = a.nsimp <= 128 ? 64 : MAX_BLOCK;
+    const size_t lds_bytes = ((size_t)a.npts * (e + in.nfield) + table.size()) * sizeof(double);
+    if (kind == KIND_Q2 && e == 3) launch_tess<KIND_Q2, 3>(block, lds_bytes, a, st);
+    else if (kind == KIND_Q2) launch_tess<KIND_Q2, 2>(block, lds_bytes, a, st);
+    else launch_tess<KIND_TRI, 2>(block, lds_bytes, a, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+    // the inputs are freed at scope exit; hipFree waits for the work that uses them
+}
+
+void tessellate_fetch(const Tessellation& T, double* points, int32_t* element, double* values, hipStream_t st) {
+    if (T.T == 0) return;
+    T.points.download(points, (size_t)T.T * 3 * T.e, st);
+    T.element.download(element, (size_t)T.T, st);
+    if (values && T.nfield) T.values.download(values, (size_t)T.T * 3 * T.nfield, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 

@@ -1,4 +1,5 @@
-// contour.hpp -- level sets of an element-space function behind mgbhip_contour_* (contour.hip).
+// contour.hpp -- level sets of an element-space function behind mgbhip_contour_*, and the lattice triangles themselves
+// behind mgbhip_tessellate_* (contour.hip).
 #pragma once
 #include <cstdint>
 
@@ -13,18 +14,20 @@ constexpr int CONTOUR_MAX_REFINE_3D = 8;   // lattice of at most 9 x 9 x 9 point
 
 struct ContourIn {
     int32_t family = 0, d = 0, k = 0, p = 0, nfield = 0, nlevels = 0, refine = 0;
+    int32_t e = 0;                   // ambient dimension: d, or 3 for a Q_k 2-D surface in R^3
     int64_t N = 0;
-    const double* x = nullptr;       // host (p*N) x d
+    const double* x = nullptr;       // host (p*N) x e
     const double* table = nullptr;   // host: Q_k: the k + 1 reference nodes; P1 / P2: p x 10 monomial coefficients
     const double* fields = nullptr;  // host (p*N) x nfield; column 0 is contoured, the others are carried
+                                     // (a tessellation: 0..CONTOUR_MAX_FIELDS columns, all alike; levels are unused)
     const double* levels = nullptr;  // host nlevels, finite
 };
 
 // The simplex soup of one call, resident on the device until it is fetched or destroyed.
 struct Contour {
-    int32_t d = 0, ncarry = 0;
+    int32_t d = 0, e = 0, ncarry = 0;
     int64_t S = 0;
-    DevBuf<double> points, carried;  // S x d x d, S x d x ncarry
+    DevBuf<double> points, carried;  // S x d x e, S x d x ncarry
     DevBuf<int32_t> level, element;  // S, S
 };
 
@@ -32,5 +35,20 @@ struct Contour {
 void contour_build(Contour& C, const ContourIn& in, hipStream_t st);
 // carried may be NULL; complete on return
 void contour_fetch(const Contour& C, double* points, int32_t* level, int32_t* element, double* carried, hipStream_t st);
+
+// Every lattice triangle of a 2-D mesh (Q_k with e = 2 or 3, P1 / P2), resident on the device until fetched or destroyed.
+struct Tessellation {
+    int32_t e = 0, nfield = 0;
+    int64_t T = 0;
+    DevBuf<double> points, values;   // T x 3 x e, T x 3 x nfield
+    DevBuf<int32_t> element;         // T
+};
+
+// N x 2 refine^2 (Q_k) or N x refine^2 (P1 / P2): known before any device work
+int64_t tessellate_count(const ContourIn& in);
+// one launch, triangle i of element e at e * ntri + i; complete on return
+void tessellate_build(Tessellation& T, const ContourIn& in, hipStream_t st);
+// values may be NULL; complete on return
+void tessellate_fetch(const Tessellation& T, double* points, int32_t* element, double* values, hipStream_t st);
 
 }  // namespace mgbhip

@@ -117,7 +117,8 @@ EXPORTS = [
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
     "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_solver_launches", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
-    "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy",
+    "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
+    "mgbhip_tessellate_create", "mgbhip_tessellate_fetch", "mgbhip_tessellate_destroy",
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
     "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy", "mgbhip_raycast_render_layers",
     "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
@@ -206,6 +207,13 @@ def load_library():
     lib.mgbhip_locator_destroy.argtypes = [vp]
     lib.mgbhip_contour_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32,
                                           _dp, C.c_int32, _dp, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64)]
+    lib.mgbhip_contour_create_embedded.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp,
+                                                   _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(vp),
+                                                   C.POINTER(C.c_int64)]
+    lib.mgbhip_tessellate_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp,
+                                             C.c_int32, _dp, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64)]
+    lib.mgbhip_tessellate_fetch.argtypes = [vp, _dp, _ip, _dp]
+    lib.mgbhip_tessellate_destroy.argtypes = [vp]
     lib.mgbhip_contour_fetch.argtypes = [vp, _dp, _ip, _ip, _dp]
     lib.mgbhip_contour_destroy.argtypes = [vp]
     lib.mgbhip_raycast_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int64,

@@ -1,6 +1,11 @@
 """Rays against surfaces: `TriangleCaster` (nearest hits of rays with a triangle soup and their shading),
 `render_surfaces(contours, eye, target)` and `render_figure(geom, u, eye, target)`.
 
+The reference's picture of a solution on a `fem2d` surface in R^3 cuts every quad into linear cells and draws them
+coloured by the solution (ext/MultiGridBarrierPyPlotExt/plot3d.jl:182-256).  `tessellate()` gives those cells as a
+triangle soup; `render_surfaces` takes it like a 3-D `Contour`, and `render_figure` on such a geometry traces and shades
+it once.
+
 The reference's default picture of a `fem3d` solution draws a volume render, five isosurfaces and optional slices into
 one image (ext/MultiGridBarrierPyPlotExt/plot3d.jl:85-149, PyVista on the CPU).  `isocontour()` gives the isosurfaces and
 slices as a triangle soup and `RayCaster` the volume render; this module turns the soup into pixels on the device
@@ -17,9 +22,10 @@ from typing import Optional
 
 import numpy as np
 
-from .contour import Contour, isocontour
+from .contour import Contour, Tessellation, isocontour, tessellate
 from .interpolate import _c_f64
 from .multigrid import Geometry
+from .tensorfem import TensorFEM
 from .raycast import (RayCaster, _check_clim, _check_size, _check_transfer, _diagonal, _raycast_plan, camera_rays, clip_box,
                       default_transfer, normalize)
 
@@ -244,9 +250,16 @@ class TriangleCaster:
 
 
 def _soup(who: str, contours, values, levels):
-    """The concatenated triangles `(T, 3, 3)` and vertex values `(T, 3)` of one `Contour` or a list of them."""
-    cs = [contours] if isinstance(contours, Contour) else list(contours)
+    """The concatenated triangles `(T, 3, 3)` and vertex values `(T, 3)` of one `Contour` or `Tessellation` (of a
+    surface in R^3) or a list of them."""
+    single = isinstance(contours, (Contour, Tessellation))
+    cs = [contours] if single else list(contours)
     for c in cs:
+        if isinstance(c, Tessellation):
+            if c.points.ndim != 3 or c.points.shape[1:] != (3, 3):
+                raise ValueError(f"{who}: a Tessellation must be of a surface in R^3, (T, 3, 3) (got points of shape "
+                                 f"{c.points.shape}: the triangles of a flat 2-D mesh have e = 2 coordinates)")
+            continue
         if not isinstance(c, Contour):
             raise ValueError(f"{who}: contours must be a Contour or a list of them (got {type(c).__name__})")
         if c.points.ndim != 3 or c.points.shape[1:] != (3, 3):
@@ -262,12 +275,17 @@ def _soup(who: str, contours, values, levels):
             raise ValueError(f"{who}: values must be ({T},) or ({T}, 3) for these contours (got shape {V.shape})")
         return pts, V
     if levels is not None:
-        levels = [levels] if isinstance(contours, Contour) else list(levels)
+        levels = [levels] if single else list(levels)
         if len(levels) != len(cs):
             raise ValueError(f"{who}: levels must give one array of level values per contour ({len(cs)})")
     vals = []
     for i, c in enumerate(cs):
-        if c.carried is not None:
+        if isinstance(c, Tessellation):
+            if c.values is None:
+                raise ValueError(f"{who}: a Tessellation without values needs values= (tessellate(geom, fields) gives "
+                                 "it the fields at its vertices)")
+            vals.append(c.values[..., 0])
+        elif c.carried is not None:
             vals.append(c.carried[..., 0])
         elif levels is not None:
             lev = np.asarray(levels[i], dtype=np.float64).reshape(-1)
@@ -283,14 +301,16 @@ def _soup(who: str, contours, values, levels):
 def render_surfaces(contours, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0,
                     height: Optional[float] = None, values=None, levels=None, transfer=None, clim=None,
                     ambient: float = 0.3, max_hits: int = 1, device_id: int = 0):
-    """`(image, depth)`: the `(H, W, 4)` premultiplied colour and alpha of the triangles of one `Contour` (3-D) or a list
-    of them seen by the camera of `camera_rays`, row 0 at the top, and the `(H, W)` ray parameter of each pixel's first
-    hit (`inf` where there is none).
+    """`(image, depth)`: the `(H, W, 4)` premultiplied colour and alpha of the triangles of one `Contour` (3-D), one
+    `Tessellation` of a surface in R^3 (`e = 3`) or a list mixing them, seen by the camera of `camera_rays`, row 0 at the
+    top, and the `(H, W)` ray parameter of each pixel's first hit (`inf` where there is none).
 
-    `values` is `(T,)` or `(T, 3)` over the concatenated triangles.  Its default is `carried[..., 0]` for a contour that
-    carries fields and the level value per triangle otherwise, looked up in `levels` (the values given to
-    `isocontour`; one array per contour).  `transfer`, `clim` and `ambient` are those of `TriangleCaster.shade`.  The
-    `max_hits` layers of a pixel are composited front to back (`composite_layers`).
+    `values` is `(T,)` or `(T, 3)` over the concatenated triangles.  Its default is `values[..., 0]` for a tessellation
+    (one with `e = 2`, or without values and without `values=`, raises `ValueError`), `carried[..., 0]` for a contour
+    that carries fields and the level value per triangle otherwise, looked up in `levels` (the values given to
+    `isocontour`; one array per contour, tessellations included: their entry is not read).  `transfer`, `clim` and
+    `ambient` are those of `TriangleCaster.shade`.  The `max_hits` layers of a pixel are composited front to back
+    (`composite_layers`).
     """
     who = "render_surfaces"
     pts, V = _soup(who, contours, values, levels)
@@ -310,24 +330,73 @@ def render_surfaces(contours, eye, target, up=(0, 0, 1), size=(800, 600), fov: f
     return composite_layers(layers).reshape(H, W, 4), hits.t[:, 0].reshape(H, W)
 
 
+def _render_surface_figure(geom: Geometry, u, eye, target, up, size, fov, isosurfaces, slices, volume, surface_alpha, step,
+                           transfer, clim, ambient, refine, device_id) -> np.ndarray:
+    """`render_figure` on a `fem2d` surface in R^3: its tessellation traced and shaded once (plot3d.jl:239-256)."""
+    who = "render_figure"
+    for name, given in (("isosurfaces", isosurfaces is not None), ("slices", slices is not None),
+                        ("volume=True", volume is True), ("step", step is not None)):
+        if given:
+            raise ValueError(f"{who}: {name} has no meaning for a fem2d surface in R^3 (the figure is the surface itself, "
+                             "coloured by u)")
+    from .contour import _check_tessellate
+    W, H = _check_size(size)
+    o, d = camera_rays(eye, target, up, (W, H), fov)
+    p, N, _ = geom.x.shape
+    U = np.asarray(u, dtype=np.float64)
+    if U.ndim != 1 or U.shape[0] != p * N:
+        raise ValueError(f"{who}: u must be a vector of {p * N} values for this fem2d geometry (got shape {U.shape})")
+    try:
+        _check_tessellate(geom, U, refine)
+    except ValueError as e:
+        raise ValueError(str(e).replace("tessellate:", f"{who}:", 1)) from None
+    clim = _clim(who, clim, U, "u")
+    table = default_transfer(1.0) if transfer is None else _check_transfer(transfer)      # its sigma column is replaced
+    if not (isinstance(surface_alpha, (int, float, np.integer, np.floating)) and 0.0 <= surface_alpha <= 1.0):
+        raise ValueError(f"{who}: surface_alpha must be a number in [0, 1] (got {surface_alpha!r})")
+    ambient = _check_ambient(who, ambient)
+    tess = tessellate(geom, U, refine, device_id=device_id)
+    surf_table = table.copy()
+    surf_table[:, 3] = float(surface_alpha)
+    K = 1 if surface_alpha == 1 else 4
+    with TriangleCaster(tess.points, device_id=device_id) as tc:
+        hits = tc.trace(o, d, max_hits=K)
+        layers = tc.shade(hits, d, tess.values[..., 0], surf_table, clim, ambient)
+    return composite_layers(layers).reshape(H, W, 4)
+
+
 def render_figure(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0, isosurfaces=None,
-                  slices=None, volume: bool = True, surface_alpha: float = 1.0, step: Optional[float] = None,
-                  transfer=None, clim=None, ambient: float = 0.3, device_id: int = 0) -> np.ndarray:
+                  slices=None, volume: Optional[bool] = None, surface_alpha: float = 1.0, step: Optional[float] = None,
+                  transfer=None, clim=None, ambient: float = 0.3, device_id: int = 0,
+                  refine: Optional[int] = None) -> np.ndarray:
     """`(H, W, 4)`: the reference's default figure of the `fem3d` solution `u`: the volume render of `render_volume` with
     isosurfaces and slices composited into it at their depth, row 0 at the top.
+
+    For a `fem2d` surface in R^3 (`fem2d(K=..., ambient=3)`) the figure is the reference's picture of a solution on a
+    surface (plot3d.jl:182-256): `tessellate(geom, u, refine)` traced and shaded once by `TriangleCaster`, coloured by
+    `u` through `transfer` / `clim` with the alpha `surface_alpha`.  `refine` is that of `tessellate`; `isosurfaces`,
+    `slices`, `volume=True` and `step` given explicitly raise `ValueError` there: they have no meaning on a surface.
+    Everything below is about `fem3d`, where `refine` must stay None.
 
     - `isosurfaces`: the level values; the default is the reference's `[0.1, 0.3, 0.5, 0.7, 0.9] * (max - min) + min`
       over the finite entries of `u`; `[]` draws none.  Their triangles are coloured by their level value.
     - `slices`: a list of `(axis, coordinate)` pairs, each the plane `x[axis] = coordinate` cut by
       `isocontour(geom, geom.xflat[:, axis], [coordinate], carry=u)` and coloured by `u` on it.
-    - `volume=False` gives the surfaces alone.
+    - `volume=False` gives the surfaces alone; the default (None) is True for `fem3d`.
     - `transfer` (`(K, 4)`: `r, g, b, sigma`; the default is that of `render_volume`) and `clim` are shared: the surfaces
       take the table's colours with the alpha `surface_alpha` in place of `sigma`.  A pixel keeps its nearest hit when
       `surface_alpha == 1` and its four nearest otherwise.
     - `step` is the sample distance of the volume (the default is 1/256 of the clip box's diagonal).
     """
     who = "render_figure"
+    disc = geom.discretization
+    if isinstance(disc, TensorFEM) and disc.d == 2 and disc.e == 3:
+        return _render_surface_figure(geom, u, eye, target, up, size, fov, isosurfaces, slices, volume, surface_alpha, step,
+                                      transfer, clim, ambient, refine, device_id)
     _, name, dim, _, p, N, _, _ = _raycast_plan(geom, who)
+    if refine is not None:
+        raise ValueError(f"{who}: refine is for a fem2d surface in R^3 (tessellate); {name} geometries do not take it")
+    volume = True if volume is None else volume
     if dim != 3:
         raise ValueError(f"{who}: {name} geometries are not supported (the camera is 3-D: fem3d only)")
     W, H = _check_size(size)
