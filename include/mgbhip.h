@@ -499,6 +499,41 @@ int mgbhip_surface_shade(mgbhip_surface* s, int64_t R, int32_t K, const double* 
                          double* layer /* R x K x 4 */);
 int mgbhip_surface_destroy(mgbhip_surface* s); /* NULL is a no-op */
 
+/* ---- rays against a soup of capsules: curves drawn as tubes ---------------------------------------------------------
+ * create uploads S segments [points: S x 2 x 3, segment, end point, coordinate; finite; S = 0 is allowed] with a radius
+ * each [finite, > 0] and sorts the boxes of their capsules [the end points' box widened by the radius] into the grid of
+ * the triangle block above, by the same kernels.  A capsule is the set of points within r of the segment [a, b].
+ *  - trace: R rays x = origin + t dir [dir of unit length].  With a . b = (a0 b0 + a1 b1) + a2 b2, without fused
+ *    multiply-add:
+ *      ba = b - a, oa = origin - a, ob = origin - b,
+ *      baba = ba . ba, bard = ba . dir, baoa = ba . oa, rdoa = dir . oa, oaoa = oa . oa,
+ *      A = baba - bard bard, B = baba rdoa - baoa bard, Cq = (baba oaoa - baoa baoa) - (r r) baba, h = B B - A Cq;
+ *      side:  valid iff A > 0, h >= 0 and 0 <= y <= baba, with ts = (-B - sqrt(h)) / A, y = baoa + ts bard; s = y / baba;
+ *      cap a: b2 = dir . oa, c2 = oaoa - r r, h2 = b2 b2 - c2; valid iff h2 >= 0; ta = -b2 - sqrt(h2); s = 0;
+ *      cap b: the same with ob; s = 1.
+ *    The entry parameter is the smallest valid one of ts, ta, tb [compared with < in that order: a tie keeps the earlier
+ *    piece; exact for the union because a capsule is convex].  The capsule is hit iff a piece is valid and
+ *    t_min <= t <= t_max for that entry parameter: a ray that starts inside a capsule does not hit it, exit points are
+ *    never reported, a capsule gives at most one hit.  Per ray the K [1..8] nearest hits in the order of (t, segment
+ *    index) are written to t, segment, s [R x K each]; a missing entry is t = +inf, segment = -1, s = NaN.
+ *  - shade: t, segment, s as trace returned them; values [S x 2] is a value per end point, table [Kt x 4] rows of
+ *    (r, g, b, alpha) looked up as mgbhip_surface_shade looks up its table with c = (1 - s) c0 + s c1;
+ *    x = origin + t dir, q = a + s ba, n = x - q, nn = n / sqrt(n . n), shade = ambient + (1 - ambient) |nn . dir|,
+ *    alpha = min(1, max(0, row[3])); layer [R x K x 4] = ((alpha shade) r, (alpha shade) g, (alpha shade) b, alpha); a
+ *    missing hit or a non-finite c gives a zero layer.
+ * The handle belongs to the context it was created from and must be destroyed before it.  Host pointers; the work runs
+ * on ctx's stream and is complete on return.                                                                        */
+typedef struct mgbhip_tubes mgbhip_tubes;
+int mgbhip_tubes_create(mgbhip_ctx* ctx, int64_t S, const double* points /* S x 2 x 3 */, const double* radii /* S */,
+                        mgbhip_tubes** out);
+int mgbhip_tubes_trace(mgbhip_tubes* s, int64_t R, const double* origin, const double* dir, double t_min, double t_max,
+                       int32_t K, double* t, int32_t* segment, double* sp /* R x K each */);
+int mgbhip_tubes_shade(mgbhip_tubes* s, int64_t R, int32_t K, const double* origin, const double* dir, const double* t,
+                       const int32_t* segment, const double* sp, const double* values /* S x 2 */, int32_t Kt,
+                       const double* table /* Kt x 4 */, double lo, double hi, double ambient,
+                       double* layer /* R x K x 4 */);
+int mgbhip_tubes_destroy(mgbhip_tubes* s); /* NULL is a no-op */
+
 /* ---- field lines: the lines of a vector field traced through the mesh ----------------------------------------------
  * The field is v = (z[:, 0], .., z[:, d-1]) [field = VECTOR: z is (p*N) x d row-major, the element-space functions of
  * the components] or v = grad u [field = GRADIENT: z is the p*N values of u].  v(y) is evaluated as

@@ -30,5 +30,6 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .raycast import RayCaster, camera_rays, render_volume
     from .surface import TriangleCaster, Hits, render_surfaces, render_figure
     from .streamlines import StreamTracer, Streamlines, streamlines
+    from .tubes import (SegmentCaster, TubeHits, segments, curve_segments, merge_layers, render_lines, render_curve)
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

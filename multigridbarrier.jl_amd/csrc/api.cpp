@@ -15,6 +15,7 @@
 #include "raycast.hpp"
 #include "stream.hpp"
 #include "surface.hpp"
+#include "tubes.hpp"
 
 using namespace mgbhip;
 
@@ -81,6 +82,13 @@ struct mgbhip_surface {
     Surface sf;
 };
 static int dev_of(const mgbhip_surface* s) { return (s && s->ctx) ? s->ctx->device : -1; }
+
+// a capsule soup in its grid (tubes.hpp) and the context it lives in
+struct mgbhip_tubes {
+    mgbhip_ctx* ctx = nullptr;
+    Tubes tb;
+};
+static int dev_of(const mgbhip_tubes* s) { return (s && s->ctx) ? s->ctx->device : -1; }
 
 // a field-line tracer (stream.hpp) and the context it lives in
 struct mgbhip_stream {
@@ -1208,6 +1216,80 @@ int mgbhip_surface_shade(mgbhip_surface* s, int64_t R, int32_t K, const double* 
 }
 
 int mgbhip_surface_destroy(mgbhip_surface* s) {
+    MGB_API_BEGIN_ON(s)
+    if (!s) return MGBHIP_OK;
+    (void)hipStreamSynchronize(s->ctx->stream);
+    delete s;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tubes_create(mgbhip_ctx* ctx, int64_t S, const double* points, const double* radii, mgbhip_tubes** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(S >= 0 && S < (int64_t)INT32_MAX / 6, "tubes: bad sizes");
+    MGB_REQUIRE(S == 0 || (points != nullptr && radii != nullptr), "null argument");
+    for (int64_t i = 0; i < S * 6; ++i) MGB_REQUIRE(std::isfinite(points[i]), "tubes: every end point must be finite");
+    for (int64_t i = 0; i < S; ++i)
+        MGB_REQUIRE(std::isfinite(radii[i]) && radii[i] > 0.0, "tubes: every radius must be finite and positive");
+    std::unique_ptr<mgbhip_tubes> s(new mgbhip_tubes());
+    s->ctx = ctx;
+    tubes_build(s->tb, S, points, radii, ctx->stream);
+    *out = s.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tubes_trace(mgbhip_tubes* s, int64_t R, const double* origin, const double* dir, double t_min, double t_max,
+                       int32_t K, double* t, int32_t* segment, double* sp) {
+    MGB_API_BEGIN_ON(s)
+    MGB_REQUIRE(s != nullptr, "null tubes");
+    MGB_REQUIRE(K >= 1 && K <= TUBES_MAX_HITS, "tubes: K must be 1..8");
+    MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * TUBES_MAX_HITS), "tubes: bad sizes");
+    MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && t != nullptr && segment != nullptr && sp != nullptr),
+                "null argument");
+    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, "tubes: t_min must be finite and t_max > t_min");
+    for (int64_t i = 0; i < R * 3; ++i)
+        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "tubes: origins and directions must be finite");
+    for (int64_t r = 0; r < R; ++r) {
+        double q = 0.0;
+        for (int a = 0; a < 3; ++a) q += dir[r * 3 + a] * dir[r * 3 + a];
+        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, "tubes: directions must have unit length");
+    }
+    tubes_trace(s->tb, R, origin, dir, t_min, t_max, K, t, segment, sp, s->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tubes_shade(mgbhip_tubes* s, int64_t R, int32_t K, const double* origin, const double* dir, const double* t,
+                       const int32_t* segment, const double* sp, const double* values, int32_t Kt, const double* table,
+                       double lo, double hi, double ambient, double* layer) {
+    MGB_API_BEGIN_ON(s)
+    MGB_REQUIRE(s != nullptr, "null tubes");
+    MGB_REQUIRE(K >= 1 && K <= TUBES_MAX_HITS, "tubes: K must be 1..8");
+    MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * TUBES_MAX_HITS), "tubes: bad sizes");
+    MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && t != nullptr && segment != nullptr && sp != nullptr &&
+                           layer != nullptr),
+                "null argument");
+    MGB_REQUIRE(table != nullptr && (s->tb.S == 0 || values != nullptr), "null argument");
+    MGB_REQUIRE(Kt >= 2, "tubes: the colour table needs at least two rows");
+    for (int64_t i = 0; i < (int64_t)Kt * 4; ++i) MGB_REQUIRE(std::isfinite(table[i]), "tubes: the colour table must be finite");
+    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "tubes: clim must be finite with lo < hi");
+    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "tubes: ambient must be in [0, 1]");
+    for (int64_t i = 0; i < R * 3; ++i)
+        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "tubes: origins and directions must be finite");
+    for (int64_t i = 0; i < R * K; ++i) {
+        MGB_REQUIRE(segment[i] >= -1 && (int64_t)segment[i] < s->tb.S, "tubes: a segment index is out of range");
+        MGB_REQUIRE(segment[i] < 0 || (std::isfinite(t[i]) && sp[i] >= 0.0 && sp[i] <= 1.0),
+                    "tubes: a hit needs a finite t and s in [0, 1]");
+    }
+    tubes_shade(s->tb, R, K, origin, dir, t, segment, sp, values, Kt, table, lo, hi, ambient, layer, s->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_tubes_destroy(mgbhip_tubes* s) {
     MGB_API_BEGIN_ON(s)
     if (!s) return MGBHIP_OK;
     (void)hipStreamSynchronize(s->ctx->stream);

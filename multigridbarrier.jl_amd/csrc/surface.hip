@@ -6,7 +6,7 @@
 // the element families and their containment tolerances): one thread per triangle forms its box, one block reduces
 // the union, the host picks the cell counts, a count pass and an exclusive scan size the (cell, triangle) pair list, an
 // emit pass writes it in triangle order and a stable radix sort by cell leaves every cell's list ascending in
-// triangle index.  No atomics.  One lane per ray then walks the cells with a 3-D DDA and tests every triangle of a
+// triangle index.  No atomics.  Everything after the boxes lives in box_grid.hpp, which tubes.hip includes too.  One lane per ray then walks the cells with a 3-D DDA and tests every triangle of a
 // cell's list; what a ray hits is a function of the ray and the triangle alone, the grid only decides what is tested.
 //
 // Every index is bounded before it is used: a cell index is clamped to the grid, a candidate is < T by construction,
@@ -18,9 +18,7 @@
 #include <limits>
 #include <string>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "box_grid.hpp"
 #include "surface.hpp"
 
 // No fused multiply-adds in this file: a plain IEEE transcription of the triangle test (tests/surface_twin.py) then
@@ -31,25 +29,7 @@ namespace mgbhip {
 
 namespace {
 
-constexpr int BLOCK = 256;
-// Every triangle's box is widened by PAD_REL * (largest extent of the union + largest |coordinate|) per side before it
-// is cut into cells.  The walk places a ray in a cell with an error of a few eps * (|origin| + |coordinate|) per axis,
-// and a computed hit point leaves its triangle's box by as little; 2^-26 covers both for origins up to 2^20 box sizes
-// away, and is far below any cell side, so it adds no pairs to speak of.
-constexpr double PAD_REL = 1.4901161193847656e-08;   // 2^-26
 constexpr int32_t NO_TRIANGLE = 2147483647;            // in a lane's list; written out as -1
-
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-__device__ inline double dnan() { return __builtin_nan(""); }
-
-// cell index of a scaled coordinate; NaN and anything below the box go to cell 0, anything above to the last cell
-__device__ inline int32_t cell_axis(double s, int32_t n) {
-    if (!(s >= 0.0)) return 0;
-    if (s >= (double)n) return n - 1;
-    const int32_t c = (int32_t)s;
-    return c < n - 1 ? c : n - 1;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // the grid over the soup
@@ -64,104 +44,6 @@ __global__ void __launch_bounds__(BLOCK) tri_boxes(int64_t T, const double* __re
         box[e * 6 + a] = fmin(x0, fmin(x1, x2));
         box[e * 6 + 3 + a] = fmax(x0, fmax(x1, x2));
     }
-}
-
-// one block: the union of all boxes (6 doubles: lo then hi)
-__global__ void __launch_bounds__(1024) union_box(int64_t T, const double* __restrict__ box, double* __restrict__ out) {
-    __shared__ double s[6][1024];
-    double lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
-    for (int64_t e = threadIdx.x; e < T; e += blockDim.x)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], box[e * 6 + a]);
-            hi[a] = fmax(hi[a], box[e * 6 + 3 + a]);
-        }
-    for (int a = 0; a < 3; ++a) { s[a][threadIdx.x] = lo[a]; s[3 + a][threadIdx.x] = hi[a]; }
-    __syncthreads();
-    for (int h = blockDim.x / 2; h > 0; h /= 2) {
-        if ((int)threadIdx.x < h)
-            for (int a = 0; a < 3; ++a) {
-                s[a][threadIdx.x] = fmin(s[a][threadIdx.x], s[a][threadIdx.x + h]);
-                s[3 + a][threadIdx.x] = fmax(s[3 + a][threadIdx.x], s[3 + a][threadIdx.x + h]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) out[threadIdx.x] = s[threadIdx.x][0];
-}
-
-// the cells the padded box of a triangle overlaps
-__device__ inline void box_cells(const SurfaceGrid& g, const double* b, int32_t* c0, int32_t* c1) {
-    for (int a = 0; a < 3; ++a) {
-        c0[a] = cell_axis(((b[a] - g.pad) - g.lo[a]) * g.inv[a], g.n[a]);
-        c1[a] = cell_axis(((b[3 + a] + g.pad) - g.lo[a]) * g.inv[a], g.n[a]);
-    }
-}
-
-__global__ void __launch_bounds__(BLOCK) box_counts(int64_t T, SurfaceGrid g, const double* __restrict__ box,
-                                                    int64_t* __restrict__ count) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= T) return;
-    int32_t c0[3], c1[3];
-    box_cells(g, box + e * 6, c0, c1);
-    int64_t c = 1;
-    for (int a = 0; a < 3; ++a) c *= (int64_t)(c1[a] - c0[a] + 1);
-    count[e] = c;
-}
-
-__global__ void __launch_bounds__(BLOCK) emit_pairs(int64_t T, SurfaceGrid g, const double* __restrict__ box,
-                                                    const int64_t* __restrict__ off, uint32_t* __restrict__ keys,
-                                                    int32_t* __restrict__ vals) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= T) return;
-    int32_t c0[3], c1[3];
-    box_cells(g, box + e * 6, c0, c1);
-    int64_t o = off[e];
-    for (int32_t l = c0[2]; l <= c1[2]; ++l)
-        for (int32_t j = c0[1]; j <= c1[1]; ++j)
-            for (int32_t i = c0[0]; i <= c1[0]; ++i, ++o) {
-                keys[o] = (uint32_t)(((int64_t)l * g.n[1] + j) * g.n[0] + i);
-                vals[o] = (int32_t)e;
-            }
-}
-
-// start[c] = first sorted pair of cell c (start[ncell] = P): every cell is written exactly once
-__global__ void __launch_bounds__(BLOCK) cell_starts(int64_t P, int64_t ncell, const uint32_t* __restrict__ keys,
-                                                     int32_t* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > P) return;
-    const int64_t a = i == 0 ? -1 : (int64_t)keys[i - 1];
-    const int64_t b = i == P ? ncell : (int64_t)keys[i];
-    for (int64_t c = a + 1; c <= b; ++c) start[c] = (int32_t)i;
-}
-
-// cells of side h with h^(#axes of positive extent) = volume / (cells_per_triangle * T), at most 1024 per axis
-SurfaceGrid pick_grid(const double* hb, int64_t T, double cells_per_triangle) {
-    SurfaceGrid g{};
-    double ext_max = 0.0, mag = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        ext_max = std::max(ext_max, hb[3 + a] - hb[a]);
-        mag = std::max(mag, std::max(std::fabs(hb[a]), std::fabs(hb[3 + a])));
-    }
-    g.pad = PAD_REL * (ext_max + mag);
-    double vol = 1.0;
-    int nz = 0;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = hb[a] - 2.0 * g.pad;
-        g.hi[a] = hb[3 + a] + 2.0 * g.pad;
-        if (g.hi[a] > g.lo[a]) { vol *= g.hi[a] - g.lo[a]; ++nz; }
-    }
-    const double h = nz ? std::pow(vol / (cells_per_triangle * (double)T), 1.0 / nz) : 1.0;
-    g.ncell = 1;
-    for (int a = 0; a < 3; ++a) {
-        const double ext = g.hi[a] - g.lo[a];
-        int64_t n = ext > 0 && h > 0 ? (int64_t)std::ceil(ext / h) : 1;
-        n = std::max<int64_t>(1, std::min<int64_t>(n, 1024));
-        g.n[a] = (int32_t)n;
-        g.inv[a] = ext > 0 ? (double)n / ext : 0.0;
-        g.size[a] = ext > 0 ? ext / (double)n : 0.0;
-        g.ncell *= n;
-    }
-    return g;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -358,60 +240,10 @@ void surface_build(Surface& S, int64_t T, const double* points, hipStream_t st) 
     S.g = SurfaceGrid{};
     if (T == 0) return;
     S.pts.upload(points, (size_t)T * 9, st);
-    DevBuf<double> box, ubox;
+    DevBuf<double> box;
     box.alloc((size_t)T * 6);
-    ubox.alloc(6);
     hipLaunchKernelGGL(tri_boxes, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, S.pts.p, box.p);
-    hipLaunchKernelGGL(union_box, dim3(1), dim3(1024), 0, st, T, box.p, ubox.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    double hb[6];
-    ubox.download(hb, 6, st);
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    for (int a = 0; a < 6; ++a) MGB_REQUIRE(std::isfinite(hb[a]), "surface: non-finite triangle box");
-    DevBuf<int64_t> count, off;
-    count.alloc((size_t)T);
-    off.alloc((size_t)T);
-    DevBuf<char> tmp;
-    // About four cells per triangle.  Triangles that span many cells (a slice next to a fine isosurface) can make the
-    // pair list far longer than the soup: the grid is then coarsened until the list is at most 16 T + 4096 pairs.
-    double cells_per_triangle = 4.0;
-    int64_t P = 0;
-    for (;;) {
-        S.g = pick_grid(hb, T, cells_per_triangle);
-        hipLaunchKernelGGL(box_counts, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, S.g, box.p, count.p);
-        MGB_HIP_CHECK(hipGetLastError());
-        size_t scan_bytes = 0;
-        MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, count.p, off.p, (int64_t)0, (size_t)T,
-                                              rocprim::plus<int64_t>(), st));
-        tmp.ensure(scan_bytes + 16);
-        MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, scan_bytes, count.p, off.p, (int64_t)0, (size_t)T,
-                                              rocprim::plus<int64_t>(), st));
-        int64_t last_off = 0, last_count = 0;
-        MGB_HIP_CHECK(hipMemcpyAsync(&last_off, off.p + (T - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        MGB_HIP_CHECK(hipMemcpyAsync(&last_count, count.p + (T - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        MGB_HIP_CHECK(hipStreamSynchronize(st));
-        P = last_off + last_count;
-        if (P <= 16 * T + 4096 || S.g.ncell == 1) break;
-        cells_per_triangle *= 0.125;
-    }
-    MGB_REQUIRE(P > 0 && P < (int64_t)INT32_MAX, "surface: (cell, triangle) pair count exceeds 32-bit indexing");
-    S.P = P;
-    DevBuf<uint32_t> k0, k1;
-    DevBuf<int32_t> v0;
-    k0.alloc((size_t)P); k1.alloc((size_t)P); v0.alloc((size_t)P);
-    S.cand.alloc((size_t)P);
-    hipLaunchKernelGGL(emit_pairs, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, S.g, box.p, off.p, k0.p, v0.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)S.g.ncell >> bits) != 0) ++bits;
-    size_t sort_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, v0.p, S.cand.p, (size_t)P, 0u, bits, st));
-    tmp.ensure(sort_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, v0.p, S.cand.p, (size_t)P, 0u, bits, st));
-    S.start.alloc((size_t)S.g.ncell + 1);
-    hipLaunchKernelGGL(cell_starts, dim3(grid_1d(P + 1)), dim3(BLOCK), 0, st, P, S.g.ncell, k1.p, S.start.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
+    S.P = grid_from_boxes("surface", "triangle", T, box, S.g, S.start, S.cand, st);
 }
 
 void surface_trace(Surface& S, int64_t R, const double* o, const double* dn, double t_min, double t_max, int32_t K,

@@ -123,6 +123,7 @@ EXPORTS = [
     "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy", "mgbhip_raycast_render_layers",
     "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
     "mgbhip_stream_create", "mgbhip_stream_set_field", "mgbhip_stream_trace", "mgbhip_stream_destroy",
+    "mgbhip_tubes_create", "mgbhip_tubes_trace", "mgbhip_tubes_shade", "mgbhip_tubes_destroy",
 ]
 
 
@@ -231,6 +232,11 @@ def load_library():
     lib.mgbhip_surface_shade.argtypes = [vp, C.c_int64, C.c_int32, _dp, _ip, _dp, _dp, _dp, C.c_int32, _dp, C.c_double,
                                          C.c_double, C.c_double, _dp]
     lib.mgbhip_surface_destroy.argtypes = [vp]
+    lib.mgbhip_tubes_create.argtypes = [vp, C.c_int64, _dp, _dp, C.POINTER(vp)]
+    lib.mgbhip_tubes_trace.argtypes = [vp, C.c_int64, _dp, _dp, C.c_double, C.c_double, C.c_int32, _dp, _ip, _dp]
+    lib.mgbhip_tubes_shade.argtypes = [vp, C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, _dp, _dp, C.c_int32, _dp, C.c_double,
+                                       C.c_double, C.c_double, _dp]
+    lib.mgbhip_tubes_destroy.argtypes = [vp]
     lib.mgbhip_stream_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp,
                                          C.POINTER(vp)]
     lib.mgbhip_stream_set_field.argtypes = [vp, _dp]

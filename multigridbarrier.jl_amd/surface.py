@@ -330,8 +330,29 @@ def render_surfaces(contours, eye, target, up=(0, 0, 1), size=(800, 600), fov: f
     return composite_layers(layers).reshape(H, W, 4), hits.t[:, 0].reshape(H, W)
 
 
+def _figure_lines(who: str, lines, line_radius, line_color) -> np.ndarray:
+    """The segments `(S, 2, 3)` of `render_figure`'s `lines`, with `line_radius` and `line_color` checked."""
+    from .tubes import _check_line_color, _check_radius, segments
+    pts, _ = segments(lines, who=who)
+    if not np.all(np.isfinite(pts)):
+        raise ValueError(f"{who}: lines have non-finite points")
+    if line_radius is not None:
+        _check_radius(who, line_radius, int(pts.shape[0]), "line_radius")
+    _check_line_color(who, line_color)
+    return pts
+
+
+def _merge_lines(who: str, seg_pts, o, d, line_radius, line_color, diagonal, ambient, device_id, t_hit, layers):
+    """The triangles' `(t_hit, layers)` with the opaque layer of the segments merged in by depth."""
+    from .tubes import _check_line_color, figure_line_layers, merge_layers
+    lt, ll = figure_line_layers(who, seg_pts, o, d, line_radius, _check_line_color(who, line_color), diagonal, ambient,
+                                device_id)
+    return merge_layers((t_hit, layers), (lt, ll), max_hits=MAX_HITS)
+
+
 def _render_surface_figure(geom: Geometry, u, eye, target, up, size, fov, isosurfaces, slices, volume, surface_alpha, step,
-                           transfer, clim, ambient, refine, device_id) -> np.ndarray:
+                           transfer, clim, ambient, refine, device_id, lines=None, line_radius=None,
+                           line_color=(0.0, 0.0, 0.0)) -> np.ndarray:
     """`render_figure` on a `fem2d` surface in R^3: its tessellation traced and shaded once (plot3d.jl:239-256)."""
     who = "render_figure"
     for name, given in (("isosurfaces", isosurfaces is not None), ("slices", slices is not None),
@@ -355,6 +376,20 @@ def _render_surface_figure(geom: Geometry, u, eye, target, up, size, fov, isosur
     if not (isinstance(surface_alpha, (int, float, np.integer, np.floating)) and 0.0 <= surface_alpha <= 1.0):
         raise ValueError(f"{who}: surface_alpha must be a number in [0, 1] (got {surface_alpha!r})")
     ambient = _check_ambient(who, ambient)
+    levels = seg_pts = None
+    if lines is not None:
+        if isinstance(lines, (list, tuple, np.ndarray)) and all(isinstance(v, (int, float, np.integer, np.floating))
+                                                                 and not isinstance(v, bool) for v in lines):
+            levels = np.asarray(lines, dtype=np.float64).reshape(-1)           # level values: cut below, on the device
+            if not np.all(np.isfinite(levels)):
+                raise ValueError(f"{who}: every level value of lines must be finite")
+            _figure_lines(who, np.zeros((0, 2, 3)), None, line_color)
+            if line_radius is not None and not (isinstance(line_radius, (int, float, np.integer, np.floating))
+                                                and math.isfinite(line_radius) and line_radius > 0.0):
+                raise ValueError(f"{who}: line_radius must be a positive finite number when lines holds level values "
+                                 f"(got {line_radius!r})")
+        else:
+            seg_pts = _figure_lines(who, lines, line_radius, line_color)
     tess = tessellate(geom, U, refine, device_id=device_id)
     surf_table = table.copy()
     surf_table[:, 3] = float(surface_alpha)
@@ -362,13 +397,20 @@ def _render_surface_figure(geom: Geometry, u, eye, target, up, size, fov, isosur
     with TriangleCaster(tess.points, device_id=device_id) as tc:
         hits = tc.trace(o, d, max_hits=K)
         layers = tc.shade(hits, d, tess.values[..., 0], surf_table, clim, ambient)
+    if levels is not None and levels.size:
+        seg_pts = isocontour(geom, U, levels, refine, device_id=device_id).points
+    if seg_pts is not None and seg_pts.shape[0]:
+        nodes = geom.xflat
+        diagonal = _diagonal(np.stack([nodes.min(axis=0), nodes.max(axis=0)]))
+        _, layers = _merge_lines(who, seg_pts, o, d, line_radius, line_color, diagonal, ambient, device_id, hits.t, layers)
     return composite_layers(layers).reshape(H, W, 4)
 
 
 def render_figure(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0, isosurfaces=None,
                   slices=None, volume: Optional[bool] = None, surface_alpha: float = 1.0, step: Optional[float] = None,
                   transfer=None, clim=None, ambient: float = 0.3, device_id: int = 0,
-                  refine: Optional[int] = None) -> np.ndarray:
+                  refine: Optional[int] = None, lines=None, line_radius=None,
+                  line_color=(0.0, 0.0, 0.0)) -> np.ndarray:
     """`(H, W, 4)`: the reference's default figure of the `fem3d` solution `u`: the volume render of `render_volume` with
     isosurfaces and slices composited into it at their depth, row 0 at the top.
 
@@ -387,12 +429,18 @@ def render_figure(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600),
       take the table's colours with the alpha `surface_alpha` in place of `sigma`.  A pixel keeps its nearest hit when
       `surface_alpha == 1` and its four nearest otherwise.
     - `step` is the sample distance of the volume (the default is 1/256 of the clip box's diagonal).
+    - `lines` (anything `tubes.segments()` takes: `Streamlines`, level curves in R^3, `(S, 2, 3)` arrays, a list of them)
+      are drawn into the figure as opaque tubes of the colour `line_color` and the radius `line_radius` (a number or
+      one per segment; the default is 0.01 x the clip box's diagonal): a `SegmentCaster` traces them, `merge_layers`
+      merges their layer with the triangles' by depth.  On a surface `lines` may also be a 1-D array of level values
+      and then means `isocontour(geom, u, lines)`, drawn on the surface; the default radius there is 0.01 x the
+      diagonal of the nodes' box.  With `lines=None` nothing of this runs.
     """
     who = "render_figure"
     disc = geom.discretization
     if isinstance(disc, TensorFEM) and disc.d == 2 and disc.e == 3:
         return _render_surface_figure(geom, u, eye, target, up, size, fov, isosurfaces, slices, volume, surface_alpha, step,
-                                      transfer, clim, ambient, refine, device_id)
+                                      transfer, clim, ambient, refine, device_id, lines, line_radius, line_color)
     _, name, dim, _, p, N, _, _ = _raycast_plan(geom, who)
     if refine is not None:
         raise ValueError(f"{who}: refine is for a fem2d surface in R^3 (tessellate); {name} geometries do not take it")
@@ -432,6 +480,7 @@ def render_figure(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600),
         step = _diagonal(box) / 256.0
     elif not (isinstance(step, (int, float, np.integer, np.floating)) and math.isfinite(step) and step > 0.0):
         raise ValueError(f"{who}: step must be finite and positive (got {step!r})")
+    seg_pts = None if lines is None else _figure_lines(who, lines, line_radius, line_color)
     # the soup: isosurfaces coloured by their level value, slices by the carried u
     pts, vals = [], []
     if lev.size:
@@ -450,7 +499,11 @@ def render_figure(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600),
     with TriangleCaster(pts, device_id=device_id) as tc:
         hits = tc.trace(o, d, max_hits=K)
         layers = tc.shade(hits, d, vals, surf_table, clim, ambient)
+    t_hit = hits.t
+    if seg_pts is not None and seg_pts.shape[0]:
+        t_hit, layers = _merge_lines(who, seg_pts, o, d, line_radius, line_color, _diagonal(box), ambient, device_id,
+                                     t_hit, layers)
     if not volume:
         return composite_layers(layers).reshape(H, W, 4)
     with RayCaster(geom, o, d, step, device_id=device_id) as rc:
-        return rc.render(U, table, clim, layers=(hits.t, layers)).reshape(H, W, 4)
+        return rc.render(U, table, clim, layers=(t_hit, layers)).reshape(H, W, 4)
