@@ -572,6 +572,47 @@ int mgbhip_stream_trace(mgbhip_stream* s, int64_t S, const double* seeds /* S x 
                         int32_t* n /* S */, int32_t* status /* S */);
 int mgbhip_stream_destroy(mgbhip_stream* s); /* NULL is a no-op */
 
+/* ---- the default figure of a fem3d solution, frame after frame -------------------------------------------------------
+ * One handle chains the stages above on the device for a fixed camera, fixed isosurface levels, fixed slices and fixed
+ * colour limits, and renders one field after another; a frame is bitwise what the host gets by chaining
+ * mgbhip_contour_create, mgbhip_surface_create / _trace / _shade and mgbhip_raycast_create / _render_layers with the same
+ * arguments, because the same kernels run on the same inputs.
+ *  - create: family, d, k, p, N, x, table are those of mgbhip_raycast_create, restricted to QK with d = 3 and k <= 8.
+ *    R >= 1 rays [origin, dir: R x 3, dir of unit length], box [2 x 3: the clip box, lo then hi] and step are those of
+ *    mgbhip_raycast_create with t_min = 0, t_max = +inf.  volume != 0 samples and locates the rays once; volume = 0
+ *    draws the surfaces alone.  levels [nlevels, 0..64, finite] are the isosurfaces of u, each coloured by its level
+ *    value; slice i [nslices, 0..16] is the plane x[axes[i]] = coords[i] [axis 0..2, finite], cut as the level set of
+ *    the coordinate function with u carried and coloured by u.  vtable [ntable x 4: r, g, b, sigma >= 0] is the
+ *    volume's table, stable [ntable x 4: r, g, b, alpha] the surfaces', both finite, ntable >= 2; lo < hi finite are
+ *    the colour limits of both; ambient in [0, 1] is that of mgbhip_surface_shade; K [1..8] hits are kept per ray.
+ *    Everything is checked, and refused by count, before anything is allocated.  Resident from here on: the mesh, the
+ *    rays, the levels, the slices' coordinate functions, both tables and, with the volume, the located samples.
+ *  - render: u is p*N values.  The contours are cut with the lattice refine = k; the soup is the isosurface triangles
+ *    followed by the slices in the order given [T = 0 is allowed: every ray misses]; it is put into its grid, traced
+ *    [K nearest hits] and shaded on the device.  With the volume the layers are merged into the samples as
+ *    mgbhip_raycast_render_layers merges them; without it they are composited alone, front to back from T = 1, C = 0 by
+ *    C = C + T layer_rgb, T = T (1 - layer_alpha), giving (C, 1 - T).  out [R x 4] is premultiplied colour and alpha.
+ *    The transfers of a frame are u going in and out coming back, besides the scalar read-backs of the stages.
+ *  - render_rgba8: the same frame over background [3 doubles, finite] as bytes: per colour channel c = C + (1 - alpha) b,
+ *    q = floor(255 min(1, max(0, c)) + 0.5), 0 for a c that is not finite; the fourth byte is that rule applied to
+ *    alpha.  out is R x 4 bytes.  No fused multiply-add.
+ *  - counts: the triangles of the last frame's soup and the (cell, triangle) pairs of its grid [0, 0 before the first
+ *    frame]; either pointer may be NULL.
+ * Per-frame buffers grow to the largest frame seen and are kept.  The handle belongs to the context it was created from
+ * and must be destroyed before it.  Host pointers; the work runs on ctx's stream and is complete on return.          */
+typedef struct mgbhip_figure mgbhip_figure;
+int mgbhip_figure_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
+                         const double* x, const double* table, int64_t R, const double* origin, const double* dir,
+                         const double* box, double step, int32_t volume, int32_t nlevels, const double* levels,
+                         int32_t nslices, const int32_t* axes, const double* coords, int32_t ntable,
+                         const double* vtable /* ntable x 4 */, const double* stable /* ntable x 4 */, double lo,
+                         double hi, double ambient, int32_t K, mgbhip_figure** out);
+int mgbhip_figure_render(mgbhip_figure* f, const double* u /* p*N */, double* out /* R x 4 */);
+int mgbhip_figure_render_rgba8(mgbhip_figure* f, const double* u /* p*N */, const double* background /* 3 */,
+                               uint8_t* out /* R x 4 */);
+int mgbhip_figure_counts(const mgbhip_figure* f, int64_t* ntriangles, int64_t* npairs);
+int mgbhip_figure_destroy(mgbhip_figure* f); /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

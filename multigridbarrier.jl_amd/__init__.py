@@ -29,6 +29,7 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .contour import isocontour, Contour, tessellate, Tessellation
     from .raycast import RayCaster, camera_rays, render_volume
     from .surface import TriangleCaster, Hits, render_surfaces, render_figure
+    from .figure import FigureRenderer, animation_timeline, render_animation
     from .streamlines import StreamTracer, Streamlines, streamlines
     from .tubes import (SegmentCaster, TubeHits, segments, curve_segments, merge_layers, render_lines, render_curve)
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "contour.hpp"
+#include "figure.hpp"
 #include "interpolate.hpp"
 #include "problem.hpp"
 #include "raycast.hpp"
@@ -96,6 +97,13 @@ struct mgbhip_stream {
     StreamTracer tr;
 };
 static int dev_of(const mgbhip_stream* s) { return (s && s->ctx) ? s->ctx->device : -1; }
+
+// a resident figure pipeline (figure.hpp) and the context it lives in
+struct mgbhip_figure {
+    mgbhip_ctx* ctx = nullptr;
+    Figure fig;
+};
+static int dev_of(const mgbhip_figure* f) { return (f && f->ctx) ? f->ctx->device : -1; }
 
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
@@ -1294,6 +1302,102 @@ int mgbhip_tubes_destroy(mgbhip_tubes* s) {
     if (!s) return MGBHIP_OK;
     (void)hipStreamSynchronize(s->ctx->stream);
     delete s;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_figure_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
+                         const double* table, int64_t R, const double* origin, const double* dir, const double* box,
+                         double step, int32_t volume, int32_t nlevels, const double* levels, int32_t nslices,
+                         const int32_t* axes, const double* coords, int32_t ntable, const double* vtable,
+                         const double* stable, double lo, double hi, double ambient, int32_t K, mgbhip_figure** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(family == MGBHIP_INTERP_QK && d == 3, "figure: only the Q_k family with d = 3 (fem3d) has a figure");
+    MGB_REQUIRE(N > 0, "figure: no elements (N = 0)");
+    MGB_REQUIRE(K >= 1 && K <= SURFACE_MAX_HITS, "figure: K must be 1..8");
+    MGB_REQUIRE(p >= 1 && R >= 1 && R < (int64_t)INT32_MAX / (4 * SURFACE_MAX_HITS), "figure: bad sizes");
+    MGB_REQUIRE(nlevels >= 0 && nlevels <= FIGURE_MAX_LEVELS, "figure: nlevels must be 0..64");
+    MGB_REQUIRE(nslices >= 0 && nslices <= FIGURE_MAX_SLICES, "figure: nslices must be 0..16");
+    MGB_REQUIRE(ntable >= 2, "figure: the colour tables need at least two rows");
+    MGB_REQUIRE(origin != nullptr && dir != nullptr && box != nullptr && vtable != nullptr && stable != nullptr,
+                "null argument");
+    MGB_REQUIRE((nlevels == 0 || levels != nullptr) && (nslices == 0 || (axes != nullptr && coords != nullptr)),
+                "null argument");
+    FigureIn in;
+    InterpIn& geo = in.rays.geo;
+    geo.family = family; geo.d = d; geo.k = k; geo.p = p; geo.N = N; geo.x = x; geo.table = table;
+    interpolate_check_geometry(geo);
+    MGB_REQUIRE(k <= CONTOUR_MAX_REFINE_3D, "figure: the contour lattice of a frame is refine = k, at most 8");
+    MGB_REQUIRE(std::isfinite(step) && step > 0.0, "figure: step must be finite and positive");
+    for (int32_t l = 0; l < nlevels; ++l) MGB_REQUIRE(std::isfinite(levels[l]), "figure: a level is not finite");
+    for (int32_t i = 0; i < nslices; ++i)
+        MGB_REQUIRE(axes[i] >= 0 && axes[i] <= 2 && std::isfinite(coords[i]),
+                    "figure: a slice needs an axis in 0..2 and a finite coordinate");
+    for (int64_t i = 0; i < (int64_t)ntable * 4; ++i) {
+        MGB_REQUIRE(std::isfinite(vtable[i]) && (i % 4 != 3 || vtable[i] >= 0.0),
+                    "figure: the volume table must be finite with sigma >= 0");
+        MGB_REQUIRE(std::isfinite(stable[i]), "figure: the surface table must be finite");
+    }
+    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "figure: clim must be finite with lo < hi");
+    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "figure: ambient must be in [0, 1]");
+    for (int64_t i = 0; i < R * 3; ++i)
+        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "figure: origins and directions must be finite");
+    for (int64_t r = 0; r < R; ++r) {
+        double q = 0.0;
+        for (int a = 0; a < 3; ++a) q += dir[r * 3 + a] * dir[r * 3 + a];
+        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, "figure: directions must have unit length");
+    }
+    for (int a = 0; a < 3; ++a)
+        MGB_REQUIRE(std::isfinite(box[a]) && std::isfinite(box[3 + a]) && box[a] <= box[3 + a], "figure: bad clip box");
+    for (int64_t i = 0; i < (int64_t)p * N * 3; ++i) MGB_REQUIRE(std::isfinite(x[i]), "figure: the mesh must be finite");
+    in.rays.R = R; in.rays.origin = origin; in.rays.dir = dir; in.rays.box = box; in.rays.step = step;
+    in.rays.t_min = 0.0; in.rays.t_max = std::numeric_limits<double>::infinity();
+    in.volume = volume ? 1 : 0;
+    in.nlevels = nlevels; in.levels = levels; in.nslices = nslices; in.axes = axes; in.coords = coords;
+    in.ntable = ntable; in.vtable = vtable; in.stable = stable; in.lo = lo; in.hi = hi; in.ambient = ambient; in.K = K;
+    std::unique_ptr<mgbhip_figure> f(new mgbhip_figure());
+    f->ctx = ctx;
+    figure_build(f->fig, in, ctx->stream);
+    *out = f.release();
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_figure_render(mgbhip_figure* f, const double* u, double* out) {
+    MGB_API_BEGIN_ON(f)
+    MGB_REQUIRE(f != nullptr, "null figure");
+    MGB_REQUIRE(u != nullptr && out != nullptr, "null argument");
+    figure_render(f->fig, u, out, f->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_figure_render_rgba8(mgbhip_figure* f, const double* u, const double* background, uint8_t* out) {
+    MGB_API_BEGIN_ON(f)
+    MGB_REQUIRE(f != nullptr, "null figure");
+    MGB_REQUIRE(u != nullptr && background != nullptr && out != nullptr, "null argument");
+    for (int a = 0; a < 3; ++a) MGB_REQUIRE(std::isfinite(background[a]), "figure: the background must be finite");
+    figure_render_rgba8(f->fig, u, background, out, f->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_figure_counts(const mgbhip_figure* f, int64_t* ntriangles, int64_t* npairs) {
+    MGB_API_BEGIN_ON(f)
+    MGB_REQUIRE(f != nullptr, "null figure");
+    if (ntriangles) *ntriangles = f->fig.T;
+    if (npairs) *npairs = f->fig.P;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_figure_destroy(mgbhip_figure* f) {
+    MGB_API_BEGIN_ON(f)
+    if (!f) return MGBHIP_OK;
+    (void)hipStreamSynchronize(f->ctx->stream);
+    delete f;
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -146,39 +146,37 @@ inline SurfaceGrid pick_grid(const double* hb, int64_t T, double cells_per_box) 
 
 // The grid over T > 0 boxes on the device (box: T x 6, lo then hi): union, cell counts, count pass, scan, emit pass,
 // stable sort by cell, cell starts.  Returns the pair count P; g, start (ncell + 1) and cand (P) are complete on return.
+// start, cand and the buffers of w grow and are kept: only the first ncell + 1 and P entries are meant.
 // `who` and `what` name the caller and its primitive in the error messages ("surface", "triangle").
-inline int64_t grid_from_boxes(const char* who, const char* what, int64_t T, const DevBuf<double>& box, SurfaceGrid& g,
-                               DevBuf<int32_t>& start, DevBuf<int32_t>& cand, hipStream_t st) {
-    DevBuf<double> ubox;
-    ubox.alloc(6);
-    hipLaunchKernelGGL(union_box, dim3(1), dim3(1024), 0, st, T, box.p, ubox.p);
+inline int64_t grid_from_boxes(const char* who, const char* what, int64_t T, const double* box, SurfaceGrid& g,
+                               DevBuf<int32_t>& start, DevBuf<int32_t>& cand, GridWork& w, hipStream_t st) {
+    w.ubox.ensure(6);
+    hipLaunchKernelGGL(union_box, dim3(1), dim3(1024), 0, st, T, box, w.ubox.p);
     MGB_HIP_CHECK(hipGetLastError());
     double hb[6];
-    ubox.download(hb, 6, st);
+    w.ubox.download(hb, 6, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     for (int a = 0; a < 6; ++a)
         MGB_REQUIRE(std::isfinite(hb[a]), std::string(who) + ": non-finite " + what + " box");
-    DevBuf<int64_t> count, off;
-    count.alloc((size_t)T);
-    off.alloc((size_t)T);
-    DevBuf<char> tmp;
+    w.count.ensure((size_t)T);
+    w.off.ensure((size_t)T);
     // About four cells per box.  Boxes that span many cells (a slice next to a fine isosurface) can make the pair list
     // far longer than the soup: the grid is then coarsened until the list is at most 16 T + 4096 pairs.
     double cells_per_box = 4.0;
     int64_t P = 0;
     for (;;) {
         g = pick_grid(hb, T, cells_per_box);
-        hipLaunchKernelGGL(box_counts, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, g, box.p, count.p);
+        hipLaunchKernelGGL(box_counts, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, g, box, w.count.p);
         MGB_HIP_CHECK(hipGetLastError());
         size_t scan_bytes = 0;
-        MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, count.p, off.p, (int64_t)0, (size_t)T,
+        MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, w.count.p, w.off.p, (int64_t)0, (size_t)T,
                                               rocprim::plus<int64_t>(), st));
-        tmp.ensure(scan_bytes + 16);
-        MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, scan_bytes, count.p, off.p, (int64_t)0, (size_t)T,
+        w.tmp.ensure(scan_bytes + 16);
+        MGB_HIP_CHECK(rocprim::exclusive_scan((void*)w.tmp.p, scan_bytes, w.count.p, w.off.p, (int64_t)0, (size_t)T,
                                               rocprim::plus<int64_t>(), st));
         int64_t last_off = 0, last_count = 0;
-        MGB_HIP_CHECK(hipMemcpyAsync(&last_off, off.p + (T - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        MGB_HIP_CHECK(hipMemcpyAsync(&last_count, count.p + (T - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        MGB_HIP_CHECK(hipMemcpyAsync(&last_off, w.off.p + (T - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        MGB_HIP_CHECK(hipMemcpyAsync(&last_count, w.count.p + (T - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
         MGB_HIP_CHECK(hipStreamSynchronize(st));
         P = last_off + last_count;
         if (P <= 16 * T + 4096 || g.ncell == 1) break;
@@ -186,23 +184,29 @@ inline int64_t grid_from_boxes(const char* who, const char* what, int64_t T, con
     }
     MGB_REQUIRE(P > 0 && P < (int64_t)INT32_MAX,
                 std::string(who) + ": (cell, " + what + ") pair count exceeds 32-bit indexing");
-    DevBuf<uint32_t> k0, k1;
-    DevBuf<int32_t> v0;
-    k0.alloc((size_t)P); k1.alloc((size_t)P); v0.alloc((size_t)P);
-    cand.alloc((size_t)P);
-    hipLaunchKernelGGL(emit_pairs, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, g, box.p, off.p, k0.p, v0.p);
+    w.k0.ensure((size_t)P); w.k1.ensure((size_t)P); w.v0.ensure((size_t)P);
+    cand.ensure((size_t)P);
+    hipLaunchKernelGGL(emit_pairs, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, g, box, w.off.p, w.k0.p, w.v0.p);
     MGB_HIP_CHECK(hipGetLastError());
     unsigned bits = 1;
     while (bits < 32 && ((uint64_t)g.ncell >> bits) != 0) ++bits;
     size_t sort_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, v0.p, cand.p, (size_t)P, 0u, bits, st));
-    tmp.ensure(sort_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, v0.p, cand.p, (size_t)P, 0u, bits, st));
-    start.alloc((size_t)g.ncell + 1);
-    hipLaunchKernelGGL(cell_starts, dim3(grid_1d(P + 1)), dim3(BLOCK), 0, st, P, g.ncell, k1.p, start.p);
+    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, w.k0.p, w.k1.p, w.v0.p, cand.p, (size_t)P, 0u, bits, st));
+    w.tmp.ensure(sort_bytes + 16);
+    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)w.tmp.p, sort_bytes, w.k0.p, w.k1.p, w.v0.p, cand.p, (size_t)P, 0u, bits,
+                                            st));
+    start.ensure((size_t)g.ncell + 1);
+    hipLaunchKernelGGL(cell_starts, dim3(grid_1d(P + 1)), dim3(BLOCK), 0, st, P, g.ncell, w.k1.p, start.p);
     MGB_HIP_CHECK(hipGetLastError());
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     return P;
+}
+
+// the same with the work buffers of this call alone, freed on return
+inline int64_t grid_from_boxes(const char* who, const char* what, int64_t T, const DevBuf<double>& box, SurfaceGrid& g,
+                               DevBuf<int32_t>& start, DevBuf<int32_t>& cand, hipStream_t st) {
+    GridWork w;
+    return grid_from_boxes(who, what, T, box.p, g, start, cand, w, st);
 }
 
 }  // namespace

@@ -369,64 +369,74 @@ void lattice_sizes(int kind, int r, ContourArgs& a) {
 
 }  // namespace
 
-void contour_build(Contour& C, const ContourIn& in, hipStream_t st) {
+void contour_build_device(Contour& C, const ContourIn& in, const double* d_x, const double* d_table, int32_t table_len,
+                          const double* d_fields, const double* d_levels, ContourWork& w, hipStream_t st) {
     C.d = in.d;
     C.e = in.e;
     C.ncarry = in.nfield - 1;
     C.S = 0;
     if (in.nlevels == 0) return;
-    const int64_t rows = (int64_t)in.p * in.N;
     const int r = in.refine, d = in.d, e = in.e;
     const bool qk = in.family == MGBHIP_INTERP_QK;
     const int kind = qk ? (d == 3 ? KIND_Q3 : KIND_Q2) : KIND_TRI;
-    const std::vector<double> table = lattice_table(in);
-
-    DevBuf<double> d_x, d_table, d_fields, d_levels;
-    d_x.upload(in.x, (size_t)rows * e, st);
-    d_table.upload(table, st);
-    d_fields.upload(in.fields, (size_t)rows * in.nfield, st);
-    d_levels.upload(in.levels, (size_t)in.nlevels, st);
-    DevBuf<int64_t> count, off;
-    count.alloc((size_t)in.N);
-    off.alloc((size_t)in.N);
+    w.count.ensure((size_t)in.N);
+    w.off.ensure((size_t)in.N);
 
     ContourArgs a{};
     a.N = in.N;
     a.p = in.p; a.k = in.k; a.r = r; a.nfield = in.nfield; a.nlevels = in.nlevels;
     lattice_sizes(kind, r, a);
-    a.table_len = (int32_t)table.size();
+    a.table_len = table_len;
     // one wave for an element of few simplices, a workgroup of four otherwise
     const unsigned block = a.nsimp <= 128 ? 64 : MAX_BLOCK;
     a.chunk = (a.nsimp + (int)block - 1) / (int)block;
-    a.x = d_x.p; a.table = d_table.p; a.fields = d_fields.p; a.levels = d_levels.p;
-    a.count = count.p;
-    launch_kind(kind, e, false, block, ((size_t)a.npts + table.size()) * sizeof(double), a, st);
+    a.x = d_x; a.table = d_table; a.fields = d_fields; a.levels = d_levels;
+    a.count = w.count.p;
+    launch_kind(kind, e, false, block, ((size_t)a.npts + (size_t)table_len) * sizeof(double), a, st);
 
     size_t scan_bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, count.p, off.p, (int64_t)0, (size_t)in.N,
+    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, w.count.p, w.off.p, (int64_t)0, (size_t)in.N,
                                           rocprim::plus<int64_t>(), st));
-    DevBuf<char> tmp;
-    tmp.alloc(scan_bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, scan_bytes, count.p, off.p, (int64_t)0, (size_t)in.N,
+    w.tmp.ensure(scan_bytes + 16);
+    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)w.tmp.p, scan_bytes, w.count.p, w.off.p, (int64_t)0, (size_t)in.N,
                                           rocprim::plus<int64_t>(), st));
     int64_t last_off = 0, last_count = 0;
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_off, off.p + (in.N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_count, count.p + (in.N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    MGB_HIP_CHECK(hipMemcpyAsync(&last_off, w.off.p + (in.N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    MGB_HIP_CHECK(hipMemcpyAsync(&last_count, w.count.p + (in.N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     const int64_t S = last_off + last_count;
     MGB_REQUIRE(S >= 0 && S < (int64_t)INT32_MAX, "contour: the number of simplices exceeds 32-bit indexing");
     if (S == 0) return;
 
-    C.points.alloc((size_t)S * d * e);
-    C.level.alloc((size_t)S);
-    C.element.alloc((size_t)S);
-    if (C.ncarry) C.carried.alloc((size_t)S * d * C.ncarry);
+    // grown to the largest soup seen and kept: a Contour that is built again (figure.hip) allocates nothing
+    C.points.ensure((size_t)S * d * e);
+    C.level.ensure((size_t)S);
+    C.element.ensure((size_t)S);
+    if (C.ncarry) C.carried.ensure((size_t)S * d * C.ncarry);
     a.S = S;
-    a.off = off.p;
+    a.off = w.off.p;
     a.points = C.points.p; a.level = C.level.p; a.element = C.element.p; a.carried = C.carried.p;
-    launch_kind(kind, e, true, block, ((size_t)a.npts * (e + in.nfield) + table.size()) * sizeof(double), a, st);
+    launch_kind(kind, e, true, block, ((size_t)a.npts * (e + in.nfield) + (size_t)table_len) * sizeof(double), a, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     C.S = S;
+}
+
+std::vector<double> contour_lattice_table(const ContourIn& in) { return lattice_table(in); }
+
+void contour_build(Contour& C, const ContourIn& in, hipStream_t st) {
+    ContourWork w;
+    if (in.nlevels == 0) {                     // nothing to cut: the core returns before it reads a pointer
+        contour_build_device(C, in, nullptr, nullptr, 0, nullptr, nullptr, w, st);
+        return;
+    }
+    const int64_t rows = (int64_t)in.p * in.N;
+    const std::vector<double> table = lattice_table(in);
+    DevBuf<double> d_x, d_table, d_fields, d_levels;
+    d_x.upload(in.x, (size_t)rows * in.e, st);
+    d_table.upload(table, st);
+    d_fields.upload(in.fields, (size_t)rows * in.nfield, st);
+    d_levels.upload(in.levels, (size_t)in.nlevels, st);
+    contour_build_device(C, in, d_x.p, d_table.p, (int32_t)table.size(), d_fields.p, d_levels.p, w, st);
     // the inputs and the scan buffers are freed at scope exit; hipFree waits for the work that uses them
 }
 

@@ -2,6 +2,7 @@
 // behind mgbhip_tessellate_* (contour.hip).
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include "../../include/mgbhip.h"
 #include "common.hpp"
@@ -33,6 +34,20 @@ struct Contour {
 
 // count pass, exclusive scan over the elements, emit pass; complete on return (C.S is known)
 void contour_build(Contour& C, const ContourIn& in, hipStream_t st);
+
+// the per-element counts, their scan and the scan's scratch: grown to the largest call seen and kept by a caller that
+// builds again and again (figure.hip)
+struct ContourWork {
+    DevBuf<int64_t> count, off;
+    DevBuf<char> tmp;
+};
+// the table the kernels read, formed on the host from in.family, in.k, in.p, in.refine and in.table
+std::vector<double> contour_lattice_table(const ContourIn& in);
+// contour_build for a mesh, a table (contour_lattice_table), fields and levels already on the device: in.x, in.table,
+// in.fields and in.levels are not read.  The buffers of C grow and are kept, so C may be built again; the valid part is
+// the first C.S simplices.  Complete on return.
+void contour_build_device(Contour& C, const ContourIn& in, const double* d_x, const double* d_table, int32_t table_len,
+                          const double* d_fields, const double* d_levels, ContourWork& w, hipStream_t st);
 // carried may be NULL; complete on return
 void contour_fetch(const Contour& C, double* points, int32_t* level, int32_t* element, double* carried, hipStream_t st);
 

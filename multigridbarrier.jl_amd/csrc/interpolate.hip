@@ -852,6 +852,11 @@ void locator_evaluate_device(Locator& L, int32_t ncomp, const double* z, bool gr
     const int64_t rows = (int64_t)L.p * L.N;
     // grown to the largest ncomp seen and kept: no allocation in a run of calls with the same ncomp
     L.z.upload(z, (size_t)rows * ncomp, st);
+    locator_evaluate_resident(L, ncomp, L.z.p, grad, st);
+}
+
+void locator_evaluate_resident(Locator& L, int32_t ncomp, const double* d_z, bool grad, hipStream_t st) {
+    if (L.M == 0) return;
     L.out.ensure((size_t)L.M * ncomp);
     if (grad) L.grad.ensure((size_t)L.M * ncomp * L.d);
     QueryArgs a{};
@@ -860,7 +865,7 @@ void locator_evaluate_device(Locator& L, int32_t ncomp, const double* z, bool gr
     a.ncomp = ncomp;
     a.x = L.x.p;
     a.table = L.table.p;
-    a.z = L.z.p;
+    a.z = d_z;
     a.pts = L.pts.p;
     a.order = L.order.p;
     a.out = L.out.p;

@@ -68,5 +68,7 @@ void locator_evaluate(Locator& L, int32_t ncomp, const double* z, double* out, d
 // the launches of locator_evaluate alone: the values stay in L.out (M x ncomp, by point) and, with grad, the gradients
 // in L.grad; queued on st, not waited for
 void locator_evaluate_device(Locator& L, int32_t ncomp, const double* z, bool grad, hipStream_t st);
+// the same for z already on the device (d_z, (p*N) x ncomp; read, not kept)
+void locator_evaluate_resident(Locator& L, int32_t ncomp, const double* d_z, bool grad, hipStream_t st);
 
 }  // namespace mgbhip

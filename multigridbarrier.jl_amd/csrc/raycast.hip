@@ -322,30 +322,42 @@ void raycast_integrate(RayCaster& RC, int32_t ncomp, const double* z, double* ou
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
+void raycast_render_device(RayCaster& RC, const double* d_u, int32_t K, const double* d_transfer, double lo, double hi,
+                           hipStream_t st) {
+    RC.result.ensure((size_t)RC.R * 4);
+    if (RC.S) locator_evaluate_resident(RC.loc, 1, d_u, false, st);
+    hipLaunchKernelGGL(ray_composite, dim3(grid_1d(RC.R)), dim3(BLOCK), 0, st, RC.R, K, RC.off.p, RC.h.p, RC.loc.out.p,
+                       d_transfer, lo, hi, RC.result.p);
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
 void raycast_render(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi, double* out,
                     hipStream_t st) {
     if (RC.R == 0) return;
-    RC.result.ensure((size_t)RC.R * 4);
     RC.transfer.upload(transfer, (size_t)K * 4, st);
-    if (RC.S) locator_evaluate_device(RC.loc, 1, u, false, st);
-    hipLaunchKernelGGL(ray_composite, dim3(grid_1d(RC.R)), dim3(BLOCK), 0, st, RC.R, K, RC.off.p, RC.h.p, RC.loc.out.p,
-                       RC.transfer.p, lo, hi, RC.result.p);
-    MGB_HIP_CHECK(hipGetLastError());
+    if (RC.S) RC.loc.z.upload(u, (size_t)RC.loc.p * RC.loc.N, st);     // without samples no value is read
+    raycast_render_device(RC, RC.loc.z.p, K, RC.transfer.p, lo, hi, st);
     RC.result.download(out, (size_t)RC.R * 4, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void raycast_render_layers_device(RayCaster& RC, const double* d_u, int32_t K, const double* d_transfer, double lo, double hi,
+                                  int32_t KH, const double* d_t_hit, const double* d_layer, hipStream_t st) {
+    RC.result.ensure((size_t)RC.R * 4);
+    if (RC.S) locator_evaluate_resident(RC.loc, 1, d_u, false, st);
+    hipLaunchKernelGGL(ray_composite_layers, dim3(grid_1d(RC.R)), dim3(BLOCK), 0, st, RC.R, K, RC.off.p, RC.tmin.p, RC.h.p,
+                       RC.loc.out.p, d_transfer, lo, hi, KH, d_t_hit, d_layer, RC.result.p);
+    MGB_HIP_CHECK(hipGetLastError());
 }
 
 void raycast_render_layers(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi,
                            int32_t KH, const double* t_hit, const double* layer, double* out, hipStream_t st) {
     if (RC.R == 0) return;
-    RC.result.ensure((size_t)RC.R * 4);
     RC.transfer.upload(transfer, (size_t)K * 4, st);
     RC.t_hit.upload(t_hit, (size_t)RC.R * KH, st);
     RC.layer.upload(layer, (size_t)RC.R * KH * 4, st);
-    if (RC.S) locator_evaluate_device(RC.loc, 1, u, false, st);
-    hipLaunchKernelGGL(ray_composite_layers, dim3(grid_1d(RC.R)), dim3(BLOCK), 0, st, RC.R, K, RC.off.p, RC.tmin.p, RC.h.p,
-                       RC.loc.out.p, RC.transfer.p, lo, hi, KH, RC.t_hit.p, RC.layer.p, RC.result.p);
-    MGB_HIP_CHECK(hipGetLastError());
+    if (RC.S) RC.loc.z.upload(u, (size_t)RC.loc.p * RC.loc.N, st);     // without samples no value is read
+    raycast_render_layers_device(RC, RC.loc.z.p, K, RC.transfer.p, lo, hi, KH, RC.t_hit.p, RC.layer.p, st);
     RC.result.download(out, (size_t)RC.R * 4, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }

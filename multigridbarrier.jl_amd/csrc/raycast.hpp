@@ -46,4 +46,11 @@ void raycast_render(RayCaster& RC, const double* u, int32_t K, const double* tra
 void raycast_render_layers(RayCaster& RC, const double* u, int32_t K, const double* transfer, double lo, double hi,
                            int32_t KH, const double* t_hit, const double* layer, double* out, hipStream_t st);
 
+// render and render_layers for u, the table, the depths and the layers already on the device, R > 0: the image is left in
+// RC.result (R x 4); queued on st, not waited for
+void raycast_render_device(RayCaster& RC, const double* d_u, int32_t K, const double* d_transfer, double lo, double hi,
+                           hipStream_t st);
+void raycast_render_layers_device(RayCaster& RC, const double* d_u, int32_t K, const double* d_transfer, double lo, double hi,
+                                  int32_t KH, const double* d_t_hit, const double* d_layer, hipStream_t st);
+
 }  // namespace mgbhip

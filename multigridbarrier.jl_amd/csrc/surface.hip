@@ -173,8 +173,9 @@ __global__ void __launch_bounds__(BLOCK) surface_trace_k(int64_t R, const double
 }
 
 template <int K>
-void launch_trace(const Surface& S, int64_t R, double t_min, double t_max, hipStream_t st) {
-    hipLaunchKernelGGL((surface_trace_k<K>), dim3(grid_1d(R)), dim3(BLOCK), 0, st, R, S.o.p, S.dn.p, t_min, t_max, S.g,
+void launch_trace(const Surface& S, int64_t R, const double* d_o, const double* d_dn, double t_min, double t_max,
+                  hipStream_t st) {
+    hipLaunchKernelGGL((surface_trace_k<K>), dim3(grid_1d(R)), dim3(BLOCK), 0, st, R, d_o, d_dn, t_min, t_max, S.g,
                        S.start.p, S.cand.p, S.pts.p, S.t.p, S.tri.p, S.u.p, S.v.p);
 }
 
@@ -234,16 +235,42 @@ __global__ void __launch_bounds__(BLOCK) surface_shade_k(int64_t n, int32_t K, c
 
 }  // namespace
 
-void surface_build(Surface& S, int64_t T, const double* points, hipStream_t st) {
+void surface_build_device(Surface& S, int64_t T, const double* d_points, GridWork& w, hipStream_t st) {
     S.T = T;
     S.P = 0;
     S.g = SurfaceGrid{};
     if (T == 0) return;
-    S.pts.upload(points, (size_t)T * 9, st);
-    DevBuf<double> box;
-    box.alloc((size_t)T * 6);
-    hipLaunchKernelGGL(tri_boxes, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, S.pts.p, box.p);
-    S.P = grid_from_boxes("surface", "triangle", T, box, S.g, S.start, S.cand, st);
+    if (d_points != S.pts.p) {
+        S.pts.ensure((size_t)T * 9);
+        MGB_HIP_CHECK(hipMemcpyAsync(S.pts.p, d_points, (size_t)T * 9 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    w.box.ensure((size_t)T * 6);
+    hipLaunchKernelGGL(tri_boxes, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, S.pts.p, w.box.p);
+    S.P = grid_from_boxes("surface", "triangle", T, w.box.p, S.g, S.start, S.cand, w, st);
+}
+
+void surface_build(Surface& S, int64_t T, const double* points, hipStream_t st) {
+    if (T) S.pts.upload(points, (size_t)T * 9, st);
+    GridWork w;                                // freed on return
+    surface_build_device(S, T, S.pts.p, w, st);
+}
+
+void surface_trace_device(Surface& S, int64_t R, const double* d_o, const double* d_dn, double t_min, double t_max,
+                          int32_t K, hipStream_t st) {
+    const size_t n = (size_t)R * K;
+    S.t.ensure(n); S.u.ensure(n); S.v.ensure(n); S.tri.ensure(n);
+    switch (K) {
+        case 1: launch_trace<1>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 2: launch_trace<2>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 3: launch_trace<3>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 4: launch_trace<4>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 5: launch_trace<5>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 6: launch_trace<6>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 7: launch_trace<7>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        case 8: launch_trace<8>(S, R, d_o, d_dn, t_min, t_max, st); break;
+        default: throw InvalidArgument("surface: K must be 1..8");
+    }
+    MGB_HIP_CHECK(hipGetLastError());
 }
 
 void surface_trace(Surface& S, int64_t R, const double* o, const double* dn, double t_min, double t_max, int32_t K,
@@ -260,24 +287,21 @@ void surface_trace(Surface& S, int64_t R, const double* o, const double* dn, dou
     }
     S.o.upload(o, (size_t)R * 3, st);
     S.dn.upload(dn, (size_t)R * 3, st);
-    S.t.ensure(n); S.u.ensure(n); S.v.ensure(n); S.tri.ensure(n);
-    switch (K) {
-        case 1: launch_trace<1>(S, R, t_min, t_max, st); break;
-        case 2: launch_trace<2>(S, R, t_min, t_max, st); break;
-        case 3: launch_trace<3>(S, R, t_min, t_max, st); break;
-        case 4: launch_trace<4>(S, R, t_min, t_max, st); break;
-        case 5: launch_trace<5>(S, R, t_min, t_max, st); break;
-        case 6: launch_trace<6>(S, R, t_min, t_max, st); break;
-        case 7: launch_trace<7>(S, R, t_min, t_max, st); break;
-        case 8: launch_trace<8>(S, R, t_min, t_max, st); break;
-        default: throw InvalidArgument("surface: K must be 1..8");
-    }
-    MGB_HIP_CHECK(hipGetLastError());
+    surface_trace_device(S, R, S.o.p, S.dn.p, t_min, t_max, K, st);
     S.t.download(t, n, st);
     S.tri.download(tri, n, st);
     S.u.download(u, n, st);
     S.v.download(v, n, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void surface_shade_device(const Surface& S, int64_t R, int32_t K, const double* d_dn, const int32_t* d_tri, const double* d_u,
+                          const double* d_v, const double* d_values, int32_t Kt, const double* d_table, double lo, double hi,
+                          double ambient, double* d_layer, hipStream_t st) {
+    const int64_t n = R * K;
+    hipLaunchKernelGGL(surface_shade_k, dim3(grid_1d(n)), dim3(BLOCK), 0, st, n, K, d_dn, d_tri, d_u, d_v, S.pts.p, d_values,
+                       Kt, d_table, lo, hi, ambient, d_layer);
+    MGB_HIP_CHECK(hipGetLastError());
 }
 
 void surface_shade(Surface& S, int64_t R, int32_t K, const double* dn, const int32_t* tri, const double* u,
@@ -296,9 +320,7 @@ void surface_shade(Surface& S, int64_t R, int32_t K, const double* dn, const int
     S.values.upload(values, (size_t)S.T * 3, st);
     S.table.upload(table, (size_t)Kt * 4, st);
     S.layer.ensure(n * 4);
-    hipLaunchKernelGGL(surface_shade_k, dim3(grid_1d((int64_t)n)), dim3(BLOCK), 0, st, (int64_t)n, K, S.dn.p, S.tri.p,
-                       S.u.p, S.v.p, S.pts.p, S.values.p, Kt, S.table.p, lo, hi, ambient, S.layer.p);
-    MGB_HIP_CHECK(hipGetLastError());
+    surface_shade_device(S, R, K, S.dn.p, S.tri.p, S.u.p, S.v.p, S.values.p, Kt, S.table.p, lo, hi, ambient, S.layer.p, st);
     S.layer.download(layer, n * 4, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }

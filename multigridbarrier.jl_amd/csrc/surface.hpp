@@ -17,6 +17,17 @@ struct SurfaceGrid {
     int64_t ncell;
 };
 
+// What building a grid needs besides its result: the boxes, their union, the per-box counts and their scan, the unsorted
+// pairs and the scratch of the scan and the sort.  A caller that builds again and again (figure.hip) keeps one, and its
+// buffers grow to the largest soup seen.
+struct GridWork {
+    DevBuf<double> box, ubox;
+    DevBuf<int64_t> count, off;
+    DevBuf<char> tmp;
+    DevBuf<uint32_t> k0, k1;
+    DevBuf<int32_t> v0;
+};
+
 // Resident: the soup (72 bytes per triangle), the sorted (cell, triangle) pair list (4 bytes per pair) and the cell
 // starts (4 bytes per cell).  The per-call buffers grow to the largest call seen and are kept.
 struct Surface {
@@ -30,12 +41,23 @@ struct Surface {
 
 // boxes, union, count pass, exclusive scan, emit pass, stable sort by cell; complete on return
 void surface_build(Surface& S, int64_t T, const double* points, hipStream_t st);
+// the same for a soup already on the device (d_points, T x 3 x 3; S.pts.p itself is allowed and then nothing is copied).
+// The buffers of S and w grow and are kept, so S may be built again; T = 0 leaves an empty surface.
+void surface_build_device(Surface& S, int64_t T, const double* d_points, GridWork& w, hipStream_t st);
 // o, dn host R x 3 (dn of unit length); t, u, v host R x K doubles, tri host R x K: the K nearest hits by (t, triangle)
 void surface_trace(Surface& S, int64_t R, const double* o, const double* dn, double t_min, double t_max, int32_t K,
                    double* t, int32_t* tri, double* u, double* v, hipStream_t st);
+// the same for rays on the device, T > 0: the hits are left in S.t, S.tri, S.u, S.v (R x K each); queued on st, not waited for
+void surface_trace_device(Surface& S, int64_t R, const double* d_o, const double* d_dn, double t_min, double t_max,
+                          int32_t K, hipStream_t st);
 // tri, u, v as trace returned them; values host T x 3, table host Kt x 4 (r, g, b, alpha); layer host R x K x 4
 void surface_shade(Surface& S, int64_t R, int32_t K, const double* dn, const int32_t* tri, const double* u,
                    const double* v, const double* values, int32_t Kt, const double* table, double lo, double hi,
                    double ambient, double* layer, hipStream_t st);
+
+// the same for device pointers throughout, T > 0: d_layer is R x K x 4 on the device; queued on st, not waited for
+void surface_shade_device(const Surface& S, int64_t R, int32_t K, const double* d_dn, const int32_t* d_tri, const double* d_u,
+                          const double* d_v, const double* d_values, int32_t Kt, const double* d_table, double lo, double hi,
+                          double ambient, double* d_layer, hipStream_t st);
 
 }  // namespace mgbhip

@@ -124,6 +124,8 @@ EXPORTS = [
     "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
     "mgbhip_stream_create", "mgbhip_stream_set_field", "mgbhip_stream_trace", "mgbhip_stream_destroy",
     "mgbhip_tubes_create", "mgbhip_tubes_trace", "mgbhip_tubes_shade", "mgbhip_tubes_destroy",
+    "mgbhip_figure_create", "mgbhip_figure_render", "mgbhip_figure_render_rgba8", "mgbhip_figure_counts",
+    "mgbhip_figure_destroy",
 ]
 
 
@@ -242,6 +244,14 @@ def load_library():
     lib.mgbhip_stream_set_field.argtypes = [vp, _dp]
     lib.mgbhip_stream_trace.argtypes = [vp, C.c_int64, _dp, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp, _ip, _ip]
     lib.mgbhip_stream_destroy.argtypes = [vp]
+    lib.mgbhip_figure_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int64,
+                                         _dp, _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, C.c_int32, _ip, _dp,
+                                         C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                         C.POINTER(vp)]
+    lib.mgbhip_figure_render.argtypes = [vp, _dp, _dp]
+    lib.mgbhip_figure_render_rgba8.argtypes = [vp, _dp, _dp, C.POINTER(C.c_uint8)]
+    lib.mgbhip_figure_counts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mgbhip_figure_destroy.argtypes = [vp]
     _LIB = lib
     return lib
 
