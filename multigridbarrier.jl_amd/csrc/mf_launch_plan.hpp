@@ -25,6 +25,7 @@ struct MfLaunch {          // one kernel launch: a contiguous range of fronts of
     bool inv = false;      // large fronts on the inverse-based path (W_j = L_jj^{-1} in the arena, pivots in dvec)
     bool iface = false;    // the interface front of a domain-decomposed system, alone in its launch: assembled, summed
                            // over ranks (MfSolver::iface_reduce), then factored redundantly on every rank
+    int32_t grec_first = -1;   // gather launches: record of the launch's first front in the static gather maps (build_gather_maps)
 };
 
 constexpr int BIG_INV_MAX_M = 7000;     // work vectors of the single-workgroup solves stay in LDS
@@ -47,11 +48,16 @@ struct MfSwitches {
     // applying W = L_jj^{-1} is only forward stable in cond(L_jj), and such systems gain nothing from it.
     int64_t inv_min_n;      // MGBHIP_INV_MIN_N, default 1024
     int64_t wave_min_n;     // MGBHIP_WAVE_MIN_N, default 0
+    bool gather_lds_maps;   // MGBHIP_GATHER_LDS_MAPS=1: mf_big_gather builds its index tables in LDS at every launch (the kernel
+                            // before the static gather maps; the reference of tests/test_gpu_gather_maps.py)
+    int gather_ct;          // MGBHIP_GATHER_CT=8/16/32: destination columns per workgroup of every mf_big_gather launch on the
+                            // static maps (default 0: big_gather_ct chooses per launch)
     static MfSwitches from_env() {
         auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
         auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
         return {on("MGBHIP_NO_GEO"), on("MGBHIP_OLD_BIG"), !on("MGBHIP_NO_MERGE_GROUPS"), !on("MGBHIP_NO_PACKED_LEAVES"),
-                !on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0)};
+                !on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0),
+                on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0)};
     }
 };
 
@@ -242,6 +248,60 @@ inline MfBlock0 big_block0_kind(const MfLaunch& L, bool inv) {
 // Backward sweep of an LDS launch: the register-resident variants for max_k <= 8 / <= 16, 0 = the general one
 // (a 32-column variant holds 143 registers and loses more to occupancy on the 8192-front level than it gains)
 inline int backward_small_kmax(const MfLaunch& L) { return L.max_k <= 8 ? 8 : (L.max_k <= 16 ? 16 : 0); }
+
+// Destination columns per workgroup of mf_big_gather on the static maps: 8 (two per wave), doubled up to 32 while the launch
+// keeps at least GATHER_MIN_WGS column workgroups.  A workgroup's fixed cost -- descriptor, map rows into LDS, two
+// barriers, the tail of matrix entries -- is then shared by more columns; below that count the launch no longer fills the
+// device (256 compute units, four resident workgroups each) and wider workgroups only lengthen it.  `forced`:
+// MGBHIP_GATHER_CT.  Measured at L = 9 (profiles/gather_maps_ab.txt).
+constexpr int GATHER_MIN_WGS = 768;
+inline int big_gather_ct(const MfLaunch& L, int forced) {
+    if (forced == 8 || forced == 16 || forced == 32) return forced;
+    int ct = 8;
+    while (ct < 32 && (int64_t)L.count * ((L.max_m + 2 * ct - 1) / (2 * ct)) >= GATHER_MIN_WGS) ct *= 2;
+    return ct;
+}
+
+// ---- static gather maps of mf_big_gather ---------------------------------------------------------------------------
+// What the gathering assembly needs of a front's children is a function of the symbolic plan alone, so analyze() lays it
+// out once.  For every front of a launch whose assembly kind is MF_ASM_GATHER:
+//   gmap[map_off + ch * m + r]   position of front row r in the update block of child ch, or -1 (the inverse of the
+//                                child's relative index list: the table the kernel used to rebuild in LDS at every launch);
+//   one GatherRec                where the maps start and, per child, where its update block starts in the arena
+//                                (F_off + k m + k), its leading dimension m and its size m - k.
+// Records are numbered in launch order; MfLaunch::grec_first is the record of a launch's first front, the others follow.
+struct GatherRec {
+    int64_t map_off;
+    int64_t base[GATHER_MAX_CHILD];
+    int32_t ld[GATHER_MAX_CHILD];
+    int32_t bs[GATHER_MAX_CHILD];
+};
+
+inline void build_gather_maps(const MfPlan& plan, LevelLaunches& levels, std::vector<GatherRec>& recs, std::vector<int32_t>& gmap) {
+    recs.clear();
+    gmap.clear();
+    for (auto& lev : levels)
+        for (auto& L : lev) {
+            L.grec_first = -1;
+            if (L.count == 0 || big_assembly_kind(L) != MF_ASM_GATHER) continue;
+            L.grec_first = (int32_t)recs.size();
+            for (int32_t q = L.first; q < L.first + L.count; ++q) {
+                const Front& f = plan.fronts[q];
+                GatherRec R{};
+                R.map_off = (int64_t)gmap.size();
+                gmap.resize(gmap.size() + (size_t)f.nchild * (size_t)f.m, -1);
+                for (int32_t c = 0; c < f.nchild; ++c) {            // f.nchild <= L.max_child <= GATHER_MAX_CHILD
+                    const Front& ch = plan.fronts[plan.children[f.child_off + c]];
+                    R.base[c] = ch.F_off + (int64_t)ch.k * ch.m + ch.k;
+                    R.ld[c] = ch.m;
+                    R.bs[c] = ch.m - ch.k;
+                    int32_t* mp = gmap.data() + R.map_off + (int64_t)c * f.m;
+                    for (int32_t j = 0; j < ch.m - ch.k; ++j) mp[plan.rel[ch.rel_off + j]] = j;
+                }
+                recs.push_back(R);
+            }
+        }
+}
 
 // ---- read-only report (mgbhip_solver_launches; mf_host_launches of the CPU checker build) ------------------------
 // One row of MF_LAUNCH_ROW int32 per factorization launch, leaves first:

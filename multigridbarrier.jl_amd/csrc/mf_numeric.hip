@@ -205,6 +205,13 @@ void MfSolver::analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, 
     leaf_packed = sw.packed_leaves && pack_leaf_fronts(plan, level_launches, on_big_path, fd);
     d_ug_ptr.upload(ug_ptr, st);
     d_ug_src.upload(ug_src, st);
+    // static gather maps of mf_big_gather: the children's inverted index lists and update-block addresses, once per plan
+    std::vector<GatherRec> grec;
+    std::vector<int32_t> gmap;
+    if (!sw.gather_lds_maps) build_gather_maps(plan, level_launches, grec, gmap);
+    gather_ct = sw.gather_ct;
+    if (grec.empty()) { d_grec.release(); d_gmap.release(); }
+    else { d_grec.upload(grec, st); d_gmap.upload(gmap, st); }
     d_fronts.upload(fd, st);
     h_fronts = fd;
     h_a_dst = remap_a_dst(plan, level_launches);
@@ -235,7 +242,8 @@ void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timer
     // the leaves' update blocks
     const FactorArgs a{condensed ? d_fronts_c.p : d_fronts.p, d_children.p, d_rel.p,
                        condensed ? d_a_src_c.p : (direct ? d_a_src_direct.p : d_a_src.p), condensed ? d_a_dst_c.p : d_a_dst.p,
-                       condensed ? d_a_colptr_c.p : d_a_colptr.p, d_values, d_arena.p, d_dscr.p, d_dvec.p, d_status.p, st};
+                       condensed ? d_a_colptr_c.p : d_a_colptr.p, d_values, d_arena.p, d_dscr.p, d_dvec.p, d_status.p, st,
+                       d_grec.n ? d_grec.p : nullptr, d_gmap.p, gather_ct};
     if (timers) timers->begin("factor");
     factored_inv = !robust;
     if (!status_zero) MGB_HIP_CHECK(hipMemsetAsync(d_status.p, 0, sizeof(int32_t), st));      // [1], the leaf flag of a condensing f2, stays

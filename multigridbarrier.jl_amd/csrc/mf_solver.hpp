@@ -31,6 +31,9 @@ struct FactorArgs {
     double *arena, *dscr, *dvec;
     int32_t* status;
     hipStream_t st;
+    const GatherRec* grec;      // static gather maps of mf_big_gather (build_gather_maps); nullptr: the kernel builds them in LDS
+    const int32_t* gmap;
+    int gather_ct;              // MGBHIP_GATHER_CT (0: big_gather_ct chooses)
 };
 struct SolveArgs {
     const FrontDev* fr;
@@ -124,6 +127,8 @@ class MfSolver {
     DevBuf<double> d_bx, d_xx, d_one;     // bordered right-hand side / solution of solve(), the constant 1
     DevBuf<FrontDev> d_fronts;
     DevBuf<int32_t> d_front_idx, d_children, d_rel, d_a_src, d_a_src_direct, d_a_dst, d_a_colptr;
+    DevBuf<GatherRec> d_grec;             // static gather maps of the gather launches (empty under MGBHIP_GATHER_LDS_MAPS=1)
+    DevBuf<int32_t> d_gmap;
     DevBuf<int64_t> d_ug_ptr, d_ug_src;   // per large front: for every local index the children's update-vector entries, in child order
     DevBuf<double> d_arena, d_uvec, d_y, d_tbig, d_tsol, d_dscr, d_dvec;
     DevBuf<double> d_ifpack;              // packed lower triangle of the interface front (domain decomposition)
@@ -138,6 +143,7 @@ class MfSolver {
     DevBuf<LeafDesc> d_leaf_desc;
     std::vector<std::vector<MfLaunch>> level_launches;   // per level, leaves first (factorization: one per LDS class)
     std::vector<std::vector<MfLaunch>> level_solves;     // triangular solves: all LDS-class fronts of a level in one launch
+    int gather_ct = 0;              // MfSwitches::gather_ct of the last analyze()
     int32_t lds_cap = 88;           // largest m factored out of LDS
     bool uses_inv = false;
     bool y_border_one = false;      // d_y[n] holds the 1 the border sweep starts from
