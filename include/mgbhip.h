@@ -304,7 +304,10 @@ int64_t mgbhip_solver_launches(mgbhip_problem* prob, int32_t level, int32_t* out
  *  - QK          d = 2 or 3, p = (k + 1)^d, x (p*N) x d, table = the k + 1 reference nodes; Newton from xi = 0.
  *  - P1 / P2     d = 2, p = 3 / 6 / 7, x (p*N) x 2, table = p x 10 coefficients of the basis over the monomials
  *                1, l1, l2, l1^2, l1 l2, l2^2, l1^3, l1^2 l2, l1 l2^2, l2^3 (l1 = 1 at corner slot 0, l2 = 1 at the
- *                next corner slot, the third corner is the origin).
+ *                next corner slot, the third corner is the origin).  P2 needs straight elements (every edge node at
+ *                its edge's midpoint, the bubble node at the centroid).
+ *  - P2C         P2 with curved elements: the element map sum_j phi_j(l1, l2) x_j over all p nodes is inverted by
+ *                Newton from the affine pair of the three corners, with Q_k's stopping and containment rule.
  *  - SPECTRAL1D  d = 1, k = n - 1, p = n, N = 1, z = Chebyshev coefficients (n x ncomp), x and table unused.
  *  - SPECTRAL2D  d = 2, k = n - 1, p = n*n, N = 1, z row i*n + j = C[i, j] (value = bx' C by), x and table unused.
  * 2-D / 3-D FEM: a point outside every element (or with a non-finite coordinate) gives NaN and elem -1; a point in
@@ -316,6 +319,7 @@ int64_t mgbhip_solver_launches(mgbhip_problem* prob, int32_t level, int32_t* out
 #define MGBHIP_INTERP_P2 4
 #define MGBHIP_INTERP_SPECTRAL1D 5
 #define MGBHIP_INTERP_SPECTRAL2D 6
+#define MGBHIP_INTERP_P2C 7 /* P2 with curved (isoparametric) elements; arguments, table and layouts are those of P2 */
 int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N,
                        const double* x, const double* table, int32_t ncomp, const double* z, int64_t M,
                        const double* pts, double* out, int32_t* elem);
@@ -325,6 +329,7 @@ int mgbhip_interpolate(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, in
  *  - QK          grad = J^{-T} sum_i grad_xi phi_i(xi) z_i at the located xi, J the Jacobian of the element map there
  *                (curved elements included).
  *  - P1 / P2     the monomial table differentiated in (l1, l2), mapped by the inverse transpose of the two edge vectors.
+ *  - P2C         grad = J^{-T} (du/dl1, du/dl2) with J[a][b] = sum_j dphi_j/dl_b x_j[a] at the located (l1, l2).
  *  - FEM1D       the derivative of the element's Lagrange interpolant over dx/dxi.  Values are clamped outside
  *                [x[0], x[p*N-1]], so the derivative there is 0.0 (also at +-Inf); at the two end points it is the
  *                one-sided derivative of the end element; NaN gives NaN.
@@ -363,8 +368,8 @@ int mgbhip_locator_destroy(mgbhip_locator* loc); /* NULL is a no-op */
  * tetrahedra around the diagonal from [i, j, k] to [i+1, j+1, k+1]; every simplex is cut linearly at every level
  * [a vertex with value >= level is above; a simplex with a non-finite vertex value emits nothing].  The result is an
  * unindexed list of S simplices of d vertices each: segments [d = 2] or triangles [d = 3].
- *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1 and P2
- *    [straight elements] are accepted.
+ *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1, P2
+ *    [straight elements] and P2C are accepted.
  *  - fields is (p*N) x nfield row-major, 1 <= nfield <= 5: column 0 is contoured, the others are carried along and
  *    interpolated linearly to every vertex of the result.
  *  - levels: nlevels finite values [nlevels = 0 gives S = 0]; duplicates are separate levels.
@@ -408,8 +413,8 @@ int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, i
  * The vertices of a triangle are in ascending lattice index.  Triangle i of element n is triangle n * ntri + i of the
  * result: T = N * ntri is known from N and refine, there is no count pass, no scan and there are no atomics; two calls
  * return bitwise equal arrays.
- *  - family, d, k, p, N, table are those of the interpolate entry point above; only QK [d = 2; e = 2 or 3], P1 and P2
- *    [d = e = 2, straight elements] are accepted.  x is (p*N) x e.
+ *  - family, d, k, p, N, table are those of the interpolate entry point above; only QK [d = 2; e = 2 or 3], P1, P2
+ *    [d = e = 2, straight elements] and P2C [d = e = 2] are accepted.  x is (p*N) x e.
  *  - fields is (p*N) x nfield row-major, 0 <= nfield <= 5 [NULL when nfield = 0]: every column is interpolated to every
  *    lattice point like the position.
  *  - refine: 1..16.  T x 3 > 2^31 - 1 vertices is MGBHIP_ERR_INVALID before anything is allocated.
@@ -435,7 +440,7 @@ int mgbhip_tessellate_destroy(mgbhip_tessellation* t); /* NULL is a no-op */
  * element and the reference coordinates on the device; it reports the number of samples S, and S > 2^31 - 1 is
  * MGBHIP_ERR_INVALID before the sample arrays are allocated.
  *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1 and P2
- *    [straight elements] are accepted.  R = 0 is allowed.
+ *    [straight elements] are accepted (not P2C: rays are clipped against the unpadded node box).  R = 0 is allowed.
  *  - offsets [R + 1]: ray r owns samples offsets[r] .. offsets[r + 1] - 1.  samples [S x d]: the positions, regenerated.
  *  - lengths: step[r] = h of ray r [0 without samples], length[r] = h x the number of its samples that lie in an
  *    element; either pointer may be NULL.
@@ -550,8 +555,8 @@ int mgbhip_tubes_destroy(mgbhip_tubes* s); /* NULL is a no-op */
  * for 0 / 0 under normalize]; otherwise it ends after max_steps [>= 1] steps.  min_speed is finite and >= 0.
  *  - points [S x (max_steps + 1) x d]: row 0 of a line is its seed, row i the point after i steps, NaN from row n on.
  *  - n [S]: the number of points of the line, 0 for a seed in no element.  status [S]: MGBHIP_STREAM_*.
- *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1 and P2
- *    [straight elements] are accepted.  S = 0 is a no-op; S (max_steps + 1) d >= 2^31 is MGBHIP_ERR_INVALID before
+ *  - family, d, k, p, N, x, table are those of the interpolate entry point above; only QK [d = 2 or 3], P1, P2
+ *    [straight elements] and P2C are accepted.  S = 0 is a no-op; S (max_steps + 1) d >= 2^31 is MGBHIP_ERR_INVALID before
  *    anything is allocated.
  * One lane traces one line and stores by seed index: two calls return bitwise equal arrays.  The handle belongs to the
  * context it was created from and must be destroyed before it.  Host pointers; the work runs on ctx's stream and is

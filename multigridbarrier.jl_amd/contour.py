@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from .interpolate import MAX_DEGREE, P1, P2, QK, _c_f64, _plan
+from .interpolate import MAX_DEGREE, P1, P2, P2C, QK, _c_f64, _plan
 from .multigrid import Geometry
 from .tensorfem import TensorFEM, _tf_nodes
 
@@ -88,16 +88,16 @@ def _contour_plan(geom: Geometry, who: str = "isocontour", surfaces_only: bool =
         return QK, "fem2d", 2, 3, disc.k, p, N, geom.xflat, _tf_nodes(disc.k)
     family, name, d, k, p, N, xnodes, table = _plan(geom)
     if surfaces_only:
-        if family not in (QK, P1, P2) or d != 2:
+        if family not in (QK, P1, P2, P2C) or d != 2:
             raise ValueError(f"{who}: {name} geometries are not supported (fem2d, flat or a surface in R^3, fem2d_P1 and "
                              "fem2d_P2 are)")
-    elif family not in (QK, P1, P2):
+    elif family not in (QK, P1, P2, P2C):
         raise ValueError(f"{who}: {name} geometries are not supported (fem2d, fem3d, fem2d_P1 and fem2d_P2 are)")
     return family, name, d, d, k, p, N, xnodes, table
 
 
 def default_refine(family: int, k: int) -> int:
-    """The lattice `isocontour()` uses when `refine` is None: k for Q_k, 1 for P1, 2 for P2."""
+    """The lattice `isocontour()` uses when `refine` is None: k for Q_k, 1 for P1, 2 for P2 (straight or curved)."""
     return k if family == QK else (1 if family == P1 else 2)
 
 
@@ -146,8 +146,9 @@ def isocontour(geom: Geometry, z, levels, refine: Optional[int] = None, carry=No
     `ncarry <= 4`: further element-space functions that are interpolated to every vertex of the result
     (`Contour.carried`); each carried column is bitwise what a call with that column alone returns.
 
-    Supported: `fem2d` and `fem3d` (Q_k, `1 <= k <= 8`, curved elements included), `fem2d_P1`, `fem2d_P2` (straight
-    elements, with or without the bubble), and `fem2d` surfaces in R^3 (`fem2d(K=..., ambient=3)`): their level curves
+    Supported: `fem2d` and `fem3d` (Q_k, `1 <= k <= 8`, curved elements included), `fem2d_P1`, `fem2d_P2` (with or
+    without the bubble; curved elements when built with `curved=True`: the lattice positions are sums over all the
+    element's nodes, as for Q_k), and `fem2d` surfaces in R^3 (`fem2d(K=..., ambient=3)`): their level curves
     are segments in R^3, `points` is `(S, 2, 3)`, and every coordinate is formed like the two of a flat mesh, so a
     surface whose third coordinate is `0.0` everywhere returns the bits of the flat call.  `fem1d` (also as a curve in
     R^2 / R^3) and the spectral families raise `ValueError`.
@@ -250,8 +251,8 @@ def tessellate(geom: Geometry, fields=None, refine: Optional[int] = None, device
     (ext/MultiGridBarrierPyPlotExt/plot3d.jl:182-256: every Q_k quad cut into linear cells over its tensor nodes),
     on the device.  `fields` is `(p*N,)` or `(p*N, nfield)` with `nfield <= 5`, in `geom.xflat` row order, or None.
 
-    Supported: `fem2d` (flat, or a surface in R^3: `fem2d(K=..., ambient=3)`), `fem2d_P1`, `fem2d_P2` (straight
-    elements).  Everything else raises `ValueError` naming the family.
+    Supported: `fem2d` (flat, or a surface in R^3: `fem2d(K=..., ambient=3)`), `fem2d_P1`, `fem2d_P2` (curved
+    elements when built with `curved=True`).  Everything else raises `ValueError` naming the family.
 
     The lattice and its triangles are those of `isocontour()` (steps 1 and 2 there; the same device code forms them):
     `refine + 1` equispaced points per axis for Q_k, the barycentric lattice for P1 / P2, the position and every field a

@@ -751,7 +751,7 @@ static void interpolate_check_geometry(InterpIn& in) {
     const int32_t family = in.family, d = in.d, k = in.k, p = in.p;
     const int64_t N = in.N;
     const double* x = in.x;
-    const bool fem = family >= MGBHIP_INTERP_FEM1D && family <= MGBHIP_INTERP_P2;
+    const bool fem = interp_is_fem(family);
     if (fem) {
         MGB_REQUIRE(x != nullptr && in.table != nullptr, "interpolate: FEM families need node coordinates and a table");
         MGB_REQUIRE(k >= 1 && k <= INTERP_MAX_DEGREE, "interpolate: element degree out of range");
@@ -772,6 +772,7 @@ static void interpolate_check_geometry(InterpIn& in) {
         }
         case MGBHIP_INTERP_P1:
         case MGBHIP_INTERP_P2:
+        case MGBHIP_INTERP_P2C:
             MGB_REQUIRE(d == 2, "interpolate: triangles need d = 2");
             MGB_REQUIRE(family == MGBHIP_INTERP_P1 ? p == 3 : (p == 6 || p == 7), "interpolate: bad nodes per triangle");
             in.table_len = (int64_t)p * 10;
@@ -884,8 +885,7 @@ int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, i
     MGB_API_BEGIN_ON(ctx)
     MGB_REQUIRE(ctx != nullptr, "null context");
     MGB_REQUIRE(out != nullptr && nsimplices != nullptr, "null output pointer");
-    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
-                "contour: only the Q_k (d = 2, 3), P1 and P2 families have level sets");
+    MGB_REQUIRE(interp_is_located(family), "contour: only the Q_k (d = 2, 3), P1 and P2 families have level sets");
     MGB_REQUIRE(N > 0, "contour: no elements (N = 0)");
     MGB_REQUIRE(p >= 1 && nlevels >= 0, "contour: bad sizes");
     MGB_REQUIRE(nfield >= 1 && nfield <= CONTOUR_MAX_FIELDS, "contour: nfield must be 1..5 (at most four carried fields)");
@@ -941,7 +941,7 @@ int mgbhip_tessellate_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t
     MGB_API_BEGIN_ON(ctx)
     MGB_REQUIRE(ctx != nullptr, "null context");
     MGB_REQUIRE(out != nullptr && ntriangles != nullptr, "null output pointer");
-    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
+    MGB_REQUIRE(interp_is_located(family),
                 "tessellate: only the Q_k (d = 2), P1 and P2 families are tessellated");
     MGB_REQUIRE(d == 2, "tessellate: d must be 2 (the lattice triangles of 2-D elements)");
     MGB_REQUIRE(N > 0, "tessellate: no elements (N = 0)");
@@ -1113,7 +1113,7 @@ int mgbhip_stream_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, 
     MGB_API_BEGIN_ON(ctx)
     MGB_REQUIRE(ctx != nullptr, "null context");
     MGB_REQUIRE(out != nullptr, "null output pointer");
-    MGB_REQUIRE(family == MGBHIP_INTERP_QK || family == MGBHIP_INTERP_P1 || family == MGBHIP_INTERP_P2,
+    MGB_REQUIRE(interp_is_located(family),
                 "stream: only the Q_k (d = 2, 3), P1 and P2 families are traced");
     MGB_REQUIRE(N > 0, "stream: no elements (N = 0)");
     MGB_REQUIRE(p >= 1 && (int64_t)p * N * 3 < (int64_t)INT32_MAX, "stream: bad sizes");

@@ -233,6 +233,74 @@ __device__ inline bool simplex_locate(const double* __restrict__ x, int64_t e, i
     return l1 >= -tol && l2 >= -tol && 1.0 - l1 - l2 >= -tol;
 }
 
+// phi_j and its derivatives in l1 and l2 at (l1, l2) from the 10-monomial table, formed as simplex_evaluate forms them
+__device__ inline void simplex_basis_d(const double* __restrict__ table, int j, const double (&mono)[10],
+                                       const double (&m1)[10], const double (&m2)[10], double& v, double& v1, double& v2) {
+    v = v1 = v2 = 0.0;
+    for (int m = 0; m < 10; ++m) v += table[j * 10 + m] * mono[m];
+    for (int m = 1; m < 10; ++m) {
+        v1 += table[j * 10 + m] * m1[m];
+        v2 += table[j * 10 + m] * m2[m];
+    }
+}
+
+// Curved (isoparametric) P2 element e: Newton on sum_j phi_j(l1, l2) x_j = q over all p nodes, started from the affine
+// barycentric pair of the three corner slots (what simplex_locate computes; (1/3, 1/3) if those corners are collinear).
+// Stopping and acceptance are those of qk_locate: the step tolerance follows the rounding level of the element, the
+// iteration gives up on |l| > 8, on a non-finite value or after NEWTON_MAXIT steps, and the pair is accepted when l1, l2
+// and 1 - l1 - l2 are >= -max(ACCEPT_TOL, tol).  l1, l2 are the pair the basis is then evaluated at.
+__device__ inline bool p2c_locate(const double* __restrict__ x, int64_t e, int32_t p, const double* __restrict__ table,
+                                  const double* q, double& l1, double& l2) {
+    constexpr int PMAX = 7;
+    const double* xe = x + e * p * 2;
+    {
+        const double ox = xe[8], oy = xe[9];
+        const double ax = xe[0] - ox, ay = xe[1] - oy;
+        const double bx = xe[4] - ox, by = xe[5] - oy;
+        const double rx = q[0] - ox, ry = q[1] - oy;
+        const double det = ax * by - ay * bx;
+        if (det != 0.0) {
+            l1 = (rx * by - ry * bx) / det;
+            l2 = (ax * ry - ay * rx) / det;
+        } else {
+            l1 = l2 = 1.0 / 3.0;
+        }
+    }
+    bool conv = false;
+    double xs = fmax(fabs(q[0]), fabs(q[1])), tol = NEWTON_STEP_TOL;
+    for (int it = 0; it < NEWTON_MAXIT && !conv; ++it) {
+        const double mono[10] = {1.0, l1, l2, l1 * l1, l1 * l2, l2 * l2, l1 * l1 * l1, l1 * l1 * l2, l1 * l2 * l2, l2 * l2 * l2};
+        const double m1[10] = {0.0, 1.0, 0.0, 2 * l1, l2, 0.0, 3 * (l1 * l1), 2 * (l1 * l2), l2 * l2, 0.0};
+        const double m2[10] = {0.0, 0.0, 1.0, 0.0, l1, 2 * l2, 0.0, l1 * l1, 2 * (l1 * l2), 3 * (l2 * l2)};
+        double F[2] = {-q[0], -q[1]}, J[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        for (int j = 0; j < PMAX; ++j)
+            if (j < p) {
+                double v, v1, v2;
+                simplex_basis_d(table, j, mono, m1, m2, v, v1, v2);
+                for (int a = 0; a < 2; ++a) {
+                    const double xa = xe[2 * j + a];
+                    if (it == 0) xs = fmax(xs, fabs(xa));
+                    F[a] += v * xa;
+                    J[a][0] += v1 * xa;
+                    J[a][1] += v2 * xa;
+                }
+            }
+        double Ji[2][2];
+        if (!jac_inverse<2>(J, Ji)) return false;
+        const double d1 = Ji[0][0] * F[0] + Ji[0][1] * F[1], d2 = Ji[1][0] * F[0] + Ji[1][1] * F[1];
+        l1 -= d1;
+        l2 -= d2;
+        const double step = fmax(fabs(d1), fabs(d2)), big = fmax(fabs(l1), fabs(l2));
+        const double ninv = fmax(fabs(Ji[0][0]) + fabs(Ji[0][1]), fabs(Ji[1][0]) + fabs(Ji[1][1]));
+        if (!(big <= 8.0)) return false;         // diverging (or NaN): not this element
+        tol = fmax(NEWTON_STEP_TOL, ROUND_FACTOR * EPS * xs * ninv);
+        conv = step <= tol;
+    }
+    if (!conv) return false;
+    const double acc = fmax(ACCEPT_TOL, tol);
+    return l1 >= -acc && l2 >= -acc && 1.0 - l1 - l2 >= -acc;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // locate and evaluate: one lane per point
 // ---------------------------------------------------------------------------------------------------------------
@@ -364,7 +432,8 @@ __device__ inline bool qk_evaluate(const QueryArgs& a, int64_t q, int64_t found,
     return true;
 }
 
-// P1 / P2 locate: the lowest-index candidate of the point's cell that contains it, with its barycentric pair
+// P1 / P2 locate: the lowest-index candidate of the point's cell that contains it, with its barycentric pair.  Curved
+// P2 (P2C) is located like Q_k: the padded-box test, then Newton on the element map.
 template <int FAM>
 __device__ inline int64_t simplex_find(const QueryArgs& a, const Grid& g, const double (&pt)[2], double& l1, double& l2) {
     const int64_t cell = point_cell<2>(g, pt);
@@ -372,13 +441,60 @@ __device__ inline int64_t simplex_find(const QueryArgs& a, const Grid& g, const 
     const int32_t j1 = a.start[cell + 1];
     for (int32_t j = a.start[cell]; j < j1; ++j) {
         const int64_t e = a.cand[j];
-        if (simplex_locate<FAM>(a.x, e, a.p, pt, l1, l2)) return e;
+        if constexpr (FAM == MGBHIP_INTERP_P2C) {
+            bool inbox = true;         // a point outside the element's padded box is not in the element: skip Newton
+            for (int d = 0; d < 2; ++d) inbox = inbox && pt[d] >= a.box[e * 4 + d] && pt[d] <= a.box[e * 4 + 2 + d];
+            if (inbox && p2c_locate(a.x, e, a.p, a.table, pt, l1, l2)) return e;
+        } else {
+            if (simplex_locate<FAM>(a.x, e, a.p, pt, l1, l2)) return e;
+        }
     }
     return -1;
 }
 
+// P2C with the gradient: the basis and its two derivatives once, the Jacobian from all p nodes, then per component the
+// value (the sum of simplex_evaluate, term for term) next to du/dl1, du/dl2 and grad = J^{-T} (du/dl1, du/dl2).
+__device__ inline bool p2c_evaluate_grad(const QueryArgs& a, int64_t q, int64_t found, double l1, double l2) {
+    const double mono[10] = {1.0, l1, l2, l1 * l1, l1 * l2, l2 * l2, l1 * l1 * l1, l1 * l1 * l2, l1 * l2 * l2, l2 * l2 * l2};
+    const double m1[10] = {0.0, 1.0, 0.0, 2 * l1, l2, 0.0, 3 * (l1 * l1), 2 * (l1 * l2), l2 * l2, 0.0};
+    const double m2[10] = {0.0, 0.0, 1.0, 0.0, l1, 2 * l2, 0.0, l1 * l1, 2 * (l1 * l2), 3 * (l2 * l2)};
+    constexpr int PMAX = 7;
+    double phi[PMAX], p1[PMAX], p2[PMAX], J[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, Ji[2][2];
+    const double* xe = a.x + found * a.p * 2;
+    for (int j = 0; j < PMAX; ++j) {
+        phi[j] = p1[j] = p2[j] = 0.0;
+        if (j < a.p) {
+            simplex_basis_d(a.table, j, mono, m1, m2, phi[j], p1[j], p2[j]);
+            for (int r = 0; r < 2; ++r) {
+                J[r][0] += p1[j] * xe[2 * j + r];
+                J[r][1] += p2[j] * xe[2 * j + r];
+            }
+        }
+    }
+    if (!jac_inverse<2>(J, Ji)) return false;
+    const double* ze = a.z + found * a.p * a.ncomp;
+    for (int c = 0; c < a.ncomp; ++c) {
+        double v = 0.0, g1 = 0.0, g2 = 0.0;
+        for (int j = 0; j < PMAX; ++j)
+            if (j < a.p) {
+                const double zv = ze[j * a.ncomp + c];
+                v += phi[j] * zv;
+                g1 += p1[j] * zv;
+                g2 += p2[j] * zv;
+            }
+        a.out[q * a.ncomp + c] = v;
+        a.grad[(q * a.ncomp + c) * 2] = Ji[0][0] * g1 + Ji[1][0] * g2;
+        a.grad[(q * a.ncomp + c) * 2 + 1] = Ji[0][1] * g1 + Ji[1][1] * g2;
+    }
+    return true;
+}
+
+// P1 / P2 / P2C evaluate at (l1, l2) of element `found`.  False (nothing written) when the Jacobian there cannot be
+// inverted: only P2C with GRAD, whose map is not affine: J[a][b] = sum_j dphi_j/dl_b x_j[a] from all p nodes at the
+// located pair, and grad = J^{-T} (du/dl1, du/dl2).  The values are the same sums in the same order for every family.
 template <int FAM, bool GRAD>
-__device__ inline void simplex_evaluate(const QueryArgs& a, int64_t q, int64_t found, double l1, double l2) {
+__device__ inline bool simplex_evaluate(const QueryArgs& a, int64_t q, int64_t found, double l1, double l2) {
+    if constexpr (FAM == MGBHIP_INTERP_P2C && GRAD) return p2c_evaluate_grad(a, q, found, l1, l2);
     const double mono[10] = {1.0, l1, l2, l1 * l1, l1 * l2, l2 * l2, l1 * l1 * l1, l1 * l1 * l2, l1 * l2 * l2, l2 * l2 * l2};
     constexpr int PMAX = 7;
     double phi[PMAX];
@@ -429,6 +545,7 @@ __device__ inline void simplex_evaluate(const QueryArgs& a, int64_t q, int64_t f
             a.grad[(q * a.ncomp + c) * 2 + 1] = (ax * g2 - bx * g1) / det;
         }
     }
+    return true;
 }
 
 }  // namespace

@@ -148,7 +148,7 @@ __global__ void cell_starts(int64_t P, int64_t ncell, const uint32_t* __restrict
 // query kernel would have evaluated at.
 struct LocArgs {
     int32_t* elem;             // M
-    double* ref;               // Q_k: M x D (xi); P1 / P2: M x 2 (l1, l2); fem1d: M (xi); spectral: unused
+    double* ref;               // Q_k: M x D (xi); P1 / P2 / P2C: M x 2 (l1, l2); fem1d: M (xi); spectral: unused
     int32_t* flag;             // fem1d: one of FEM1D_GENERAL .. FEM1D_CROSSED; unused otherwise
 };
 
@@ -218,8 +218,7 @@ __global__ void __launch_bounds__(BLOCK) query_simplex(QueryArgs a, Grid g) {
     const double pt[2] = {a.pts[q * 2], a.pts[q * 2 + 1]};
     double l1 = 0.0, l2 = 0.0;
     const int64_t found = simplex_find<FAM>(a, g, pt, l1, l2);
-    if (found < 0) { write_nan<2, GRAD>(a, q); return; }
-    simplex_evaluate<FAM, GRAD>(a, q, found, l1, l2);
+    if (found < 0 || !simplex_evaluate<FAM, GRAD>(a, q, found, l1, l2)) { write_nan<2, GRAD>(a, q); return; }
     if (a.elem) a.elem[q] = (int32_t)found;
 }
 
@@ -243,7 +242,7 @@ __global__ void __launch_bounds__(BLOCK) eval_simplex(QueryArgs a, LocArgs l) {
     const int64_t q = a.order[i];
     const int64_t found = l.elem[i];
     if (found < 0) { write_nan<2, GRAD>(a, q); return; }
-    simplex_evaluate<FAM, GRAD>(a, q, found, l.ref[i * 2], l.ref[i * 2 + 1]);
+    if (!simplex_evaluate<FAM, GRAD>(a, q, found, l.ref[i * 2], l.ref[i * 2 + 1])) write_nan<2, GRAD>(a, q);
 }
 
 // d/dx of the Lagrange interpolant of element e at the reference point xi: (sum_j L_j'(xi) z_j) / (sum_j L_j'(xi) x_j)
@@ -543,7 +542,7 @@ void launch_simplex(Pass pass, const QueryArgs& a, const Grid& g, const LocArgs&
     }
 }
 
-// Q_k / P1 / P2 in D dimensions; EVAL needs no grid
+// Q_k / P1 / P2 / P2C in D dimensions; EVAL needs no grid
 template <int D>
 void launch_located(int32_t family, int32_t k, Pass pass, const QueryArgs& a, const Grid& g, const LocArgs& l,
                     hipStream_t st) {
@@ -552,8 +551,10 @@ void launch_located(int32_t family, int32_t k, Pass pass, const QueryArgs& a, co
     } else if constexpr (D == 2) {
         if (family == MGBHIP_INTERP_P1)
             launch_simplex<MGBHIP_INTERP_P1>(pass, a, g, l, st);
-        else
+        else if (family == MGBHIP_INTERP_P2)
             launch_simplex<MGBHIP_INTERP_P2>(pass, a, g, l, st);
+        else
+            launch_simplex<MGBHIP_INTERP_P2C>(pass, a, g, l, st);
     }
     MGB_HIP_CHECK(hipGetLastError());
 }
@@ -617,7 +618,12 @@ void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, 
     DevBuf<double> ubox;
     box.alloc((size_t)N * 2 * D);
     ubox.alloc(2 * D);
-    const double pad = in.family == MGBHIP_INTERP_QK && in.k >= 2 ? QK_BOX_PAD : 0.0;
+    // Curved P2 takes the Q_k pad: the image of a valid element (det J > 0 throughout) is bounded by its three edge
+    // curves, the bubble vanishes on the edges, and each edge is the quadratic through its three nodes.  A quadratic
+    // Lagrange interpolant on three equispaced parameters leaves the interval of its node values by at most 1/8 of
+    // their spread (ends 0 and 1 with mid-node 1 peak at 9/8), so 1/8 of the largest extent always suffices.
+    const bool curved = (in.family == MGBHIP_INTERP_QK && in.k >= 2) || in.family == MGBHIP_INTERP_P2C;
+    const double pad = curved ? QK_BOX_PAD : 0.0;
     hipLaunchKernelGGL((elem_boxes<D>), dim3(grid_1d(N)), dim3(BLOCK), 0, st, N, in.p, d_x, pad, box.p);
     hipLaunchKernelGGL((union_box<D>), dim3(1), dim3(1024), 0, st, N, box.p, ubox.p);
     MGB_HIP_CHECK(hipGetLastError());
@@ -727,7 +733,7 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
     const int64_t rows = (int64_t)in.p * in.N;
     DevBuf<double> d_x, d_table, d_z, d_pts, d_out, d_grad;
     DevBuf<int32_t> d_elem, d_order;
-    const bool fem = in.family <= MGBHIP_INTERP_P2;
+    const bool fem = interp_is_fem(in.family);
     if (fem) d_x.upload(in.x, (size_t)rows * in.d, st);
     if (in.table) d_table.upload(in.table, (size_t)in.table_len, st);
     d_z.upload(in.z, (size_t)rows * in.ncomp, st);
@@ -754,6 +760,7 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
         case MGBHIP_INTERP_QK:
         case MGBHIP_INTERP_P1:
         case MGBHIP_INTERP_P2:
+        case MGBHIP_INTERP_P2C:
             if (in.d == 2) run_located<2>(in, Pass::FUSED, a, none, d_x.p, st, d_order);
             else run_located<3>(in, Pass::FUSED, a, none, d_x.p, st, d_order);
             break;
@@ -774,7 +781,7 @@ void interpolate_run(const InterpIn& in, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------------
 
 void locator_build(Locator& L, const InterpIn& in, hipStream_t st) {
-    const bool fem = in.family <= MGBHIP_INTERP_P2;
+    const bool fem = interp_is_fem(in.family);
     if (in.M == 0 || !fem) {
         L.family = in.family; L.d = in.d; L.k = in.k; L.p = in.p; L.N = in.N; L.M = in.M;
         if (in.M == 0) return;
@@ -790,7 +797,7 @@ void locator_build(Locator& L, const InterpIn& in, hipStream_t st) {
 void locator_build_device(Locator& L, const InterpIn& in, const double* d_pts, hipStream_t st) {
     L.family = in.family; L.d = in.d; L.k = in.k; L.p = in.p; L.N = in.N; L.M = in.M;
     if (in.M == 0) return;
-    MGB_REQUIRE(in.family <= MGBHIP_INTERP_P2, "interpolate: only the FEM families locate device-resident points");
+    MGB_REQUIRE(interp_is_fem(in.family), "interpolate: only the FEM families locate device-resident points");
     const int64_t rows = (int64_t)in.p * in.N;
     L.x.upload(in.x, (size_t)rows * in.d, st);
     L.table.upload(in.table, (size_t)in.table_len, st);
@@ -816,7 +823,7 @@ void locator_build_device(Locator& L, const InterpIn& in, const double* d_pts, h
 
 void locator_elements(const Locator& L, int32_t* elem, hipStream_t st) {
     if (L.M == 0) return;
-    if (L.family > MGBHIP_INTERP_P2) {           // spectral: one element; a non-finite point has none (as write_nan reports)
+    if (!interp_is_fem(L.family)) {              // spectral: one element; a non-finite point has none (as write_nan reports)
         std::vector<double> pts((size_t)L.M * L.d);
         L.pts.download(pts.data(), pts.size(), st);
         MGB_HIP_CHECK(hipStreamSynchronize(st));
@@ -879,6 +886,7 @@ void locator_evaluate_resident(Locator& L, int32_t ncomp, const double* d_z, boo
         case MGBHIP_INTERP_QK:
         case MGBHIP_INTERP_P1:
         case MGBHIP_INTERP_P2:
+        case MGBHIP_INTERP_P2C:
             if (L.d == 2) launch_located<2>(L.family, L.k, Pass::EVAL, a, g, l, st);
             else launch_located<3>(L.family, L.k, Pass::EVAL, a, g, l, st);
             break;

@@ -10,6 +10,14 @@ namespace mgbhip {
 
 constexpr int INTERP_MAX_DEGREE = 8;    // element degree k of the FEM families (the kernels are unrolled per k + 1)
 
+// The families with elements (node coordinates and a basis table).  The ids are not ordered by kind: 5 and 6 are the
+// spectral families, 7 (curved P2) is an element family again.
+inline bool interp_is_fem(int32_t family) {
+    return (family >= MGBHIP_INTERP_FEM1D && family <= MGBHIP_INTERP_P2) || family == MGBHIP_INTERP_P2C;
+}
+// the 2-D / 3-D element families, whose points are located through a grid of element boxes
+inline bool interp_is_located(int32_t family) { return interp_is_fem(family) && family != MGBHIP_INTERP_FEM1D; }
+
 struct InterpIn {
     int32_t family = 0, d = 0, k = 0, p = 0, ncomp = 0;
     int64_t N = 0, M = 0;

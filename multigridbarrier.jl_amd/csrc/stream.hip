@@ -59,8 +59,7 @@ struct SimplexField {
                                            double (&v)[2]) {
         double l1 = 0.0, l2 = 0.0;
         const int64_t found = simplex_find<FAM>(a, g, y, l1, l2);
-        if (found < 0) return false;
-        simplex_evaluate<FAM, GRAD>(a, q, found, l1, l2);
+        if (found < 0 || !simplex_evaluate<FAM, GRAD>(a, q, found, l1, l2)) return false;
         const double* r = GRAD ? a.grad : a.out;
         for (int d = 0; d < 2; ++d) v[d] = r[q * 2 + d];
         return true;
@@ -164,8 +163,7 @@ size_t field_len(const StreamTracer& T) {
 }  // namespace
 
 void stream_build(StreamTracer& T, const InterpIn& geo, int32_t field, const double* z, hipStream_t st) {
-    MGB_REQUIRE(geo.family == MGBHIP_INTERP_QK || geo.family == MGBHIP_INTERP_P1 || geo.family == MGBHIP_INTERP_P2,
-                "stream: only the Q_k (d = 2, 3), P1 and P2 families are traced");
+    MGB_REQUIRE(interp_is_located(geo.family), "stream: only the Q_k (d = 2, 3), P1 and P2 families are traced");
     T.family = geo.family; T.d = geo.d; T.k = geo.k; T.p = geo.p; T.N = geo.N; T.field = field;
     T.x.upload(geo.x, (size_t)geo.p * geo.N * geo.d, st);
     T.table.upload(geo.table, (size_t)geo.table_len, st);
@@ -209,9 +207,12 @@ void stream_trace(StreamTracer& T, int64_t S, const double* seeds, double h, int
     } else if (T.family == MGBHIP_INTERP_P1) {
         if (grad) launch<SimplexField<MGBHIP_INTERP_P1, true>>(a, g, t, st);
         else launch<SimplexField<MGBHIP_INTERP_P1, false>>(a, g, t, st);
-    } else {
+    } else if (T.family == MGBHIP_INTERP_P2) {
         if (grad) launch<SimplexField<MGBHIP_INTERP_P2, true>>(a, g, t, st);
         else launch<SimplexField<MGBHIP_INTERP_P2, false>>(a, g, t, st);
+    } else {
+        if (grad) launch<SimplexField<MGBHIP_INTERP_P2C, true>>(a, g, t, st);
+        else launch<SimplexField<MGBHIP_INTERP_P2C, false>>(a, g, t, st);
     }
     MGB_HIP_CHECK(hipGetLastError());
     T.points.download(points, npts, st);

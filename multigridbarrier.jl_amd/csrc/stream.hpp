@@ -21,7 +21,7 @@ struct StreamTracer {
     DevBuf<int32_t> n, status;
 };
 
-// geo: family, d, k, p, N, x, table (table_len set): QK (d = 2, 3), P1, P2.  z host (p*N) x d (VECTOR) or p*N (GRADIENT).
+// geo: family, d, k, p, N, x, table (table_len set): QK (d = 2, 3), P1, P2, P2C.  z host (p*N) x d (VECTOR) or p*N (GRADIENT).
 void stream_build(StreamTracer& T, const InterpIn& geo, int32_t field, const double* z, hipStream_t st);
 void stream_set_field(StreamTracer& T, const double* z, hipStream_t st);
 // seeds host S x d; points host S x (max_steps + 1) x d, n and status host S; h is the signed step; complete on return

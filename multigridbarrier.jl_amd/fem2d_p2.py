@@ -36,6 +36,9 @@ class FEM2D_P2:
     bubble: bool
     K: np.ndarray       # (3, N, 2) corner mesh
     Kfull: np.ndarray   # (V, N, 2) full node mesh
+    # opt-in of the point-evaluation entries (interpolate, PointLocator, isocontour, tessellate, StreamTracer): elements
+    # whose edge or bubble nodes are off their straight positions are inverted by Newton instead of being refused
+    curved: bool = False
 
     dim = 2
 
@@ -204,7 +207,7 @@ def _extract_corner_mesh(Kfull: np.ndarray) -> np.ndarray:
     return Kfull[[0, 2, 4], :, :].copy()
 
 
-def _build_geometry(Kfull: np.ndarray, t: np.ndarray) -> Geometry:
+def _build_geometry(Kfull: np.ndarray, t: np.ndarray, curved: bool = False) -> Geometry:
     """Fine-level isoparametric operators and weights (reference: src/fem2d_P2.jl:518-596)."""
     p, N, _ = Kfull.shape
     bubble = p == 7
@@ -229,12 +232,17 @@ def _build_geometry(Kfull: np.ndarray, t: np.ndarray) -> Geometry:
     idb = np.broadcast_to(np.eye(p)[None, :, :], (N, p, p)).copy().transpose(2, 1, 0)
     w = (detJ * Rw[:, None]).T.reshape(-1)
     ops = {"id": BlockDiag(idb), "dx": BlockDiag(dxb), "dy": BlockDiag(dyb)}
-    disc = FEM2D_P2(bubble, _extract_corner_mesh(Kfull), Kfull)
+    disc = FEM2D_P2(bubble, _extract_corner_mesh(Kfull), Kfull, bool(curved))
     return Geometry(disc, np.asarray(t, dtype=np.int64), Kfull, w, ops)
 
 
-def fem2d_P2(bubble: bool | None = None, K: np.ndarray | None = None, t: np.ndarray | None = None) -> Geometry:
-    """Single-level P2(+bubble) geometry (reference: `fem2d_P2`, src/fem2d_P2.jl:262-277)."""
+def fem2d_P2(bubble: bool | None = None, K: np.ndarray | None = None, t: np.ndarray | None = None,
+             curved: bool = False) -> Geometry:
+    """Single-level P2(+bubble) geometry (reference: `fem2d_P2`, src/fem2d_P2.jl:262-277).
+
+    The operators and weights are isoparametric whatever `curved` says: it changes no array.  `curved=True` lets
+    `interpolate`, `PointLocator`, `isocontour`, `tessellate` and `StreamTracer` accept elements whose edge or bubble
+    nodes are off their straight positions (they are refused otherwise); `subdivide`, `geometric_mg` and `amg` carry it."""
     b = (K is None or K.shape[0] == 7) if bubble is None else bubble
     Kf = _default_Kfull(b) if K is None else np.asarray(K, dtype=np.float64)
     V = 7 if b else 6
@@ -245,7 +253,7 @@ def fem2d_P2(bubble: bool | None = None, K: np.ndarray | None = None, t: np.ndar
     if t is None:
         flat = Kf.transpose(1, 0, 2).reshape(-1, 2)
         t = dedupe_labels(flat).reshape(Kf.shape[1], V).T
-    return _build_geometry(Kf, t)
+    return _build_geometry(Kf, t, curved)
 
 
 def subdivide(geom: Geometry, L: int) -> Geometry:
@@ -253,9 +261,11 @@ def subdivide(geom: Geometry, L: int) -> Geometry:
     src/multigrid.jl:472 -> src/fem2d_P2.jl:468-596).
 
     Child node coordinates are the parent element map evaluated at the child nodes.
-    For the straight-sided elements the package builds this is the affine image of
-    the child corners, identical (up to roundoff) to the reference's `refine * x`;
-    curved parents would need the reference's bubble-distribution table and are refused.
+    For straight-sided elements this is the affine image of the child corners, identical
+    (up to roundoff) to the reference's `refine * x`.  Curved (isoparametric) parents keep
+    curved children: they take the reference's `x <- refine * x` with `refine_table`, the
+    same products in the same order as `geometric_mg`, so the result is bitwise
+    `geometric_mg(geom, L).geometry`.
     """
     if not isinstance(geom.discretization, FEM2D_P2):
         raise TypeError("subdivide: FEM2D_P2 geometry expected")
@@ -265,8 +275,10 @@ def subdivide(geom: Geometry, L: int) -> Geometry:
     p = Kf.shape[0]
     RK = reference_triangle(p == 7)["K"]
     straight = np.einsum("vc,ced->ved", RK, Kf[[0, 2, 4], :, :])
+    curved = geom.discretization.curved
     if not np.allclose(straight, Kf, rtol=0, atol=1e-13 * max(1.0, np.abs(Kf).max())):
-        raise NotImplementedError("subdivide: curved (isoparametric) P2 elements are not supported")
+        _, topo, _, Kfine = _refine_levels(geom, L)
+        return _build_geometry(Kfine, topo[-1], curved)
     for _ in range(L - 1):
         N = Kf.shape[1]
         six = Kf[:6]                                       # (6, N, 2)
@@ -275,7 +287,7 @@ def subdivide(geom: Geometry, L: int) -> Geometry:
         child_corners = child_corners.transpose(1, 2, 0, 3).reshape(3, 4 * N, 2)  # element-major, child fastest
         Kf = np.einsum("vc,ced->ved", RK, child_corners)
         t = _refine_p2_connectivity(t)
-    return _build_geometry(Kf, t)
+    return _build_geometry(Kf, t, curved)
 
 
 # ---------------------------------------------------------------------------
@@ -470,16 +482,11 @@ def continuous(t: np.ndarray) -> sp.csr_matrix:
     return continuous_subspace(labels, int(labels.max()) + 1, bdry)
 
 
-def geometric_mg(geom: Geometry, L: int) -> MultiGrid:
-    """`geometric_mg(geom, L)`: L levels of red refinement with the element-local transfer table
-    (reference: src/fem2d_P2.jl:468-596).  Per level: continuous zero-trace P2(+bubble), broken identity,
-    constants and the broken-P1 rider."""
-    from .multigrid import make_multigrid
+def _refine_levels(geom: Geometry, L: int):
+    """The coordinate / topology part of L - 1 red refinements with the element-local transfer table, shared by
+    `geometric_mg` and `subdivide` (curved elements): (refine matrices of levels 0 .. L-2, connectivity per level,
+    element count per level, fine node coordinates (p, N_L, 2))."""
     from .tensorfem import _vblock_refine
-    if not isinstance(geom.discretization, FEM2D_P2):
-        raise TypeError("geometric_mg: FEM2D_P2 geometry expected")
-    if L < 1:
-        raise ValueError("L must be >= 1")
     p = geom.x.shape[0]
     T = refine_table(p == 7)
     X, t = geom.x, geom.t
@@ -489,13 +496,27 @@ def geometric_mg(geom: Geometry, L: int) -> MultiGrid:
         topo.append(t)
         sizes.append(4 * sizes[-1])
     refine = [_vblock_refine(T, p, 4, sizes[l]) for l in range(L - 1)]
-    refine.append(sp.identity(p * sizes[-1], format="csr"))
     # fine coordinates: x[l+1] = refine[l] * x[l] like the reference (src/fem2d_P2.jl:513)
     xf = X.transpose(1, 0, 2).reshape(-1, X.shape[2])
     for l in range(L - 1):
         xf = refine[l] @ xf
     Kfine = xf.reshape(sizes[-1], p, X.shape[2]).transpose(1, 0, 2)
-    geomL = _build_geometry(np.ascontiguousarray(Kfine), topo[-1])
+    return refine, topo, sizes, np.ascontiguousarray(Kfine)
+
+
+def geometric_mg(geom: Geometry, L: int) -> MultiGrid:
+    """`geometric_mg(geom, L)`: L levels of red refinement with the element-local transfer table
+    (reference: src/fem2d_P2.jl:468-596).  Per level: continuous zero-trace P2(+bubble), broken identity,
+    constants and the broken-P1 rider."""
+    from .multigrid import make_multigrid
+    if not isinstance(geom.discretization, FEM2D_P2):
+        raise TypeError("geometric_mg: FEM2D_P2 geometry expected")
+    if L < 1:
+        raise ValueError("L must be >= 1")
+    p = geom.x.shape[0]
+    refine, topo, sizes, Kfine = _refine_levels(geom, L)
+    refine.append(sp.identity(p * sizes[-1], format="csr"))
+    geomL = _build_geometry(Kfine, topo[-1], geom.discretization.curved)
     subspaces = {"dirichlet": [], "full": [], "uniform": [], "broken_P1": []}
     for l in range(L):
         nl = p * sizes[l]

@@ -26,6 +26,7 @@ from .tensorfem import TensorFEM, _tf_nodes
 
 # include/mgbhip.h MGBHIP_INTERP_*
 FEM1D, QK, P1, P2, SPECTRAL_1D, SPECTRAL_2D = range(1, 7)
+P2C = 7                 # MGBHIP_INTERP_P2C: fem2d_P2 with curved elements (`fem2d_P2(..., curved=True)`)
 MAX_DEGREE = 8          # csrc/interpolate.hpp INTERP_MAX_DEGREE
 
 
@@ -95,8 +96,15 @@ def _plan(geom: Geometry):
         return P1, "fem2d_P1", 2, 1, p, N, geom.xflat, fem2d_p1.basis_coefficient_table()
     if isinstance(disc, FEM2D_P2):
         p, N, _ = geom.x.shape
-        _check_p2_straight(geom.x, p == 7)
-        return P2, "fem2d_P2", 2, 2, p, N, geom.xflat, fem2d_p2.basis_coefficient_table(p == 7)
+        family = P2                # straight elements take the affine path whatever the flag says
+        try:
+            _check_p2_straight(geom.x, p == 7)
+        except ValueError as err:
+            if not disc.curved:
+                raise ValueError(f"{err} (build the geometry with fem2d_P2(..., curved=True) to evaluate on curved "
+                                 "elements)") from None
+            family = P2C
+        return family, "fem2d_P2", 2, 2, p, N, geom.xflat, fem2d_p2.basis_coefficient_table(p == 7)
     if isinstance(disc, SPECTRAL1D):
         n = len(geom.w)
         return SPECTRAL_1D, "spectral1d", 1, n - 1, n, 1, None, None
@@ -180,9 +188,11 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
 
     - fem1d: the reference's algorithm (src/TensorFEM.jl:967-1014), clamped outside the mesh: `t <= x[0]` gives the
       first value, `t >= x[-1]` the last (also for +-Inf); NaN gives NaN.
-    - fem2d / fem3d (Q_k), fem2d_P1, fem2d_P2 (straight elements): the element map of the lowest-index element that
-      contains the point (within a 1e-11 tolerance in reference coordinates) is inverted and the element's basis
-      evaluated; a point outside the mesh, or with a NaN or Inf coordinate, gives NaN.
+    - fem2d / fem3d (Q_k), fem2d_P1, fem2d_P2: the element map of the lowest-index element that contains the point
+      (within a 1e-11 tolerance in reference coordinates) is inverted and the element's basis evaluated; a point
+      outside the mesh, or with a NaN or Inf coordinate, gives NaN.  fem2d_P2 elements must be straight (every edge
+      node at its edge's midpoint, the bubble at the centroid) unless the geometry was built with
+      `fem2d_P2(..., curved=True)`: curved elements are then inverted by Newton over all their nodes, as for Q_k.
     - spectral1d / spectral2d: the Chebyshev interpolant of the reference, not clamped; a non-finite point gives NaN.
 
     With `return_element=True` the result is `(values, elements)`: the int32 element used per point (-1: none; the
@@ -195,7 +205,8 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
 
     - fem2d / fem3d: `J^{-T} sum_i grad_xi phi_i z_i` with the Jacobian of the element map at the located reference
       point (curved elements included); fem2d_P1 / fem2d_P2: the basis differentiated in barycentric coordinates and
-      mapped by the inverse transpose of the edge vectors.
+      mapped by the inverse transpose of the edge vectors, or, on curved fem2d_P2 elements, of the Jacobian
+      `J[a][b] = sum_j dphi_j/dl_b x_j[a]` at the located barycentric pair.
     - fem1d: the derivative of the element's interpolant over `dx/dxi`.  Values are clamped outside the mesh, so the
       derivative there is 0.0; at `x[0]` and `x[-1]` it is the one-sided derivative of the end element; NaN gives NaN.
     - spectral1d / spectral2d: the derivative of the Chebyshev interpolant (finite at +-1); a non-finite point gives NaN.

@@ -17,20 +17,25 @@ from typing import Optional
 
 import numpy as np
 
-from .interpolate import P1, P2, QK, _c_f64, _columns, _plan
+from .interpolate import P1, P2, P2C, QK, _c_f64, _columns, _plan
 from .multigrid import Geometry
 from .tensorfem import TensorFEM
 
 QK_BOX_PAD = 0.125      # csrc/interp_device.hpp QK_BOX_PAD: a curved Q_k image can leave its nodes' box
 
 
-def _raycast_plan(geom: Geometry, who: str = "RayCaster"):
-    """`interpolate._plan` restricted to the families rays are cast through; ValueError names the family otherwise."""
+def _raycast_plan(geom: Geometry, who: str = "RayCaster", curved_p2: bool = False):
+    """`interpolate._plan` restricted to the families rays are cast through; ValueError names the family otherwise.
+
+    Curved fem2d_P2 (`P2C`) is refused by name unless `curved_p2` is set (the field-line tracer sets it): the ray sampler
+    clips against the unpadded node box, which a curved domain can leave."""
     disc = geom.discretization
     if isinstance(disc, TensorFEM) and disc.e != disc.d:
         raise ValueError(f"{who}: fem{disc.d}d embedded in {disc.e} dimensions (a manifold) is not supported")
     family, name, d, k, p, N, xnodes, table = _plan(geom)
-    if family not in (QK, P1, P2):
+    if family == P2C and not curved_p2:
+        raise ValueError(f"{who}: curved fem2d_P2 geometries are not supported")
+    if family not in (QK, P1, P2, P2C):
         raise ValueError(f"{who}: {name} geometries are not supported (fem2d, fem3d, fem2d_P1 and fem2d_P2 are)")
     if N == 0:
         raise ValueError(f"{who}: the {name} geometry has no elements")
@@ -42,7 +47,7 @@ def _raycast_plan(geom: Geometry, who: str = "RayCaster"):
 def clip_box(geom: Geometry) -> np.ndarray:
     """(2, d): the box rays are clipped against, lo then hi.  The per-axis minimum and maximum of `geom.xflat`; for
     Q_k with k >= 2 every axis is widened by 1/8 of its extent on both sides (a curved image can leave its nodes' box)."""
-    family, _, _, k, _, _, xnodes, _ = _raycast_plan(geom)
+    family, _, _, k, _, _, xnodes, _ = _raycast_plan(geom, "clip_box")
     lo, hi = xnodes.min(axis=0), xnodes.max(axis=0)
     if family == QK and k >= 2:
         ext = hi - lo

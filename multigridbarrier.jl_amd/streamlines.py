@@ -121,8 +121,8 @@ class StreamTracer:
     """The field lines of `v = (z[:, 0], .., z[:, d-1])` (`field="vector"`: `z` is `(p*N, d)`, the columns are the
     velocity components) or of `v = grad u` (`field="gradient"`: `z` is `(p*N,)`), traced on the device.
 
-    Supported: `fem2d` and `fem3d` (Q_k, `1 <= k <= 8`, curved elements included), `fem2d_P1`, `fem2d_P2` (straight
-    elements).  `fem1d`, embedded manifolds and the spectral families raise `ValueError`.  The node coordinates, the
+    Supported: `fem2d` and `fem3d` (Q_k, `1 <= k <= 8`, curved elements included), `fem2d_P1`, `fem2d_P2` (curved
+    elements when built with `curved=True`).  `fem1d`, embedded manifolds and the spectral families raise `ValueError`.  The node coordinates, the
     basis table, the location grid (cells, candidate lists, element boxes) and the field stay on the device for the life
     of the tracer; `set_field(z2)` replaces the field alone (the frames of a parabolic solve), `trace` may be called any
     number of times.
@@ -148,7 +148,7 @@ class StreamTracer:
     def __init__(self, geom: Geometry, z, field: str = "vector", device_id: int = 0):
         self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
         self.closed = False
-        self._family, self._name, self._d, k, self._p, self._N, xnodes, table = _raycast_plan(geom, "StreamTracer")
+        self._family, self._name, self._d, k, self._p, self._N, xnodes, table = _raycast_plan(geom, "StreamTracer", curved_p2=True)
         self._kind = _field_kind(field)
         Z = _check_field(self._name, self._d, self._p, self._N, self._kind, z)
         from .device import HipContext, _check, _ptr
@@ -241,7 +241,7 @@ def streamlines(geom: Geometry, z, seeds, step, max_steps: int, field: str = "ve
                 normalize: bool = False, min_speed: float = 0.0, device_id: int = 0) -> Streamlines:
     """Bitwise `StreamTracer(geom, z, field).trace(seeds, step, max_steps, direction, normalize, min_speed)`, with every
     argument checked before any device work."""
-    _, name, d, _, p, N, _, _ = _raycast_plan(geom, "streamlines")
+    _, name, d, _, p, N, _, _ = _raycast_plan(geom, "streamlines", curved_p2=True)
     _check_field(name, d, p, N, _field_kind(field), z)
     _check_trace(d, seeds, step, max_steps, direction, normalize, min_speed)
     with StreamTracer(geom, z, field, device_id=device_id) as st:
