@@ -3,16 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include "dense.hpp"
+#include "node_core.hpp"
 
 namespace mgbhip {
 
 namespace {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int dtri_index(int k, int k2, int NY) {   // k <= k2
-    return k * NY - (k * (k - 1)) / 2 + (k2 - k);
-}
 
 // ---------------------------------------------------------------------------------------------
 // GEMV.  y = A x: a workgroup of 16 waves owns 64 rows; wave w sums its column range with the
@@ -114,19 +111,13 @@ __global__ __launch_bounds__(256) void dense_node_kernel(const ElemParams P) {
         double val = 0.0;
         if (active) {
             cone_eval<NY, 0>(P.cone, node, n, y, F, g, H);
-            double bar;
-            if (P.bw != nullptr) {
-                const double bwv = P.bw[node];
-                bar = (bwv == 0.0) ? 0.0 : bwv * F;
-            } else {
-                bar = (P.invn == 0.0) ? 0.0 : P.invn * F;   // invn == 0: linear part only (c_dot_Dz)
-            }
+            const double bar = barrier_f0(P, node, F);
             double lin = 0.0;
 #pragma unroll
             for (int k = 0; k < NY; ++k) lin += P.c[node + n * k] * y[k];
             val = bar + P.w[node] * lin;
         }
-        red[tid] = val;
+        red[tid] = val;         // LDS tree, not block_sum_256: the two sum in different orders, switching would change bits
         __syncthreads();
         for (int off = 128; off > 0; off >>= 1) {
             if (tid < off) red[tid] += red[tid + off];
@@ -157,8 +148,8 @@ __global__ __launch_bounds__(256) void dense_node_kernel(const ElemParams P) {
 #pragma unroll
                 for (int k2 = k; k2 < NY; ++k2) {
                     const double h = H[k * NY + k2];
-                    const double sc = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * h) : P.invn * h;
-                    P.dn_Y[node + n * dtri_index(k, k2, NY)] = sc;
+                    const double sc = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * h) : P.invn * h;   // written out: scale_by changes the NY = 1 stream
+                    P.dn_Y[node + n * tri_index(k, k2, NY)] = sc;
                 }
         }
         return;
@@ -168,14 +159,8 @@ __global__ __launch_bounds__(256) void dense_node_kernel(const ElemParams P) {
 template <int NY>
 void launch_node_ny(const ElemParams& P, int mode, hipStream_t st) {
     const dim3 grid((unsigned)dense_grid(P.n)), blk(256);
-    switch (mode) {
-        case MODE_F0: hipLaunchKernelGGL((dense_node_kernel<NY, MODE_F0>), grid, blk, 0, st, P); break;
-        case MODE_F1: hipLaunchKernelGGL((dense_node_kernel<NY, MODE_F1>), grid, blk, 0, st, P); break;
-        case MODE_F2: hipLaunchKernelGGL((dense_node_kernel<NY, MODE_F2>), grid, blk, 0, st, P); break;
-        case MODE_NODE_F: hipLaunchKernelGGL((dense_node_kernel<NY, MODE_NODE_F>), grid, blk, 0, st, P); break;
-        case MODE_NODE_SLACK: hipLaunchKernelGGL((dense_node_kernel<NY, MODE_NODE_SLACK>), grid, blk, 0, st, P); break;
-        default: throw InvalidArgument("launch_dense_eval: bad mode");
-    }
+    if (!dispatch_mode<false>(mode, [&](auto M) { hipLaunchKernelGGL((dense_node_kernel<NY, decltype(M)::value>), grid, blk, 0, st, P); }))
+        throw InvalidArgument("launch_dense_eval: bad mode");      // the node kernels have no MODE_F01
     MGB_HIP_CHECK(hipGetLastError());
 }
 
@@ -211,18 +196,12 @@ __global__ __launch_bounds__(256) void dense_node_wide_kernel(const ElemParams P
         double val = 0.0;
         if (active) {
             cone_eval_wide<0>(P.cone, node, n, nD, y, F, g, nullptr, 0);
-            double bar;
-            if (P.bw != nullptr) {
-                const double bwv = P.bw[node];
-                bar = (bwv == 0.0) ? 0.0 : bwv * F;
-            } else {
-                bar = (P.invn == 0.0) ? 0.0 : P.invn * F;
-            }
+            const double bar = barrier_f0(P, node, F);
             double lin = 0.0;
             for (int k = 0; k < nD; ++k) lin += P.c[node + n * k] * y[k];
             val = bar + P.w[node] * lin;
         }
-        red[tid] = val;
+        red[tid] = val;         // LDS tree, not block_sum_256: the two sum in different orders, switching would change bits
         __syncthreads();
         for (int off = 128; off > 0; off >>= 1) {
             if (tid < off) red[tid] += red[tid + off];
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(256) void dense_node_wide_kernel(const ElemParams P
             const double bwv = P.bw ? P.bw[node] : 0.0;
             for (int t = 0; t < NT; ++t) {
                 const double h = Tn[n * t];
-                Tn[n * t] = P.bw ? ((bwv == 0.0) ? 0.0 : bwv * h) : P.invn * h;
+                Tn[n * t] = scale_by(P, bwv, h);
             }
         }
         return;
@@ -263,14 +242,8 @@ __global__ __launch_bounds__(256) void dense_node_wide_kernel(const ElemParams P
 
 static void launch_node_wide(const ElemParams& P, int mode, hipStream_t st) {
     const dim3 grid((unsigned)dense_grid(P.n)), blk(256);
-    switch (mode) {
-        case MODE_F0: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_F0>), grid, blk, 0, st, P); break;
-        case MODE_F1: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_F1>), grid, blk, 0, st, P); break;
-        case MODE_F2: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_F2>), grid, blk, 0, st, P); break;
-        case MODE_NODE_F: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_NODE_F>), grid, blk, 0, st, P); break;
-        case MODE_NODE_SLACK: hipLaunchKernelGGL((dense_node_wide_kernel<MODE_NODE_SLACK>), grid, blk, 0, st, P); break;
-        default: throw InvalidArgument("launch_dense_eval: bad mode");
-    }
+    if (!dispatch_mode<false>(mode, [&](auto M) { hipLaunchKernelGGL((dense_node_wide_kernel<decltype(M)::value>), grid, blk, 0, st, P); }))
+        throw InvalidArgument("launch_dense_eval: bad mode");
     MGB_HIP_CHECK(hipGetLastError());
 }
 
@@ -294,7 +267,7 @@ __global__ __launch_bounds__(256) void dense_weight_kernel(int klo, int khi, int
 #pragma unroll
         for (int k2 = 0; k2 < NY; ++k2) {
             if (k2 < klo || k2 > khi) continue;
-            const int t = (k <= k2) ? dtri_index(k, k2, NY) : dtri_index(k2, k, NY);
+            const int t = (k <= k2) ? tri_index(k, k2, NY) : tri_index(k2, k, NY);
             acc += Yh[i + n * t] * dr[k2];
         }
         W[k * n + i + ld * j] = acc;

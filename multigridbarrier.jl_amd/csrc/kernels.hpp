@@ -2,11 +2,9 @@
 #pragma once
 #include "common.hpp"
 #include "cone.hpp"
+#include "elem_layout.hpp"   // ElemMode, elem_group, WIDE_F2_THREADS, the LDS layout of the element kernels
 
 namespace mgbhip {
-
-enum ElemMode { MODE_F0 = 0, MODE_F1 = 1, MODE_F2 = 2, MODE_NODE_F = 3, MODE_NODE_SLACK = 4,
-                MODE_F01 = 5 };   // MODE_F01: value and gradient of one line-search trial in ONE pass over the operators
 
 // Where the leaf front of an element lives and how its boundary is ordered (built by MfSolver::enable_condensed).
 struct LeafDesc {
@@ -85,13 +83,11 @@ inline int64_t hel_layout(int nu, int64_t N, int p, int diag_mask, int64_t* off)
     return total;
 }
 
-int elem_group(int p);                                   // lanes per element (power of two >= p)
-// wide path: threads per workgroup of the element Hessian kernel (the other modes run 256, like the narrow kernels, so
-// that f0's workgroup partials keep their count elem_grid(p, N)) and the LDS it needs
-constexpr int WIDE_F2_THREADS = 128;
-size_t wide_lds_bytes(int p, int nu, int nD, int nstage, int mode);
 int64_t elem_grid(int p, int64_t N);                     // workgroups
-size_t elem_lds_bytes(const ElemParams& P, int mode);
+// dynamic LDS of a generic launch (elem_layout.hpp: one layout for every element kernel, narrow and wide)
+inline size_t elem_lds_bytes(const ElemParams& P, int mode) {
+    return elem_lds_bytes(elem_threads(P.wide != 0, mode), P.p, P.nu, P.nD, P.nstage, mode);
+}
 void launch_elem(const ElemParams& P, int mode, hipStream_t st);
 
 // deterministic two-stage reductions into a device scalar block

@@ -143,7 +143,7 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         }
         P->store->w.upload(d->w, (size_t)P->n, st);
     }
-    // wide path (kernels.hip: elem_wide_kernel): chosen once here, from the D rows and the piece widths
+    // wide path (elem_kernels.hpp: elem_wide_kernel): chosen once here, from the D rows and the piece widths
     P->wide = d->nD > 10;
     for (int k = 0; k < d->cone.npieces && k < MGBHIP_MAX_PIECES; ++k)
         if (d->cone.pieces[k].kind == MGBHIP_KIND_EP && d->cone.pieces[k].ni > NARROW_W) P->wide = true;
@@ -151,8 +151,6 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
     P->nstage = 0;
     int slot_of_op[MGBHIP_MAX_OPS];
     for (int o = 0; o < MGBHIP_MAX_OPS; ++o) slot_of_op[o] = -1;
-    const int G = elem_group(P->p);
-    const int EPB = P->dense ? 1 : 256 / G;
     for (int k = 0; k < d->nD; ++k) {
         MGB_REQUIRE(d->D_state[k] >= 0 && d->D_state[k] < d->nu, "D row references a missing state variable");
         MGB_REQUIRE(d->D_op[k] >= 0 && d->D_op[k] < d->n_ops, "D row references a missing operator");
@@ -161,14 +159,9 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         const int o = d->D_op[k];
         if (P->store->identity[o]) { P->D_stage[k] = -1; continue; }
         if (slot_of_op[o] < 0) {
-            // stage through LDS while the operator tiles of one workgroup stay under 64 KB
-            // ... and the whole f2 working set (operators + broken values + nD(nD+1)/2 node weights
-            // per lane) fits the 160 KB of a CU
-            size_t bytes = (size_t)(P->nstage + 1) * EPB * P->p * P->p * sizeof(double);
-            size_t f2_total = bytes + 256 * sizeof(double) * (size_t)(d->nu + d->nD * (d->nD + 1) / 2);
-            if (P->wide)    // the wide Hessian kernel runs WIDE_F2_THREADS lanes per workgroup
-                f2_total = wide_lds_bytes(P->p, d->nu, d->nD, P->nstage + 1, MODE_F2);
-            if (!P->dense && bytes <= 64 * 1024 && f2_total <= 150 * 1024) {
+            // stage through LDS while the operator tiles of one workgroup and the whole f2 working set (operators + broken
+            // values + nD(nD+1)/2 node weights per lane) fit: elem_layout.hpp, elem_stage_fits
+            if (!P->dense && elem_stage_fits(P->p, d->nu, d->nD, P->nstage + 1, P->wide)) {
                 slot_of_op[o] = P->nstage;
                 P->stage_ptr[P->nstage++] = P->store->ops[o].p;
             } else {

@@ -1,0 +1,339 @@
+// reduce_kernels.hpp -- compensated sums, reductions and the finishing launches (included by kernels.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+
+namespace mgbhip {
+
+namespace {
+
+// ---- compensated sums --------------------------------------------------------------------------
+// The coarse-level sums run over every element of the mesh, and near the end of a barrier solve one node's term can
+// exceed the rest by sixteen orders of magnitude (an iterate 1e-13 from the cone's wall: Hessian entries ~ 1e16, soft
+// eigenvalues ~ 1e1).  A plain running sum then loses the other 10^5 terms below the ulp of the large one -- an
+// absolute error of hundreds in a matrix whose smallest eigenvalue is 34: H comes out indefinite by summation
+// noise alone (tests/dev/logs/gpu_coarse_noise_probe_L8_p1.5.txt).  TwoSum accumulation (Knuth) carries the rounding
+// error of every addition in a second word: the sum is the correctly rounded one to a few ulps, whatever the order.
+// Used by the gather_assemble_* kernels and the long-row restrictions.  (At cond(H) ~ 1e15 the sign of lambda^2 also
+// depends on the rounding of the per-node terms themselves, which no summation scheme removes: DESIGN.md section 5.)
+struct DSum {
+    double s = 0.0, c = 0.0;
+    __device__ __forceinline__ void add(double x) {
+#ifdef MGB_PLAIN_SUMS
+        s += x;
+        return;
+#endif
+        const double t = s + x;
+        const double bp = t - s;
+        c += (s - (t - bp)) + (x - bp);
+        s = t;
+    }
+    __device__ __forceinline__ void merge(double s2, double c2) { add(s2); c += c2; }
+    __device__ __forceinline__ double value() const { return s + c; }
+};
+__device__ __forceinline__ void dsum_wave_reduce(DSum& a) {      // fixed shuffle tree over the 64 lanes; result in lane 0
+    for (int off = 32; off > 0; off >>= 1) {
+        const double s2 = __shfl_down(a.s, off, 64), c2 = __shfl_down(a.c, off, 64);
+        a.merge(s2, c2);
+    }
+}
+
+// ---- reductions ------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const double* __restrict__ partials, int64_t count,
+                                                              double* __restrict__ out) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int64_t i = tid; i < count; i += 256) s += partials[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) red[tid] += red[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = red[0];
+}
+
+// MODE 0: sum a*b ; MODE 1: sum a*a and count of non-finite a
+template <int MODE>
+__global__ __launch_bounds__(256) void block_reduce_kernel(const double* __restrict__ a, const double* __restrict__ b,
+                                                           int64_t n, double* __restrict__ partials,
+                                                           const double* __restrict__ mask) {
+    __shared__ double red[256];
+    __shared__ double red2[256];
+    const int tid = threadIdx.x;
+    double s = 0.0, bad = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += (int64_t)gridDim.x * 256) {
+        const double v = a[i];
+        const double w = mask ? mask[i] : 1.0;       // domain decomposition: 1 on the entries this rank owns, else 0
+        if (MODE == 0) s += mask ? w * (v * b[i]) : v * b[i];
+        else {
+            s += mask ? w * (v * v) : v * v;
+            bad += isfinite(v) ? 0.0 : 1.0;
+        }
+    }
+    red[tid] = s;
+    red2[tid] = bad;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) { red[tid] += red[tid + off]; red2[tid] += red2[tid + off]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        partials[blockIdx.x] = red[0];
+        if (MODE == 1) partials[gridDim.x + blockIdx.x] = red2[0];
+    }
+}
+
+// Line-search trial, everything behind the element kernel in ONE launch: the restriction g = R' ret (row gather, as
+// csr_matvec_row_kernel), the partial sums of |g|^2 and its non-finite count (the same grid-stride order and LDS tree as
+// block_reduce_kernel<1>: identical partials), and the step kernel's work -- xn = x - s n with its own fused multiply-add and
+// the "moved" stamp.  Three launches fewer per trial than restrict + block_reduce + step.
+__global__ __launch_bounds__(256) void restrict_trial_kernel(int64_t rows, const int32_t* __restrict__ ptr, const int32_t* __restrict__ col,
+                                                             const double* __restrict__ val, const double* __restrict__ ret,
+                                                             double* __restrict__ g, double* __restrict__ partials,
+                                                             const double* __restrict__ x, const double* __restrict__ nn, double s,
+                                                             double* __restrict__ xn, int32_t* __restrict__ moved, int32_t stamp) {
+    __shared__ double red[256];
+    __shared__ double red2[256];
+    __shared__ int any_moved;
+    const int tid = threadIdx.x;
+    if (tid == 0) any_moved = 0;
+    __syncthreads();
+    double ss = 0.0, bad = 0.0;
+    bool m = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < rows; i += (int64_t)gridDim.x * 256) {
+        double acc = 0.0;
+        for (int32_t q = ptr[i]; q < ptr[i + 1]; ++q) acc += val[q] * ret[col[q]];
+        g[i] = acc;
+        ss += acc * acc;
+        bad += isfinite(acc) ? 0.0 : 1.0;
+        if (xn) {
+            const double xi = x[i];
+            const double v = __builtin_fma(-s, nn[i], xi);
+            xn[i] = v;
+            m = m || (v != xi);
+        }
+    }
+    red[tid] = ss;
+    red2[tid] = bad;
+    if (m) any_moved = 1;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) { red[tid] += red[tid + off]; red2[tid] += red2[tid + off]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        partials[blockIdx.x] = red[0];
+        partials[gridDim.x + blockIdx.x] = red2[0];
+        if (any_moved) *moved = stamp;
+    }
+}
+
+// Newton direction statistics in one pass: sum v*v, count of non-finite v, and g.v (the same per-block partial sums
+// and trees as block_reduce_kernel<1> and <0>: identical values, two launches fewer per Newton iteration)
+__global__ __launch_bounds__(256) void dir_stats_kernel(const double* __restrict__ v, const double* __restrict__ g, int64_t n,
+                                                        double* __restrict__ partials, const double* __restrict__ mask) {
+    __shared__ double red[3][256];
+    const int tid = threadIdx.x;
+    double s = 0.0, bad = 0.0, d = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += (int64_t)gridDim.x * 256) {
+        const double x = v[i];
+        const double w = mask ? mask[i] : 1.0;
+        s += mask ? w * (x * x) : x * x;
+        bad += isfinite(x) ? 0.0 : 1.0;
+        d += mask ? w * (g[i] * x) : g[i] * x;
+    }
+    red[0][tid] = s; red[1][tid] = bad; red[2][tid] = d;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) {
+            red[0][tid] += red[0][tid + off];
+            red[1][tid] += red[1][tid + off];
+            red[2][tid] += red[2][tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        partials[blockIdx.x] = red[0][0];
+        partials[gridDim.x + blockIdx.x] = red[1][0];
+        partials[2 * gridDim.x + blockIdx.x] = red[2][0];
+    }
+}
+
+// Second stage of every two-stage reduction, ONE launch for everything the host wants from one synchronisation:
+// up to four strided sums (each: 256 threads stride over the partials + the same LDS tree as before, so the values
+// are bit for bit those of the separate reduce_partials / reduce2 launches this replaces), device flags that ride
+// behind the sums as doubles (a pivot status, the step kernel's "moved" stamp; `reset` clears them for their next
+// producer: no hipMemsetAsync per Newton iteration), and a copy of out[host_lo .. host_lo + host_n) straight into
+// the pinned host block (host-coherent memory: visible after the stream synchronises; no copy launch).
+struct FinishJob { const double* src; int64_t count; int32_t out; };
+struct FinishParams {
+    FinishJob job[4];
+    int32_t njobs;
+    double* out;
+    int32_t* ints;
+    int32_t nints, ints_out, reset;
+    double* host;
+    int32_t host_lo, host_n;
+    double seq;                  // != 0: written to host[15] after the results (system-scope fence in between): the host polls it
+};
+__global__ __launch_bounds__(256) void finish_kernel(const FinishParams P) {
+    __shared__ double red[256];
+    __shared__ double res[16];
+    const int tid = threadIdx.x;
+    if (tid < P.nints) {
+        res[P.ints_out + tid] = (double)P.ints[tid];
+        if (P.reset) P.ints[tid] = 0;
+    }
+    for (int o = 0; o < P.njobs; ++o) {
+        const double* __restrict__ src = P.job[o].src;
+        const int64_t cnt = P.job[o].count;
+        double s = 0.0;
+        for (int64_t i = tid; i < cnt; i += 256) s += src[i];
+        red[tid] = s;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if (tid < off) red[tid] += red[tid + off];
+            __syncthreads();
+        }
+        if (tid == 0) res[P.job[o].out] = red[0];
+        __syncthreads();
+    }
+    __syncthreads();
+    // results -> device scalar block (every slot this launch produced) and -> host
+    if (tid < 16) {
+        bool mine = false;
+        for (int o = 0; o < P.njobs; ++o) mine = mine || (P.job[o].out == tid);
+        if (tid >= P.ints_out && tid < P.ints_out + P.nints) mine = true;
+        if (mine) P.out[tid] = res[tid];
+        if (P.host && tid >= P.host_lo && tid < P.host_lo + P.host_n) P.host[tid] = mine ? res[tid] : P.out[tid];
+    }
+    if (P.host && P.seq != 0.0) {
+        __threadfence_system();                      // this thread's result stores are visible to the host ...
+        __syncthreads();                             // ... for every writing thread, before the stamp
+        if (tid == 0) {
+            __hip_atomic_store(P.host + 15, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+}  // namespace
+
+void launch_reduce_partials(const double* partials, int64_t count, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, partials, count, out);
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
+static int reduce_blocks(int64_t n);      // workgroups of a vector reduction: kernels.hip (the gate tests read its cap from there)
+
+int64_t reduce_scratch_doubles(int64_t n) { return 3 * (int64_t)reduce_blocks(n); }
+
+static void launch_finish(const FinishParams& F, hipStream_t st) {
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, F);
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
+void launch_vec_stats(const double* v, int64_t n, double* scratch, double* stats, hipStream_t st, const double* mask,
+                      const int32_t* ints, int nints) {
+    const int nb = reduce_blocks(n);
+    hipLaunchKernelGGL(block_reduce_kernel<1>, dim3(nb), dim3(256), 0, st, v, (const double*)nullptr, n, scratch, mask);
+    FinishParams F{};
+    F.job[0] = FinishJob{scratch, nb, 0};
+    F.job[1] = FinishJob{scratch + nb, nb, 1};
+    F.njobs = 2;
+    F.out = stats;
+    F.ints = const_cast<int32_t*>(ints); F.nints = nints; F.ints_out = 2; F.reset = 0;
+    launch_finish(F, st);
+}
+
+void launch_dir_stats(const double* v, const double* g, int64_t n, double* scratch, double* stats3, hipStream_t st,
+                      const double* mask, const int32_t* ints, int nints) {
+    const int nb = reduce_blocks(n);
+    hipLaunchKernelGGL(dir_stats_kernel, dim3(nb), dim3(256), 0, st, v, g, n, scratch, mask);
+    FinishParams F{};
+    F.job[0] = FinishJob{scratch, nb, 0};
+    F.job[1] = FinishJob{scratch + nb, nb, 1};
+    F.job[2] = FinishJob{scratch + 2 * nb, nb, 2};
+    F.njobs = 3;
+    F.out = stats3;
+    F.ints = const_cast<int32_t*>(ints); F.nints = nints; F.ints_out = 3; F.reset = 0;
+    launch_finish(F, st);
+}
+
+// The Newton direction's read-back in one finishing launch: scal[2] = sum v^2, scal[3] = non-finite count, scal[4] = g.v,
+// scal[5], scal[6] = the solver's status flags (read AND cleared: the next factorization / condensing f2 finds them zero
+// without a memset launch); scal[2..7) also lands in the pinned host block `host` (same indices).
+// n <= 16 scalars of the device block to the pinned host block (through its device pointer) with the sequence stamp behind
+// them: what a hipMemcpyAsync + hipStreamSynchronize pair did with a runtime copy kernel (11 us) and the runtime's wait.
+__global__ void publish_kernel(const double* __restrict__ src, int n, double* __restrict__ host, double* __restrict__ stamp, double seq) {
+    const int tid = threadIdx.x;
+    if (tid < n) host[tid] = src[tid];
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(stamp, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+void launch_publish(const double* src, int n, double* host_block, int host_lo, double seq, hipStream_t st) {
+    // host_block: device pointer of the 16-double pinned block; the stamp always goes to its slot 15
+    hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, st, src, n, host_block + host_lo, host_block + 15, seq);
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
+void launch_dir_finish(const double* v, const double* g, int64_t n, double* scratch, double* scal, int32_t* status2, double* host,
+                       hipStream_t st, const double* mask, double seq) {
+    const int nb = reduce_blocks(n);
+    hipLaunchKernelGGL(dir_stats_kernel, dim3(nb), dim3(256), 0, st, v, g, n, scratch, mask);
+    FinishParams F{};
+    F.job[0] = FinishJob{scratch, nb, 2};
+    F.job[1] = FinishJob{scratch + nb, nb, 3};
+    F.job[2] = FinishJob{scratch + 2 * nb, nb, 4};
+    F.njobs = 3;
+    F.out = scal;
+    F.ints = status2; F.nints = 2; F.ints_out = 5; F.reset = 1;
+    F.host = host; F.host_lo = 2; F.host_n = 5;
+    F.seq = seq;
+    launch_finish(F, st);
+}
+
+// One line-search trial's read-back: scal[0] = f0 (sum of the element kernel's workgroup partials), scal[2] = |g|^2,
+// scal[3] = non-finite count of g, scal[4] = the step kernel's "moved" stamp; scal[0..5) -> host.
+void launch_trial_finish(const double* g, int64_t n, double* scratch, const double* f0_partials, int64_t f0_count, double* scal,
+                         int32_t* moved, double* host, hipStream_t st, const double* mask, double seq, bool partials_ready) {
+    const int nb = reduce_blocks(n);
+    if (!partials_ready) hipLaunchKernelGGL(block_reduce_kernel<1>, dim3(nb), dim3(256), 0, st, g, (const double*)nullptr, n, scratch, mask);
+    FinishParams F{};
+    int nj = 0;
+    if (f0_partials) F.job[nj++] = FinishJob{f0_partials, f0_count, 0};
+    F.job[nj++] = FinishJob{scratch, nb, 2};
+    F.job[nj++] = FinishJob{scratch + nb, nb, 3};
+    F.njobs = nj;
+    F.out = scal;
+    F.ints = moved; F.nints = 1; F.ints_out = 4; F.reset = 0;
+    F.host = host; F.host_lo = 0; F.host_n = 5;
+    F.seq = seq;
+    launch_finish(F, st);
+}
+
+void launch_dot(const double* a, const double* b, int64_t n, double* scratch, double* out, hipStream_t st, const double* mask) {
+    const int nb = reduce_blocks(n);
+    hipLaunchKernelGGL(block_reduce_kernel<0>, dim3(nb), dim3(256), 0, st, a, b, n, scratch, mask);
+    FinishParams F{};
+    F.job[0] = FinishJob{scratch, nb, 0};
+    F.njobs = 1;
+    F.out = out;
+    launch_finish(F, st);
+}
+
+void launch_restrict_trial(int64_t rows, const int32_t* ptr, const int32_t* col, const double* val, const double* ret, double* g,
+                            double* scratch, const double* x, const double* nn, double s, double* xn, int32_t* moved, int32_t stamp,
+                            hipStream_t st) {
+    if (rows == 0) return;
+    const int nb = reduce_blocks(rows);                      // the partial-sum layout launch_trial_finish reads
+    hipLaunchKernelGGL(restrict_trial_kernel, dim3(nb), dim3(256), 0, st, rows, ptr, col, val, ret, g, scratch, x, nn, s, xn, moved, stamp);
+    MGB_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace mgbhip

@@ -1,6 +1,6 @@
-"""Compare the device code of two builds of csrc/mf_numeric.hip kernel by kernel: register counts, LDS, scratch and the
-instruction streams (label numbers normalised).  Inputs are the assembly listings of
-    hipcc $(CXXFLAGS of csrc/Makefile) --cuda-device-only -S mf_numeric.hip -o X.s
+"""Compare the device code of two builds of one .hip file of csrc/ (mf_numeric.hip, kernels.hip, dense.hip, ...) kernel by
+kernel: register counts, LDS, scratch and the instruction streams (label numbers normalised).  Inputs are the listings of
+    hipcc $(CXXFLAGS of csrc/Makefile) --cuda-device-only -S FILE.hip -o X.s
 Usage: python tools/mf_isa_diff.py OLD.s NEW.s  (exit status 1 on any difference)."""
 import re
 import sys
