@@ -283,6 +283,26 @@ int mgbhip_solver_chain(mgbhip_problem* prob, int32_t level, double* out8);
  * [4]..[10], [13] and [14] describe it and are zero / defaults before).                                                   */
 enum { MGBHIP_PROJ_NONE = 0, MGBHIP_PROJ_LOOP = 1, MGBHIP_PROJ_STAGED = 2, MGBHIP_PROJ_MFMA = 3, MGBHIP_PROJ_ACCUMULATE = 4 };
 int mgbhip_level_plan(mgbhip_problem* prob, int32_t level, int32_t* out16);
+/* Which element kernel a launch of `mode` (MGBHIP_ELEM_F0 .. MGBHIP_ELEM_F01) runs on this problem (inspection only; nothing is
+ * launched).  The decision is the launchers' own (csrc/elem_layout.hpp, elem_decide).  out[0] kernel kind (MGBHIP_ELEM_KIND_*) of
+ * the plain launch, [1] NY and [2] P of the instantiation (fast kernels: the compile-time pair; generic: NY = nD, P = 0; wide and
+ * dense: 0, 0), [3] threads per workgroup, [4] lanes per element G, [5] elements per workgroup, [6] workgroups, [7] dynamic LDS
+ * bytes ([3]..[7] are 0 on the dense path, which sizes its own launches), [8] operators staged through LDS, [9] D rows whose
+ * operator is read from HBM, [10] ymask (bit k: row k of D z enters a barrier term), [11] kind of the Hessian launch of the
+ * Newton loop on the finest level: MGBHIP_ELEM_KIND_CONDENSE once that level has condensed leaves and mode is MGBHIP_ELEM_F2,
+ * otherwise [0]; [12]..[15] reserved (0).                                                                              */
+enum { MGBHIP_ELEM_F0 = 0, MGBHIP_ELEM_F1 = 1, MGBHIP_ELEM_F2 = 2, MGBHIP_ELEM_NODE_F = 3, MGBHIP_ELEM_NODE_SLACK = 4, MGBHIP_ELEM_F01 = 5 };
+enum { MGBHIP_ELEM_KIND_DENSE = 0, MGBHIP_ELEM_KIND_WIDE = 1, MGBHIP_ELEM_KIND_FAST_DEFAULT = 2, MGBHIP_ELEM_KIND_FAST_RUNTIME = 3,
+       MGBHIP_ELEM_KIND_CONDENSE = 4, MGBHIP_ELEM_KIND_GENERIC = 5 };
+int mgbhip_elem_plan(mgbhip_problem* prob, int32_t mode, int32_t* out16);
+/* Test and diagnostic entry point: ONE line-search trial of the Newton loop at level `level`, run by the loop's own code.
+ * x and dir (m_level each) are the iterate and the direction, the trial point is x - step * dir; c (n x nD, column-major) and
+ * z0 (nu * n) as in mgbhip_f0.  y: the objective at the trial point, g (m_level): its gradient, xn (m_level): the trial point as
+ * the device formed it, moved: 0 when no entry of x changed, finite: 0 when the loop would reject the trial (non-finite value or
+ * gradient; y, g are then whatever the kernels left), path: bit 0 the element kernel formed the trial point on the fly, bit 1 the
+ * restriction, the |g|^2 partial sums and the step ran in one launch.  Valid without any earlier solve.  Not for sharded problems. */
+int mgbhip_trial_values(mgbhip_problem* prob, int32_t level, const double* x, const double* dir, double step, const double* c,
+                        const double* z0, double* y, double* g, double* xn, int32_t* moved, int32_t* finite, int32_t* path);
 /* The factorization launches of a level's sparse LDL', leaves first (inspection only, valid after the level's first solve;
  * nothing is computed or changed).  Returns the number of launches, or -status on an error, and writes at most `cap` rows of
  * MGBHIP_LAUNCH_ROW int32 to out (out may be NULL with cap = 0):  [0] tree level, [1] first front, [2] fronts, [3] LDS class

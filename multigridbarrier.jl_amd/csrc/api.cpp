@@ -23,6 +23,7 @@ using namespace mgbhip;
 mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mgbhip_problem* share);
 int core_run(mgbhip_problem* P, double* z, const double* c, const mgbhip_options* opt, mgbhip_core_result* res);
 int matched_t_run(mgbhip_problem* P, const double* z, const double* c, double t_default, double* t_out);
+void trial_values_run(mgbhip_problem* P, int level, double step, double* y, int32_t* moved, int32_t* finite, int32_t* path);
 
 #ifdef MGB_STEP_PROBE
 namespace mgbhip { void mf_debug_probe(long long* out64); }
@@ -241,6 +242,28 @@ int mgbhip_level_plan(mgbhip_problem* P, int32_t level, int32_t* out) {
     MGB_API_END
 }
 
+static_assert(MGBHIP_ELEM_F0 == MODE_F0 && MGBHIP_ELEM_F1 == MODE_F1 && MGBHIP_ELEM_F2 == MODE_F2 && MGBHIP_ELEM_NODE_F == MODE_NODE_F &&
+              MGBHIP_ELEM_NODE_SLACK == MODE_NODE_SLACK && MGBHIP_ELEM_F01 == MODE_F01, "mgbhip.h mirrors ElemMode");
+static_assert(MGBHIP_ELEM_KIND_DENSE == ELEM_DENSE && MGBHIP_ELEM_KIND_WIDE == ELEM_WIDE && MGBHIP_ELEM_KIND_FAST_DEFAULT == ELEM_FAST_DEFAULT &&
+              MGBHIP_ELEM_KIND_FAST_RUNTIME == ELEM_FAST_RUNTIME && MGBHIP_ELEM_KIND_CONDENSE == ELEM_CONDENSE &&
+              MGBHIP_ELEM_KIND_GENERIC == ELEM_GENERIC, "mgbhip.h mirrors ElemKind");
+
+int mgbhip_elem_plan(mgbhip_problem* P, int32_t mode, int32_t* out) {
+    MGB_API_BEGIN
+    MGB_REQUIRE(P != nullptr && out != nullptr, "null argument");
+    MGB_REQUIRE(mode >= MODE_F0 && mode <= MODE_F01, "elem_plan: bad mode");
+    const ElemParams E = P->base_params(-1, nullptr, nullptr, nullptr);      // level -1: nothing is launched or cached
+    const ElemPlan plan = elem_plan_of(E, mode, false);
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = plan.kind; out[1] = plan.NY; out[2] = plan.P; out[3] = plan.threads; out[4] = plan.G; out[5] = plan.EPB;
+    out[6] = (int32_t)plan.grid; out[7] = (int32_t)plan.lds;
+    out[8] = E.nstage; out[9] = elem_unstaged_rows(E); out[10] = E.ymask;
+    out[11] = plan.kind;
+    if (mode == MODE_F2 && !P->levels.empty() && P->levels.back().condense) out[11] = elem_plan_of(E, mode, true).kind;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
 static void stage_inputs(mgbhip_problem* P, int32_t level, const double* s, const double* c, const double* z0) {
     hipStream_t st = P->stream();
     P->d_x.upload(s, (size_t)P->levels[level].m, st);
@@ -406,6 +429,24 @@ int mgbhip_newton_direction(mgbhip_problem* P, int32_t level, const double* s, c
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     if (status != MGBHIP_OK) g_last_error = "Cholesky met a non-positive pivot";
     return status;
+    MGB_API_END
+}
+
+int mgbhip_trial_values(mgbhip_problem* P, int32_t level, const double* x, const double* dir, double step, const double* c,
+                        const double* z0, double* y, double* g, double* xn, int32_t* moved, int32_t* finite, int32_t* path) {
+    MGB_API_BEGIN_ON(P)
+    check_level(P, level);
+    MGB_REQUIRE(x && dir && c && z0 && y && g && xn && moved && finite && path, "null argument");
+    MGB_REQUIRE(!P->sharded(), "trial_values: not for sharded problems");
+    hipStream_t st = P->stream();
+    const size_t m = (size_t)P->levels[level].m;
+    stage_inputs(P, level, x, c, z0);                  // d_x, d_c, d_z0 (the workspace of problem_create holds every level), touch()
+    P->d_nv.upload(dir, m, st);
+    trial_values_run(P, level, step, y, moved, finite, path);
+    P->d_gn.download(g, m, st);
+    P->d_xn.download(xn, m, st);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+    return MGBHIP_OK;
     MGB_API_END
 }
 

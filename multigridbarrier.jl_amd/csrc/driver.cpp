@@ -398,6 +398,16 @@ bool slack_feasible(mgbhip_problem* P, std::vector<double>& hbuf) {
 
 }  // namespace
 
+// mgbhip_trial_values: one trial of linesearch_backtracking at x = d_x, direction d_nv, snapshot d_z0, cost d_c.
+void trial_values_run(mgbhip_problem* P, int level, double step, double* y, int32_t* moved, int32_t* finite, int32_t* path) {
+    NewtonCtx C{P, level, P->d_z0.p, P->d_c.p, P->levels[level].m};
+    double yn = 0.0, gn = 0.0;
+    const bool onfly = P->can_fuse_step(level);
+    *finite = trial_values(C, yn, gn, moved, &step) ? 1 : 0;
+    *y = yn;
+    *path = (onfly ? 1 : 0) | (P->trial_fuse.done ? 2 : 0);
+}
+
 int core_run(mgbhip_problem* P, double* z, const double* c, const mgbhip_options* optp, mgbhip_core_result* res) {
     const mgbhip_options opt = *optp;
     hipStream_t st = P->stream();

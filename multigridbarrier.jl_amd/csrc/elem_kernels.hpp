@@ -1,6 +1,7 @@
 // elem_kernels.hpp -- element evaluation kernels and launch_elem (included by kernels.hip).
 #pragma once
 #include <mutex>
+#include <utility>
 
 #include "dense.hpp"
 #include "elem_device.hpp"
@@ -855,28 +856,11 @@ int64_t elem_grid(int p, int64_t N) {
     return (N + epb - 1) / epb;
 }
 
-template <int NY>
-static bool is_default_signature(const ElemParams& P) {
-    if (P.nu != 2 || P.nD != NY || P.ymask != (((1 << NY) - 1) & ~1)) return false;
-    for (int k = 0; k < NY; ++k) {
-        if (P.D_state[k] != (k == NY - 1 ? 1 : 0)) return false;
-        if (P.D_stage[k] != ((k == 0 || k == NY - 1) ? -1 : k - 1)) return false;
-    }
-    return true;
-}
-
-static bool all_ops_staged(const ElemParams& P) {        // else: generic path (it reads unstaged operators from HBM)
-    for (int k = 0; k < P.nD; ++k)
-        if (P.D_stage[k] == -2) return false;
-    return true;
-}
-
-// The fast kernels of one (NY, PN) and mode: KD / KR are the default- and the runtime-signature instantiation.
-template <int NY, int PN, auto KD, auto KR>
-static bool try_fast(const ElemParams& P, int mode, hipStream_t st) {
-    if (P.nD != NY || P.p != PN || !all_ops_staged(P)) return false;
-    const size_t lds = elem_lds_bytes(256, PN, P.nu, NY, P.nstage, mode);
-    if (lds > ELEM_LDS_MAX) return false;
+// The fast kernels of entry I of ELEM_FAST_TABLE for one mode: KD / KR are the default- and the runtime-signature
+// instantiation.  Launches when the plan names this entry.
+template <int I, auto KD, auto KR>
+static bool launch_fast_entry(const ElemParams& P, const ElemPlan& plan, hipStream_t st) {
+    if (plan.NY != ELEM_FAST_TABLE[I][0] || plan.P != ELEM_FAST_TABLE[I][1]) return false;
     static bool attr = [] {
         allow_big_lds(KR);
         allow_big_lds(KD);
@@ -884,32 +868,37 @@ static bool try_fast(const ElemParams& P, int mode, hipStream_t st) {
         return true;
     }();
     (void)attr;
-    hipLaunchKernelGGL(is_default_signature<NY>(P) ? KD : KR, dim3((unsigned)elem_grid(PN, P.N)), dim3(256), lds, st, P);
+    hipLaunchKernelGGL(plan.kind == ELEM_FAST_DEFAULT ? KD : KR, dim3((unsigned)plan.grid), dim3((unsigned)plan.threads), plan.lds, st, P);
     return true;
 }
-template <int NY, int PN>
-static bool try_f2_fast(const ElemParams& P, hipStream_t st) {
-    return try_fast<NY, PN, &elem_f2_fast<NY, PN, SigDefault<NY>>, &elem_f2_fast<NY, PN, SigRuntime>>(P, MODE_F2, st);
+template <int I>
+static bool launch_f2_fast_entry(const ElemParams& P, const ElemPlan& plan, hipStream_t st) {
+    constexpr int NY = ELEM_FAST_TABLE[I][0], PN = ELEM_FAST_TABLE[I][1];
+    return launch_fast_entry<I, &elem_f2_fast<NY, PN, SigDefault<NY>>, &elem_f2_fast<NY, PN, SigRuntime>>(P, plan, st);
 }
-template <int NY, int PN>
-static bool try_f01_fast(const ElemParams& P, hipStream_t st) {
-    return try_fast<NY, PN, &elem_f01_fast<NY, PN, SigDefault<NY>>, &elem_f01_fast<NY, PN, SigRuntime>>(P, MODE_F01, st);
+template <int I>
+static bool launch_f01_fast_entry(const ElemParams& P, const ElemPlan& plan, hipStream_t st) {
+    constexpr int NY = ELEM_FAST_TABLE[I][0], PN = ELEM_FAST_TABLE[I][1];
+    return launch_fast_entry<I, &elem_f01_fast<NY, PN, SigDefault<NY>>, &elem_f01_fast<NY, PN, SigRuntime>>(P, plan, st);
+}
+template <int... I>
+static bool launch_fast(const ElemParams& P, int mode, const ElemPlan& plan, hipStream_t st, std::integer_sequence<int, I...>) {
+    return mode == MODE_F2 ? (launch_f2_fast_entry<I>(P, plan, st) || ...) : (launch_f01_fast_entry<I>(P, plan, st) || ...);
 }
 
 bool launch_elem_f2_condense(const ElemParams& P, hipStream_t st) {
     // fem2d_P2 with bubble, default D table: 7 nodes per element, node 6 interior (the only family specialised so far)
-    constexpr int NY = 4, PN = 7;
-    if (P.wide || P.nD != NY || P.p != PN || P.nu != 2 || P.nstage != 2 || !is_default_signature<NY>(P)) return false;
-    if (!all_ops_staged(P)) return false;
+    constexpr int NY = ELEM_CONDENSE_NY, PN = ELEM_CONDENSE_P;
+    const ElemPlan plan = elem_plan_of(P, MODE_F2, true);
+    if (plan.kind != ELEM_CONDENSE) return false;
     MGB_REQUIRE(P.leaf_desc && P.leaf_arena && P.leaf_g && P.leaf_status, "condensing f2: leaf arguments missing");
-    const size_t lds = elem_lds_bytes(256, PN, P.nu, NY, P.nstage, MODE_F2);
     static bool attr = [] {
         allow_big_lds(elem_f2_fast<NY, PN, SigDefault<NY>, true>);
         (void)hipGetLastError();
         return true;
     }();
     (void)attr;
-    hipLaunchKernelGGL((elem_f2_fast<NY, PN, SigDefault<NY>, true>), dim3((unsigned)elem_grid(PN, P.N)), dim3(256), lds, st, P);
+    hipLaunchKernelGGL((elem_f2_fast<NY, PN, SigDefault<NY>, true>), dim3((unsigned)plan.grid), dim3((unsigned)plan.threads), plan.lds, st, P);
     MGB_HIP_CHECK(hipGetLastError());
     return true;
 }
@@ -917,70 +906,57 @@ bool launch_elem_f2_condense(const ElemParams& P, hipStream_t st) {
 // Generic kernels, narrow and wide: kernel_of(M) is the MODE instantiation of the kernel template for
 // M = std::integral_constant<int, MODE_*> -- the one list of modes serves the launch and the LDS opt-in.
 template <class K>
-static void launch_elem_generic(const ElemParams& P, int mode, K kernel_of, hipStream_t st) {
+static void launch_elem_generic(const ElemParams& P, int mode, const ElemPlan& plan, K kernel_of, hipStream_t st) {
     static std::once_flag once;
     std::call_once(once, [&] {
         for (int m = MODE_F0; m <= MODE_F01; ++m) dispatch_mode(m, [&](auto M) { allow_big_lds(kernel_of(M)); });
         (void)hipGetLastError();
     });
-    const int G = elem_group(P.p);
     int lgG = 0;
-    while ((1 << lgG) < G) ++lgG;
-    const int threads = elem_threads(P.wide != 0, mode);
-    const int EPB = threads / G;
-    const dim3 grid((unsigned)((P.N + EPB - 1) / EPB)), blk((unsigned)threads);
-    const size_t lds = elem_lds_bytes(P, mode);
+    while ((1 << lgG) < plan.G) ++lgG;
+    const dim3 grid((unsigned)plan.grid), blk((unsigned)plan.threads);
+    const size_t lds = plan.lds;
     MGB_REQUIRE(lds <= ELEM_LDS_MAX, "element kernel LDS budget exceeded");
     if (!dispatch_mode(mode, [&](auto M) { hipLaunchKernelGGL(kernel_of(M), grid, blk, lds, st, P, lgG); }))
         throw InvalidArgument("launch_elem: bad mode");
     MGB_HIP_CHECK(hipGetLastError());
 }
 template <int NY>
-static void launch_elem_ny(const ElemParams& P, int mode, hipStream_t st) {
-    launch_elem_generic(P, mode, [](auto M) { return &elem_kernel<NY, decltype(M)::value>; }, st);
+static void launch_elem_ny(const ElemParams& P, int mode, const ElemPlan& plan, hipStream_t st) {
+    launch_elem_generic(P, mode, plan, [](auto M) { return &elem_kernel<NY, decltype(M)::value>; }, st);
 }
 
 void launch_elem(const ElemParams& P, int mode, hipStream_t st) {
-    if (P.p > 64) {      // one dense spectral element: GEMV + node kernel path (dense.hip)
+    const ElemPlan plan = elem_plan_of(P, mode, false);
+    if (plan.kind == ELEM_DENSE) {      // one dense spectral element: GEMV + node kernel path (dense.hip)
         launch_dense_eval(P, mode, st);
         return;
     }
     MGB_REQUIRE(P.p >= 1 && P.p <= 64, "element kernels support 1 <= p <= 64 nodes per element");
     MGB_REQUIRE(P.nD >= 1 && P.nD <= MGBHIP_MAX_ND, "nD out of range");
-    if (P.wide) {
-        launch_elem_generic(P, mode, [](auto M) { return &elem_wide_kernel<decltype(M)::value>; }, st);
+    if (plan.kind == ELEM_WIDE) {
+        launch_elem_generic(P, mode, plan, [](auto M) { return &elem_wide_kernel<decltype(M)::value>; }, st);
         return;
     }
     MGB_REQUIRE(P.nD <= 10, "narrow element kernels: nD out of range");
-    if (mode == MODE_F2) {
-        // compile-time specialisations for the discretisations of the BASELINE configs
-        // (fem1d, fem2d_P2 with/without bubble, fem3d Q1) and their phase-I images
-        if (try_f2_fast<4, 7>(P, st) || try_f2_fast<3, 2>(P, st) || try_f2_fast<5, 8>(P, st) ||
-            try_f2_fast<4, 6>(P, st) || try_f2_fast<7, 7>(P, st) || try_f2_fast<6, 2>(P, st) ||
-            try_f2_fast<8, 8>(P, st) || try_f2_fast<7, 6>(P, st)) {
-            MGB_HIP_CHECK(hipGetLastError());
-            return;
-        }
+    if (plan.kind == ELEM_FAST_DEFAULT || plan.kind == ELEM_FAST_RUNTIME) {
+        // compile-time specialisations (elem_layout.hpp: ELEM_FAST_TABLE)
+        const bool launched = launch_fast(P, mode, plan, st, std::make_integer_sequence<int, ELEM_FAST_COUNT>{});
+        MGB_REQUIRE(launched, "launch_elem: no fast kernel for the planned (NY, P)");
+        MGB_HIP_CHECK(hipGetLastError());
+        return;
     }
-    if (mode == MODE_F01) {
-        if (try_f01_fast<4, 7>(P, st) || try_f01_fast<3, 2>(P, st) || try_f01_fast<5, 8>(P, st) ||
-            try_f01_fast<4, 6>(P, st) || try_f01_fast<7, 7>(P, st) || try_f01_fast<6, 2>(P, st) ||
-            try_f01_fast<8, 8>(P, st) || try_f01_fast<7, 6>(P, st)) {
-            MGB_HIP_CHECK(hipGetLastError());
-            return;
-        }
-    }
-    switch (P.nD) {
-        case 1: launch_elem_ny<1>(P, mode, st); break;
-        case 2: launch_elem_ny<2>(P, mode, st); break;
-        case 3: launch_elem_ny<3>(P, mode, st); break;
-        case 4: launch_elem_ny<4>(P, mode, st); break;
-        case 5: launch_elem_ny<5>(P, mode, st); break;
-        case 6: launch_elem_ny<6>(P, mode, st); break;
-        case 7: launch_elem_ny<7>(P, mode, st); break;
-        case 8: launch_elem_ny<8>(P, mode, st); break;
-        case 9: launch_elem_ny<9>(P, mode, st); break;
-        case 10: launch_elem_ny<10>(P, mode, st); break;
+    switch (plan.NY) {
+        case 1: launch_elem_ny<1>(P, mode, plan, st); break;
+        case 2: launch_elem_ny<2>(P, mode, plan, st); break;
+        case 3: launch_elem_ny<3>(P, mode, plan, st); break;
+        case 4: launch_elem_ny<4>(P, mode, plan, st); break;
+        case 5: launch_elem_ny<5>(P, mode, plan, st); break;
+        case 6: launch_elem_ny<6>(P, mode, plan, st); break;
+        case 7: launch_elem_ny<7>(P, mode, plan, st); break;
+        case 8: launch_elem_ny<8>(P, mode, plan, st); break;
+        case 9: launch_elem_ny<9>(P, mode, plan, st); break;
+        case 10: launch_elem_ny<10>(P, mode, plan, st); break;
     }
 }
 

@@ -63,4 +63,49 @@ constexpr bool elem_stage_fits(int p, int nu, int nD, int nstage, bool wide) {
     return tiles <= 64 * 1024 && elem_lds_bytes(elem_threads(wide, MODE_F2), p, nu, nD, nstage, MODE_F2) <= 150 * 1024;
 }
 
+// ---- which kernel a launch runs ----------------------------------------------------------------------------------------
+// The one dispatch decision of the element family: launch_elem, launch_elem_f2_condense and the generic launchers run what
+// elem_decide returns, and mgbhip_elem_plan reports it read-only.
+enum ElemKind { ELEM_DENSE = 0, ELEM_WIDE = 1, ELEM_FAST_DEFAULT = 2, ELEM_FAST_RUNTIME = 3, ELEM_CONDENSE = 4, ELEM_GENERIC = 5 };
+
+// (NY, P) of the compile-time specialisations elem_f2_fast / elem_f01_fast, in the order they are tried: the
+// discretisations of the BASELINE configs (fem2d_P2 with bubble, fem1d, fem3d Q1, fem2d_P2 without bubble) and their
+// phase-I images.  Each exists for the default D-table signature (SigDefault<NY>) and for a runtime one.
+constexpr int ELEM_FAST_COUNT = 8;
+constexpr int ELEM_FAST_TABLE[ELEM_FAST_COUNT][2] = {{4, 7}, {3, 2}, {5, 8}, {4, 6}, {7, 7}, {6, 2}, {8, 8}, {7, 6}};
+constexpr int elem_fast_index(int NY, int P) {
+    for (int i = 0; i < ELEM_FAST_COUNT; ++i)
+        if (ELEM_FAST_TABLE[i][0] == NY && ELEM_FAST_TABLE[i][1] == P) return i;
+    return -1;
+}
+// the condensing f2 (elem_f2_fast<4, 7, SigDefault<4>, true>): fem2d_P2 with bubble, both operators staged
+constexpr int ELEM_CONDENSE_NY = 4, ELEM_CONDENSE_P = 7, ELEM_CONDENSE_NU = 2, ELEM_CONDENSE_NSTAGE = 2;
+
+struct ElemPlan {
+    int kind;            // ElemKind
+    int NY, P;           // the instantiation: (NY, P) of a fast kernel, (nD, 0) of elem_kernel<NY>, (0, 0) wide and dense
+    int threads, G, EPB; // workgroup size, lanes per element, elements per workgroup (0 on the dense path)
+    long long grid;      // workgroups (0 on the dense path: dense.hip sizes its own launches)
+    size_t lds;          // dynamic LDS bytes
+};
+
+// all_staged: no D row reads its operator from HBM (D_stage == -2).  default_sig: the D table and ymask are SigDefault<nD>'s.
+// condensing: the caller asks for the leaf-condensing f2; where it does not apply the plain decision for `mode` is returned.
+constexpr ElemPlan elem_decide(int p, int nu, int nD, int nstage, bool wide, bool dense, bool all_staged, bool default_sig,
+                               int mode, bool condensing, long long N) {
+    if (dense) return ElemPlan{ELEM_DENSE, 0, 0, 0, 0, 0, 0, 0};
+    const int threads = elem_threads(wide, mode);
+    const int G = elem_group(p);
+    const int EPB = threads / G;
+    const long long grid = (N + EPB - 1) / EPB;
+    const size_t lds = elem_lds_bytes(threads, p, nu, nD, nstage, mode);
+    if (wide) return ElemPlan{ELEM_WIDE, 0, 0, threads, G, EPB, grid, lds};
+    if (condensing && mode == MODE_F2 && nD == ELEM_CONDENSE_NY && p == ELEM_CONDENSE_P && nu == ELEM_CONDENSE_NU &&
+        nstage == ELEM_CONDENSE_NSTAGE && default_sig && all_staged)
+        return ElemPlan{ELEM_CONDENSE, nD, p, threads, G, EPB, grid, lds};
+    if ((mode == MODE_F2 || mode == MODE_F01) && elem_fast_index(nD, p) >= 0 && all_staged && lds <= ELEM_LDS_MAX)
+        return ElemPlan{default_sig ? ELEM_FAST_DEFAULT : ELEM_FAST_RUNTIME, nD, p, threads, G, EPB, grid, lds};
+    return ElemPlan{ELEM_GENERIC, nD, 0, threads, G, EPB, grid, lds};
+}
+
 }  // namespace mgbhip

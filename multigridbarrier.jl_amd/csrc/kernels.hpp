@@ -88,6 +88,26 @@ int64_t elem_grid(int p, int64_t N);                     // workgroups
 inline size_t elem_lds_bytes(const ElemParams& P, int mode) {
     return elem_lds_bytes(elem_threads(P.wide != 0, mode), P.p, P.nu, P.nD, P.nstage, mode);
 }
+// The D table and ymask are those of SigDefault<nD> (elem_kernels.hpp): [u id; u D_1; ...; s id], rows 1 .. nD-1 in the barrier.
+inline bool elem_default_signature(const ElemParams& P) {
+    const int NY = P.nD;
+    if (P.nu != 2 || P.ymask != (((1 << NY) - 1) & ~1)) return false;
+    for (int k = 0; k < NY; ++k) {
+        if (P.D_state[k] != (k == NY - 1 ? 1 : 0)) return false;
+        if (P.D_stage[k] != ((k == 0 || k == NY - 1) ? -1 : k - 1)) return false;
+    }
+    return true;
+}
+inline int elem_unstaged_rows(const ElemParams& P) {      // D rows whose operator is read from HBM (generic kernels only)
+    int cnt = 0;
+    for (int k = 0; k < P.nD; ++k) cnt += P.D_stage[k] == -2;
+    return cnt;
+}
+// What launch_elem (condensing = false) or launch_elem_f2_condense (true) runs for these parameters: elem_layout.hpp, elem_decide.
+inline ElemPlan elem_plan_of(const ElemParams& P, int mode, bool condensing) {
+    return elem_decide(P.p, P.nu, P.nD, P.nstage, P.wide != 0, P.p > 64, elem_unstaged_rows(P) == 0, elem_default_signature(P), mode,
+                       condensing, P.N);
+}
 void launch_elem(const ElemParams& P, int mode, hipStream_t st);
 
 // deterministic two-stage reductions into a device scalar block

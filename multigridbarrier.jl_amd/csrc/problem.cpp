@@ -286,6 +286,7 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         P->d_tchunk.alloc(2 * tch);            // (sum, carried error) per chunk
     }
     P->d_flag.alloc(4);
+    P->d_flag.zero(st);                    // the "moved" stamp of launch_step: no stamp of a later step may be there by chance
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     if (dbg2) fprintf(stderr, "[mgbhip] problem_create: done after %.3f s\n", since0());
     return P.release();

@@ -115,7 +115,7 @@ EXPORTS = [
     "mgbhip_vec_alloc", "mgbhip_vec_free", "mgbhip_vec_len", "mgbhip_vec_upload", "mgbhip_vec_download",
     "mgbhip_vec_fill", "mgbhip_vec_copy", "mgbhip_vec_axpy", "mgbhip_vec_scale", "mgbhip_vec_dot",
     "mgbhip_vec_norm", "mgbhip_vec_isfinite", "mgbhip_f0_d", "mgbhip_f1_d", "mgbhip_f2_d", "mgbhip_solve_d",
-    "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_solver_launches", "mgbhip_interpolate", "mgbhip_interpolate_grad",
+    "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_elem_plan", "mgbhip_trial_values", "mgbhip_solver_launches", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
     "mgbhip_tessellate_create", "mgbhip_tessellate_fetch", "mgbhip_tessellate_destroy",
@@ -178,6 +178,8 @@ def load_library():
     lib.mgbhip_solver_stats.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.mgbhip_solver_chain.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.mgbhip_level_plan.argtypes = [C.c_void_p, C.c_int32, _ip]
+    lib.mgbhip_elem_plan.argtypes = [C.c_void_p, C.c_int32, _ip]
+    lib.mgbhip_trial_values.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
     lib.mgbhip_solver_launches.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int64]
     lib.mgbhip_solver_launches.restype = C.c_int64
     vp = C.c_void_p
@@ -694,6 +696,34 @@ class DeviceProblem:
         for k in ("R_unit", "R_long", "T_long", "acc", "long_lists", "planned"):
             d[k] = bool(d[k])
         return d
+
+    ELEM_MODES = ("f0", "f1", "f2", "node_F", "node_slack", "f01")
+    ELEM_KINDS = ("dense", "wide", "fast_default", "fast_runtime", "condense", "generic")
+
+    def elem_plan(self, mode) -> dict:
+        """Which element kernel a launch of `mode` (a name of ELEM_MODES or its number) runs (`mgbhip_elem_plan`): read-only,
+        nothing is launched.  `kind` is the plain launch (f0 / f1 / f2 / node maps / the line-search trial f01), `newton_kind`
+        the Hessian launch of the Newton loop on the finest level ("condense" once that level has condensed leaves)."""
+        mode = self.ELEM_MODES.index(mode) if isinstance(mode, str) else int(mode)
+        out = (C.c_int32 * 16)()
+        _check(self.lib, self.lib.mgbhip_elem_plan(self.handle, mode, out))
+        keys = ("kind", "NY", "P", "threads", "G", "EPB", "grid", "lds", "nstage", "unstaged", "ymask", "newton_kind")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["kind"], d["newton_kind"] = self.ELEM_KINDS[d["kind"]], self.ELEM_KINDS[d["newton_kind"]]
+        return d
+
+    def trial_values(self, level: int, x, direction, step: float, c, z0) -> dict:
+        """One line-search trial of the Newton loop at x - step * direction, run by the loop's own code (`mgbhip_trial_values`,
+        a test and diagnostic entry point): y, g, xn, moved, finite, on_the_fly, fused_restrict."""
+        x, direction, c, z0 = _f64(x), _f64(direction), np.asfortranarray(c, dtype=np.float64), _f64(z0)
+        m = self.level_sizes[level]
+        g, xn = np.empty(m), np.empty(m)
+        y, moved, finite, path = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32()
+        _check(self.lib, self.lib.mgbhip_trial_values(self.handle, level, _ptr(x), _ptr(direction), float(step), _ptr(c), _ptr(z0),
+                                                      C.cast(C.byref(y), _dp), _ptr(g), _ptr(xn), C.byref(moved), C.byref(finite),
+                                                      C.byref(path)))
+        return dict(y=y.value, g=g, xn=xn, moved=int(moved.value), finite=int(finite.value), on_the_fly=bool(path.value & 1),
+                    fused_restrict=bool(path.value & 2))
 
     LAUNCH_KEYS = ("level", "first", "count", "cls", "max_m", "max_k", "max_child", "tiny", "wave", "inv", "iface", "packed",
                    "assembly", "block0", "backward")

@@ -1,8 +1,9 @@
-// elem_layout_check.cpp -- host check of the element kernels' LDS layout (csrc/elem_layout.hpp).  Stand-alone: the sizes
+// elem_layout_check.cpp -- host check of the element kernels' LDS layout and dispatch decision (csrc/elem_layout.hpp).  Stand-alone: the sizes
 // the layout gives every launch against the six formulas the launchers and the staging decision carried before the layout
 // existed, written out here as the expected values.  Built with plain g++ by tests/test_elem_layout_host.py; prints OK.
 #include <cstddef>
 #include <cstdio>
+#include <initializer_list>
 
 #include "../../multigridbarrier.jl_amd/csrc/elem_layout.hpp"
 
@@ -60,6 +61,35 @@ bool old_stage_decision(int p, int nu, int nD, int nstage_before, bool wide) {  
     return bytes <= 64 * 1024 && f2_total <= 150 * 1024;
 }
 
+// ---- the dispatch, as launch_elem / try_fast / launch_elem_f2_condense / launch_elem_generic decided it before elem_decide ----
+const int old_fast[8][2] = {{4, 7}, {3, 2}, {5, 8}, {4, 6}, {7, 7}, {6, 2}, {8, 8}, {7, 6}};
+ElemPlan old_dispatch(int p, int nu, int nD, int nstage, bool wide, bool all_staged, bool default_sig, int mode, bool condensing,
+                      long long N) {
+    if (p > 64) return ElemPlan{ELEM_DENSE, 0, 0, 0, 0, 0, 0, 0};
+    const int G = group(p);
+    if (wide) {
+        const int threads = (mode == MODE_F2) ? 128 : 256;
+        const int EPB = threads / G;
+        return ElemPlan{ELEM_WIDE, 0, 0, threads, G, EPB, (N + EPB - 1) / EPB, old_wide_lds_bytes(p, nu, nD, nstage, mode)};
+    }
+    const int EPB = 256 / G;
+    const long long grid = (N + EPB - 1) / EPB;
+    if (condensing && mode == MODE_F2 && nD == 4 && p == 7 && nu == 2 && nstage == 2 && default_sig && all_staged)
+        return ElemPlan{ELEM_CONDENSE, 4, 7, 256, G, EPB, grid, old_f2_fast_lds(7, nu, 4, nstage)};
+    if (mode == MODE_F2 || mode == MODE_F01)
+        for (const auto& f : old_fast) {
+            if (nD != f[0] || p != f[1] || !all_staged) continue;
+            const size_t lds = (mode == MODE_F2) ? old_f2_fast_lds(p, nu, nD, nstage) : old_f01_fast_lds(p, nu, nD, nstage);
+            if (lds > 160 * 1024) continue;
+            return ElemPlan{default_sig ? ELEM_FAST_DEFAULT : ELEM_FAST_RUNTIME, nD, p, 256, G, EPB, grid, lds};
+        }
+    return ElemPlan{ELEM_GENERIC, nD, 0, 256, G, EPB, grid, old_elem_lds_bytes(p, nu, nD, nstage, mode)};
+}
+bool same(const ElemPlan& a, const ElemPlan& b) {
+    return a.kind == b.kind && a.NY == b.NY && a.P == b.P && a.threads == b.threads && a.G == b.G && a.EPB == b.EPB && a.grid == b.grid &&
+           a.lds == b.lds;
+}
+
 }  // namespace
 
 int main() {
@@ -95,6 +125,35 @@ int main() {
                     checked += 4;
                 }
     }
+    // the dispatch decision over the whole grid: every p up to the dense gate, every nD, both paths, every flag
+    long decided = 0;
+    int kinds_seen = 0;
+    for (int p = 1; p <= 66; ++p)
+        for (int nu = 1; nu <= 4; ++nu)
+            for (int nD = 1; nD <= 13; ++nD)
+                for (int nstage = 0; nstage <= 6; ++nstage)
+                    for (int flags = 0; flags < 16; ++flags) {
+                        const bool wide = (flags & 1) || nD > 10, all_staged = flags & 2, default_sig = flags & 4, condensing = flags & 8;
+                        for (int mode : modes)
+                            for (long long N : {1LL, 31LL, 32LL, 33LL, 129LL, 70000LL}) {
+                                const ElemPlan got = elem_decide(p, nu, nD, nstage, wide, p > 64, all_staged, default_sig, mode, condensing, N);
+                                const ElemPlan want = old_dispatch(p, nu, nD, nstage, wide, all_staged, default_sig, mode, condensing, N);
+                                CHECK(same(got, want), "dispatch p=%d nu=%d nD=%d nstage=%d flags=%d mode=%d N=%lld: kind %d/%d NY %d/%d lds %zu/%zu",
+                                      p, nu, nD, nstage, flags, mode, N, got.kind, want.kind, got.NY, want.NY, got.lds, want.lds);
+                                if (got.kind != ELEM_DENSE) CHECK(got.EPB * got.G == got.threads && got.grid * got.EPB >= N && (got.grid - 1) * got.EPB < N,
+                                                                  "grid covers N: p=%d mode=%d N=%lld", p, mode, N);
+                                kinds_seen |= 1 << got.kind;
+                                ++decided;
+                            }
+                    }
+    CHECK(kinds_seen == 0x3f, "every kernel kind is reached: %x", kinds_seen);
+    for (int i = 0; i < ELEM_FAST_COUNT; ++i) {
+        CHECK(ELEM_FAST_TABLE[i][0] == old_fast[i][0] && ELEM_FAST_TABLE[i][1] == old_fast[i][1], "fast table entry %d", i);
+        CHECK(elem_fast_index(ELEM_FAST_TABLE[i][0], ELEM_FAST_TABLE[i][1]) == i, "fast index %d", i);
+    }
+    CHECK(elem_fast_index(4, 8) == -1 && elem_fast_index(3, 7) == -1, "pairs outside the table");
+    checked += decided;
+
     // the kernels' own offsets: opL behind zl, YL behind opL
     CHECK(elem_lds_z(256, 2) == 512 && elem_lds_z((size_t)128, 4) == 512, "z region");
     CHECK(elem_lds_ops(2, 32, 49) == 3136, "operator region");
