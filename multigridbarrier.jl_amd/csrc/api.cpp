@@ -47,64 +47,24 @@ struct DeviceGuard {
     }
 };
 static int dev_of(const mgbhip_ctx* c) { return c ? c->device : -1; }
-static int dev_of(const mgbhip_problem* p) { return (p && p->ctx) ? p->ctx->device : -1; }
-static int dev_of(const mgbhip_vec* v) { return (v && v->ctx) ? v->ctx->device : -1; }
+// every other handle (problem, vector and the post-processing handles below) names its context
+template <class H>
+static int dev_of(const H* h) { return (h && h->ctx) ? h->ctx->device : -1; }
 
-// a point locator (interpolate.hpp) and the context it lives in
-struct mgbhip_locator {
+// A post-processing object and the context it lives in.  The opaque types of include/mgbhip.h are one line each.
+template <class T>
+struct Handle {
     mgbhip_ctx* ctx = nullptr;
-    Locator loc;
+    T obj;
 };
-static int dev_of(const mgbhip_locator* l) { return (l && l->ctx) ? l->ctx->device : -1; }
-
-// a simplex soup (contour.hpp) and the context it lives in
-struct mgbhip_contour {
-    mgbhip_ctx* ctx = nullptr;
-    Contour con;
-};
-static int dev_of(const mgbhip_contour* c) { return (c && c->ctx) ? c->ctx->device : -1; }
-
-// the lattice triangles of a 2-D mesh (contour.hpp) and the context they live in
-struct mgbhip_tessellation {
-    mgbhip_ctx* ctx = nullptr;
-    Tessellation tes;
-};
-static int dev_of(const mgbhip_tessellation* t) { return (t && t->ctx) ? t->ctx->device : -1; }
-
-// a ray caster (raycast.hpp) and the context it lives in
-struct mgbhip_raycast {
-    mgbhip_ctx* ctx = nullptr;
-    RayCaster rc;
-};
-static int dev_of(const mgbhip_raycast* r) { return (r && r->ctx) ? r->ctx->device : -1; }
-
-// a triangle soup in its grid (surface.hpp) and the context it lives in
-struct mgbhip_surface {
-    mgbhip_ctx* ctx = nullptr;
-    Surface sf;
-};
-static int dev_of(const mgbhip_surface* s) { return (s && s->ctx) ? s->ctx->device : -1; }
-
-// a capsule soup in its grid (tubes.hpp) and the context it lives in
-struct mgbhip_tubes {
-    mgbhip_ctx* ctx = nullptr;
-    Tubes tb;
-};
-static int dev_of(const mgbhip_tubes* s) { return (s && s->ctx) ? s->ctx->device : -1; }
-
-// a field-line tracer (stream.hpp) and the context it lives in
-struct mgbhip_stream {
-    mgbhip_ctx* ctx = nullptr;
-    StreamTracer tr;
-};
-static int dev_of(const mgbhip_stream* s) { return (s && s->ctx) ? s->ctx->device : -1; }
-
-// a resident figure pipeline (figure.hpp) and the context it lives in
-struct mgbhip_figure {
-    mgbhip_ctx* ctx = nullptr;
-    Figure fig;
-};
-static int dev_of(const mgbhip_figure* f) { return (f && f->ctx) ? f->ctx->device : -1; }
+struct mgbhip_locator : Handle<Locator> {};            // a point locator (interpolate.hpp)
+struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
+struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
+struct mgbhip_raycast : Handle<RayCaster> {};          // a ray caster (raycast.hpp)
+struct mgbhip_surface : Handle<Surface> {};            // a triangle soup in its grid (surface.hpp)
+struct mgbhip_tubes : Handle<Tubes> {};                // a capsule soup in its grid (tubes.hpp)
+struct mgbhip_stream : Handle<StreamTracer> {};        // a field-line tracer (stream.hpp)
+struct mgbhip_figure : Handle<Figure> {};              // a resident figure pipeline (figure.hpp)
 
 #define MGB_API_BEGIN try {
 #define MGB_API_BEGIN_ON(h) try { DeviceGuard _guard(dev_of(h));
@@ -122,6 +82,67 @@ static int dev_of(const mgbhip_figure* f) { return (f && f->ctx) ? f->ctx->devic
         g_last_error = e.what();                      \
         return MGBHIP_ERR_INVALID;                    \
     }
+
+// a new handle in ctx, built by build(obj), released into *out only once it is complete
+template <class H, class Build>
+static void create_handle(mgbhip_ctx* ctx, H** out, Build build) {
+    std::unique_ptr<H> h(new H());
+    h->ctx = ctx;
+    build(h->obj);
+    *out = h.release();
+}
+
+// null is fine; else whatever is queued on the context's stream may still read the object's buffers
+template <class H>
+static int destroy_handle(H* h) {
+    MGB_API_BEGIN_ON(h)
+    if (!h) return MGBHIP_OK;
+    (void)hipStreamSynchronize(h->ctx->stream);
+    delete h;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+// The argument checks the rendering entry points share; `who` is the caller's prefix in the message.
+static void check_window(const std::string& who, double t_min, double t_max) {
+    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, who + ": t_min must be finite and t_max > t_min");
+}
+
+// R rays of dimension dim: finite, directions of unit length within 1e-12
+static void check_rays(const std::string& who, int64_t R, int dim, const double* origin, const double* dir) {
+    for (int64_t i = 0; i < R * dim; ++i)
+        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), who + ": origins and directions must be finite");
+    for (int64_t r = 0; r < R; ++r) {
+        double q = 0.0;
+        for (int a = 0; a < dim; ++a) q += dir[r * dim + a] * dir[r * dim + a];
+        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, who + ": directions must have unit length");
+    }
+}
+
+static void check_clim(const std::string& who, double lo, double hi) {
+    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, who + ": clim must be finite with lo < hi");
+}
+
+static void check_ambient(const std::string& who, double ambient) {
+    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, who + ": ambient must be in [0, 1]");
+}
+
+// the Kt x 4 colour table of a shade call (r, g, b, alpha), then its colour limits and ambient term
+static void check_table_clim_ambient(const std::string& who, int32_t Kt, const double* table, double lo, double hi,
+                                     double ambient) {
+    MGB_REQUIRE(Kt >= 2, who + ": the colour table needs at least two rows");
+    for (int64_t i = 0; i < (int64_t)Kt * 4; ++i) MGB_REQUIRE(std::isfinite(table[i]), who + ": the colour table must be finite");
+    check_clim(who, lo, hi);
+    check_ambient(who, ambient);
+}
+
+// the K x 4 transfer table of a volume render (r, g, b, sigma), then its colour limits
+static void check_transfer_clim(int32_t K, const double* transfer, double lo, double hi) {
+    for (int64_t i = 0; i < (int64_t)K * 4; ++i)
+        MGB_REQUIRE(std::isfinite(transfer[i]) && (i % 4 != 3 || transfer[i] >= 0.0),
+                    "raycast: the transfer table must be finite with sigma >= 0");
+    check_clim("raycast", lo, hi);
+}
 
 extern "C" {
 
@@ -881,10 +902,7 @@ int mgbhip_locator_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
     in.family = family; in.d = d; in.k = k; in.p = p; in.N = N; in.M = M;
     in.x = x; in.table = table; in.pts = pts;
     interpolate_check_geometry(in);
-    std::unique_ptr<mgbhip_locator> loc(new mgbhip_locator());
-    loc->ctx = ctx;
-    locator_build(loc->loc, in, ctx->stream);
-    *out = loc.release();
+    create_handle(ctx, out, [&](Locator& L) { locator_build(L, in, ctx->stream); });
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -892,8 +910,8 @@ int mgbhip_locator_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
 int mgbhip_locator_elements(const mgbhip_locator* loc, int32_t* elem) {
     MGB_API_BEGIN_ON(loc)
     MGB_REQUIRE(loc != nullptr, "null locator");
-    MGB_REQUIRE(loc->loc.M == 0 || elem != nullptr, "null argument");
-    locator_elements(loc->loc, elem, loc->ctx->stream);
+    MGB_REQUIRE(loc->obj.M == 0 || elem != nullptr, "null argument");
+    locator_elements(loc->obj, elem, loc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -901,23 +919,16 @@ int mgbhip_locator_elements(const mgbhip_locator* loc, int32_t* elem) {
 int mgbhip_locator_evaluate(mgbhip_locator* loc, int32_t ncomp, const double* z, double* out, double* grad) {
     MGB_API_BEGIN_ON(loc)
     MGB_REQUIRE(loc != nullptr, "null locator");
-    const Locator& L = loc->loc;
+    const Locator& L = loc->obj;
     MGB_REQUIRE(ncomp >= 1, "interpolate: bad sizes");
     MGB_REQUIRE(z != nullptr && (L.M == 0 || out != nullptr || grad != nullptr), "null argument");
     MGB_REQUIRE(L.M * ncomp * (grad ? L.d : 1) < (int64_t)INT32_MAX, "interpolate: sizes exceed 32-bit indexing");
-    locator_evaluate(loc->loc, ncomp, z, out, grad, loc->ctx->stream);
+    locator_evaluate(loc->obj, ncomp, z, out, grad, loc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_locator_destroy(mgbhip_locator* loc) {
-    MGB_API_BEGIN_ON(loc)
-    if (!loc) return MGBHIP_OK;
-    (void)hipStreamSynchronize(loc->ctx->stream);
-    delete loc;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_locator_destroy(mgbhip_locator* loc) { return destroy_handle(loc); }
 
 int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
                                    const double* x, const double* table, int32_t nfield, const double* fields,
@@ -942,11 +953,8 @@ int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, i
     ContourIn in;
     in.family = family; in.d = d; in.e = e; in.k = k; in.p = p; in.N = N; in.nfield = nfield; in.nlevels = nlevels;
     in.refine = refine; in.x = x; in.table = table; in.fields = fields; in.levels = levels;
-    std::unique_ptr<mgbhip_contour> c(new mgbhip_contour());
-    c->ctx = ctx;
-    contour_build(c->con, in, ctx->stream);
-    *nsimplices = c->con.S;
-    *out = c.release();
+    create_handle(ctx, out, [&](Contour& C) { contour_build(C, in, ctx->stream); });
+    *nsimplices = (*out)->obj.S;
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -961,20 +969,13 @@ int mgbhip_contour_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
 int mgbhip_contour_fetch(const mgbhip_contour* c, double* points, int32_t* level, int32_t* element, double* carried) {
     MGB_API_BEGIN_ON(c)
     MGB_REQUIRE(c != nullptr, "null contour");
-    MGB_REQUIRE(c->con.S == 0 || (points != nullptr && level != nullptr && element != nullptr), "null argument");
-    contour_fetch(c->con, points, level, element, carried, c->ctx->stream);
+    MGB_REQUIRE(c->obj.S == 0 || (points != nullptr && level != nullptr && element != nullptr), "null argument");
+    contour_fetch(c->obj, points, level, element, carried, c->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_contour_destroy(mgbhip_contour* c) {
-    MGB_API_BEGIN_ON(c)
-    if (!c) return MGBHIP_OK;
-    (void)hipStreamSynchronize(c->ctx->stream);
-    delete c;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_contour_destroy(mgbhip_contour* c) { return destroy_handle(c); }
 
 int mgbhip_tessellate_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
                              const double* x, const double* table, int32_t nfield, const double* fields, int32_t refine,
@@ -1002,11 +1003,8 @@ int mgbhip_tessellate_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t
     if (T > (int64_t)INT32_MAX / 3)
         throw InvalidArgument("tessellate: T = " + std::to_string(T) + " triangles have more than 2^31 - 1 vertices: use a "
                               "smaller refine");
-    std::unique_ptr<mgbhip_tessellation> t(new mgbhip_tessellation());
-    t->ctx = ctx;
-    tessellate_build(t->tes, in, ctx->stream);
-    *ntriangles = t->tes.T;
-    *out = t.release();
+    create_handle(ctx, out, [&](Tessellation& Ts) { tessellate_build(Ts, in, ctx->stream); });
+    *ntriangles = (*out)->obj.T;
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1015,19 +1013,12 @@ int mgbhip_tessellate_fetch(const mgbhip_tessellation* t, double* points, int32_
     MGB_API_BEGIN_ON(t)
     MGB_REQUIRE(t != nullptr, "tessellate_fetch: null tessellation");
     MGB_REQUIRE(points != nullptr && element != nullptr, "tessellate_fetch: null argument");
-    tessellate_fetch(t->tes, points, element, values, t->ctx->stream);
+    tessellate_fetch(t->obj, points, element, values, t->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_tessellate_destroy(mgbhip_tessellation* t) {
-    MGB_API_BEGIN_ON(t)
-    if (!t) return MGBHIP_OK;
-    (void)hipStreamSynchronize(t->ctx->stream);
-    delete t;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_tessellate_destroy(mgbhip_tessellation* t) { return destroy_handle(t); }
 
 int mgbhip_raycast_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
                           const double* table, int64_t R, const double* origin, const double* dir, const double* box,
@@ -1044,22 +1035,13 @@ int mgbhip_raycast_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k,
     in.geo.family = family; in.geo.d = d; in.geo.k = k; in.geo.p = p; in.geo.N = N; in.geo.x = x; in.geo.table = table;
     interpolate_check_geometry(in.geo);
     MGB_REQUIRE(std::isfinite(step) && step > 0.0, "raycast: step must be finite and positive");
-    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, "raycast: t_min must be finite and t_max > t_min");
-    for (int64_t i = 0; i < R * d; ++i)
-        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "raycast: origins and directions must be finite");
-    for (int64_t r = 0; r < R; ++r) {
-        double s = 0.0;
-        for (int a = 0; a < d; ++a) s += dir[r * d + a] * dir[r * d + a];
-        MGB_REQUIRE(std::fabs(s - 1.0) <= 1e-12, "raycast: directions must have unit length");
-    }
+    check_window("raycast", t_min, t_max);
+    check_rays("raycast", R, d, origin, dir);
     for (int a = 0; a < d && R > 0; ++a)
         MGB_REQUIRE(std::isfinite(box[a]) && std::isfinite(box[d + a]) && box[a] <= box[d + a], "raycast: bad clip box");
     in.R = R; in.origin = origin; in.dir = dir; in.box = box; in.step = step; in.t_min = t_min; in.t_max = t_max;
-    std::unique_ptr<mgbhip_raycast> rc(new mgbhip_raycast());
-    rc->ctx = ctx;
-    raycast_build(rc->rc, in, ctx->stream);
-    *nsamples = rc->rc.S;
-    *out = rc.release();
+    create_handle(ctx, out, [&](RayCaster& RC) { raycast_build(RC, in, ctx->stream); });
+    *nsamples = (*out)->obj.S;
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1068,7 +1050,7 @@ int mgbhip_raycast_offsets(const mgbhip_raycast* rc, int64_t* offsets) {
     MGB_API_BEGIN_ON(rc)
     MGB_REQUIRE(rc != nullptr, "null ray caster");
     MGB_REQUIRE(offsets != nullptr, "null argument");
-    raycast_offsets(rc->rc, offsets, rc->ctx->stream);
+    raycast_offsets(rc->obj, offsets, rc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1076,8 +1058,8 @@ int mgbhip_raycast_offsets(const mgbhip_raycast* rc, int64_t* offsets) {
 int mgbhip_raycast_samples(const mgbhip_raycast* rc, double* pts) {
     MGB_API_BEGIN_ON(rc)
     MGB_REQUIRE(rc != nullptr, "null ray caster");
-    MGB_REQUIRE(rc->rc.S == 0 || pts != nullptr, "null argument");
-    raycast_samples(rc->rc, pts, rc->ctx->stream);
+    MGB_REQUIRE(rc->obj.S == 0 || pts != nullptr, "null argument");
+    raycast_samples(rc->obj, pts, rc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1085,7 +1067,7 @@ int mgbhip_raycast_samples(const mgbhip_raycast* rc, double* pts) {
 int mgbhip_raycast_lengths(const mgbhip_raycast* rc, double* step, double* length) {
     MGB_API_BEGIN_ON(rc)
     MGB_REQUIRE(rc != nullptr, "null ray caster");
-    raycast_lengths(rc->rc, step, length, rc->ctx->stream);
+    raycast_lengths(rc->obj, step, length, rc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1094,8 +1076,8 @@ int mgbhip_raycast_integrate(mgbhip_raycast* rc, int32_t ncomp, const double* z,
     MGB_API_BEGIN_ON(rc)
     MGB_REQUIRE(rc != nullptr, "null ray caster");
     MGB_REQUIRE(ncomp >= 1, "raycast: bad sizes");
-    MGB_REQUIRE(z != nullptr && (rc->rc.R == 0 || out != nullptr), "null argument");
-    raycast_integrate(rc->rc, ncomp, z, out, rc->ctx->stream);
+    MGB_REQUIRE(z != nullptr && (rc->obj.R == 0 || out != nullptr), "null argument");
+    raycast_integrate(rc->obj, ncomp, z, out, rc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1104,39 +1086,26 @@ int mgbhip_raycast_render(mgbhip_raycast* rc, const double* u, int32_t K, const 
                           double* out) {
     MGB_API_BEGIN_ON(rc)
     MGB_REQUIRE(rc != nullptr, "null ray caster");
-    MGB_REQUIRE(u != nullptr && transfer != nullptr && (rc->rc.R == 0 || out != nullptr), "null argument");
+    MGB_REQUIRE(u != nullptr && transfer != nullptr && (rc->obj.R == 0 || out != nullptr), "null argument");
     MGB_REQUIRE(K >= 2, "raycast: the transfer table needs at least two rows");
-    for (int64_t i = 0; i < (int64_t)K * 4; ++i)
-        MGB_REQUIRE(std::isfinite(transfer[i]) && (i % 4 != 3 || transfer[i] >= 0.0),
-                    "raycast: the transfer table must be finite with sigma >= 0");
-    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "raycast: clim must be finite with lo < hi");
-    raycast_render(rc->rc, u, K, transfer, lo, hi, out, rc->ctx->stream);
+    check_transfer_clim(K, transfer, lo, hi);
+    raycast_render(rc->obj, u, K, transfer, lo, hi, out, rc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_raycast_destroy(mgbhip_raycast* rc) {
-    MGB_API_BEGIN_ON(rc)
-    if (!rc) return MGBHIP_OK;
-    (void)hipStreamSynchronize(rc->ctx->stream);
-    delete rc;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_raycast_destroy(mgbhip_raycast* rc) { return destroy_handle(rc); }
 
 int mgbhip_raycast_render_layers(mgbhip_raycast* rc, const double* u, int32_t K, const double* transfer, double lo,
                                  double hi, int32_t nhits, const double* t_hit, const double* layer, double* out) {
     MGB_API_BEGIN_ON(rc)
     MGB_REQUIRE(rc != nullptr, "null ray caster");
-    MGB_REQUIRE(u != nullptr && transfer != nullptr && (rc->rc.R == 0 || (out != nullptr && t_hit != nullptr && layer != nullptr)),
+    MGB_REQUIRE(u != nullptr && transfer != nullptr && (rc->obj.R == 0 || (out != nullptr && t_hit != nullptr && layer != nullptr)),
                 "null argument");
     MGB_REQUIRE(K >= 2, "raycast: the transfer table needs at least two rows");
     MGB_REQUIRE(nhits >= 1 && nhits <= SURFACE_MAX_HITS, "raycast: the number of layers per ray must be 1..8");
-    for (int64_t i = 0; i < (int64_t)K * 4; ++i)
-        MGB_REQUIRE(std::isfinite(transfer[i]) && (i % 4 != 3 || transfer[i] >= 0.0),
-                    "raycast: the transfer table must be finite with sigma >= 0");
-    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "raycast: clim must be finite with lo < hi");
-    for (int64_t r = 0; r < rc->rc.R; ++r)
+    check_transfer_clim(K, transfer, lo, hi);
+    for (int64_t r = 0; r < rc->obj.R; ++r)
         for (int32_t k = 0; k < nhits; ++k) {
             const double th = t_hit[r * nhits + k];
             MGB_REQUIRE(!std::isnan(th) && (k == 0 || t_hit[r * nhits + k - 1] <= th),
@@ -1144,7 +1113,7 @@ int mgbhip_raycast_render_layers(mgbhip_raycast* rc, const double* u, int32_t K,
             for (int c = 0; c < 4; ++c)
                 MGB_REQUIRE(std::isfinite(layer[(r * nhits + k) * 4 + c]), "raycast: every layer entry must be finite");
         }
-    raycast_render_layers(rc->rc, u, K, transfer, lo, hi, nhits, t_hit, layer, out, rc->ctx->stream);
+    raycast_render_layers(rc->obj, u, K, transfer, lo, hi, nhits, t_hit, layer, out, rc->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1164,10 +1133,7 @@ int mgbhip_stream_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, 
     geo.family = family; geo.d = d; geo.k = k; geo.p = p; geo.N = N; geo.x = x; geo.table = table;
     interpolate_check_geometry(geo);
     for (int64_t i = 0; i < (int64_t)p * N * d; ++i) MGB_REQUIRE(std::isfinite(x[i]), "stream: non-finite node coordinates");
-    std::unique_ptr<mgbhip_stream> s(new mgbhip_stream());
-    s->ctx = ctx;
-    stream_build(s->tr, geo, field, z, ctx->stream);
-    *out = s.release();
+    create_handle(ctx, out, [&](StreamTracer& Tr) { stream_build(Tr, geo, field, z, ctx->stream); });
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1176,7 +1142,7 @@ int mgbhip_stream_set_field(mgbhip_stream* s, const double* z) {
     MGB_API_BEGIN_ON(s)
     MGB_REQUIRE(s != nullptr, "null stream tracer");
     MGB_REQUIRE(z != nullptr, "null argument");
-    stream_set_field(s->tr, z, s->ctx->stream);
+    stream_set_field(s->obj, z, s->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1189,22 +1155,15 @@ int mgbhip_stream_trace(mgbhip_stream* s, int64_t S, const double* seeds, double
     MGB_REQUIRE(std::isfinite(h) && h != 0.0, "stream: the step must be finite and non-zero");
     MGB_REQUIRE(std::isfinite(min_speed) && min_speed >= 0.0, "stream: min_speed must be finite and >= 0");
     // by count, in a type that cannot overflow: S (max_steps + 1) d < 2^31
-    MGB_REQUIRE((long double)S * ((long double)max_steps + 1.0L) * (long double)s->tr.d < 2147483648.0L,
+    MGB_REQUIRE((long double)S * ((long double)max_steps + 1.0L) * (long double)s->obj.d < 2147483648.0L,
                 "stream: S * (max_steps + 1) * d exceeds 32-bit indexing");
     MGB_REQUIRE(S == 0 || (seeds != nullptr && points != nullptr && n != nullptr && status != nullptr), "null argument");
-    stream_trace(s->tr, S, seeds, h, max_steps, normalize != 0, min_speed, points, n, status, s->ctx->stream);
+    stream_trace(s->obj, S, seeds, h, max_steps, normalize != 0, min_speed, points, n, status, s->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_stream_destroy(mgbhip_stream* s) {
-    MGB_API_BEGIN_ON(s)
-    if (!s) return MGBHIP_OK;
-    (void)hipStreamSynchronize(s->ctx->stream);
-    delete s;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_stream_destroy(mgbhip_stream* s) { return destroy_handle(s); }
 
 int mgbhip_surface_create(mgbhip_ctx* ctx, int64_t T, const double* points, mgbhip_surface** out) {
     MGB_API_BEGIN_ON(ctx)
@@ -1213,10 +1172,7 @@ int mgbhip_surface_create(mgbhip_ctx* ctx, int64_t T, const double* points, mgbh
     MGB_REQUIRE(T >= 0 && T < (int64_t)INT32_MAX / 9, "surface: bad sizes");
     MGB_REQUIRE(T == 0 || points != nullptr, "null argument");
     for (int64_t i = 0; i < T * 9; ++i) MGB_REQUIRE(std::isfinite(points[i]), "surface: every vertex must be finite");
-    std::unique_ptr<mgbhip_surface> s(new mgbhip_surface());
-    s->ctx = ctx;
-    surface_build(s->sf, T, points, ctx->stream);
-    *out = s.release();
+    create_handle(ctx, out, [&](Surface& Sf) { surface_build(Sf, T, points, ctx->stream); });
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1229,15 +1185,9 @@ int mgbhip_surface_trace(mgbhip_surface* s, int64_t R, const double* origin, con
     MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * SURFACE_MAX_HITS), "surface: bad sizes");
     MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && t != nullptr && tri != nullptr && u != nullptr && v != nullptr),
                 "null argument");
-    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, "surface: t_min must be finite and t_max > t_min");
-    for (int64_t i = 0; i < R * 3; ++i)
-        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "surface: origins and directions must be finite");
-    for (int64_t r = 0; r < R; ++r) {
-        double q = 0.0;
-        for (int a = 0; a < 3; ++a) q += dir[r * 3 + a] * dir[r * 3 + a];
-        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, "surface: directions must have unit length");
-    }
-    surface_trace(s->sf, R, origin, dir, t_min, t_max, K, t, tri, u, v, s->ctx->stream);
+    check_window("surface", t_min, t_max);
+    check_rays("surface", R, 3, origin, dir);
+    surface_trace(s->obj, R, origin, dir, t_min, t_max, K, t, tri, u, v, s->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1251,27 +1201,17 @@ int mgbhip_surface_shade(mgbhip_surface* s, int64_t R, int32_t K, const double* 
     MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * SURFACE_MAX_HITS), "surface: bad sizes");
     MGB_REQUIRE(R == 0 || (dir != nullptr && tri != nullptr && u != nullptr && v != nullptr && layer != nullptr),
                 "null argument");
-    MGB_REQUIRE(table != nullptr && (s->sf.T == 0 || values != nullptr), "null argument");
-    MGB_REQUIRE(Kt >= 2, "surface: the colour table needs at least two rows");
-    for (int64_t i = 0; i < (int64_t)Kt * 4; ++i) MGB_REQUIRE(std::isfinite(table[i]), "surface: the colour table must be finite");
-    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "surface: clim must be finite with lo < hi");
-    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "surface: ambient must be in [0, 1]");
+    MGB_REQUIRE(table != nullptr && (s->obj.n == 0 || values != nullptr), "null argument");
+    check_table_clim_ambient("surface", Kt, table, lo, hi, ambient);
     for (int64_t i = 0; i < R * 3; ++i) MGB_REQUIRE(std::isfinite(dir[i]), "surface: directions must be finite");
     for (int64_t i = 0; i < R * K; ++i)
-        MGB_REQUIRE(tri[i] >= -1 && (int64_t)tri[i] < s->sf.T, "surface: a triangle index is out of range");
-    surface_shade(s->sf, R, K, dir, tri, u, v, values, Kt, table, lo, hi, ambient, layer, s->ctx->stream);
+        MGB_REQUIRE(tri[i] >= -1 && (int64_t)tri[i] < s->obj.n, "surface: a triangle index is out of range");
+    surface_shade(s->obj, R, K, dir, tri, u, v, values, Kt, table, lo, hi, ambient, layer, s->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_surface_destroy(mgbhip_surface* s) {
-    MGB_API_BEGIN_ON(s)
-    if (!s) return MGBHIP_OK;
-    (void)hipStreamSynchronize(s->ctx->stream);
-    delete s;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_surface_destroy(mgbhip_surface* s) { return destroy_handle(s); }
 
 int mgbhip_tubes_create(mgbhip_ctx* ctx, int64_t S, const double* points, const double* radii, mgbhip_tubes** out) {
     MGB_API_BEGIN_ON(ctx)
@@ -1282,10 +1222,7 @@ int mgbhip_tubes_create(mgbhip_ctx* ctx, int64_t S, const double* points, const 
     for (int64_t i = 0; i < S * 6; ++i) MGB_REQUIRE(std::isfinite(points[i]), "tubes: every end point must be finite");
     for (int64_t i = 0; i < S; ++i)
         MGB_REQUIRE(std::isfinite(radii[i]) && radii[i] > 0.0, "tubes: every radius must be finite and positive");
-    std::unique_ptr<mgbhip_tubes> s(new mgbhip_tubes());
-    s->ctx = ctx;
-    tubes_build(s->tb, S, points, radii, ctx->stream);
-    *out = s.release();
+    create_handle(ctx, out, [&](Tubes& Tb) { tubes_build(Tb, S, points, radii, ctx->stream); });
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1298,15 +1235,9 @@ int mgbhip_tubes_trace(mgbhip_tubes* s, int64_t R, const double* origin, const d
     MGB_REQUIRE(R >= 0 && R < (int64_t)INT32_MAX / (4 * TUBES_MAX_HITS), "tubes: bad sizes");
     MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && t != nullptr && segment != nullptr && sp != nullptr),
                 "null argument");
-    MGB_REQUIRE(std::isfinite(t_min) && t_max > t_min, "tubes: t_min must be finite and t_max > t_min");
-    for (int64_t i = 0; i < R * 3; ++i)
-        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "tubes: origins and directions must be finite");
-    for (int64_t r = 0; r < R; ++r) {
-        double q = 0.0;
-        for (int a = 0; a < 3; ++a) q += dir[r * 3 + a] * dir[r * 3 + a];
-        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, "tubes: directions must have unit length");
-    }
-    tubes_trace(s->tb, R, origin, dir, t_min, t_max, K, t, segment, sp, s->ctx->stream);
+    check_window("tubes", t_min, t_max);
+    check_rays("tubes", R, 3, origin, dir);
+    tubes_trace(s->obj, R, origin, dir, t_min, t_max, K, t, segment, sp, s->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1321,31 +1252,21 @@ int mgbhip_tubes_shade(mgbhip_tubes* s, int64_t R, int32_t K, const double* orig
     MGB_REQUIRE(R == 0 || (origin != nullptr && dir != nullptr && t != nullptr && segment != nullptr && sp != nullptr &&
                            layer != nullptr),
                 "null argument");
-    MGB_REQUIRE(table != nullptr && (s->tb.S == 0 || values != nullptr), "null argument");
-    MGB_REQUIRE(Kt >= 2, "tubes: the colour table needs at least two rows");
-    for (int64_t i = 0; i < (int64_t)Kt * 4; ++i) MGB_REQUIRE(std::isfinite(table[i]), "tubes: the colour table must be finite");
-    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "tubes: clim must be finite with lo < hi");
-    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "tubes: ambient must be in [0, 1]");
+    MGB_REQUIRE(table != nullptr && (s->obj.n == 0 || values != nullptr), "null argument");
+    check_table_clim_ambient("tubes", Kt, table, lo, hi, ambient);
     for (int64_t i = 0; i < R * 3; ++i)
         MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "tubes: origins and directions must be finite");
     for (int64_t i = 0; i < R * K; ++i) {
-        MGB_REQUIRE(segment[i] >= -1 && (int64_t)segment[i] < s->tb.S, "tubes: a segment index is out of range");
+        MGB_REQUIRE(segment[i] >= -1 && (int64_t)segment[i] < s->obj.n, "tubes: a segment index is out of range");
         MGB_REQUIRE(segment[i] < 0 || (std::isfinite(t[i]) && sp[i] >= 0.0 && sp[i] <= 1.0),
                     "tubes: a hit needs a finite t and s in [0, 1]");
     }
-    tubes_shade(s->tb, R, K, origin, dir, t, segment, sp, values, Kt, table, lo, hi, ambient, layer, s->ctx->stream);
+    tubes_shade(s->obj, R, K, origin, dir, t, segment, sp, values, Kt, table, lo, hi, ambient, layer, s->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_tubes_destroy(mgbhip_tubes* s) {
-    MGB_API_BEGIN_ON(s)
-    if (!s) return MGBHIP_OK;
-    (void)hipStreamSynchronize(s->ctx->stream);
-    delete s;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_tubes_destroy(mgbhip_tubes* s) { return destroy_handle(s); }
 
 int mgbhip_figure_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
                          const double* table, int64_t R, const double* origin, const double* dir, const double* box,
@@ -1381,15 +1302,9 @@ int mgbhip_figure_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, 
                     "figure: the volume table must be finite with sigma >= 0");
         MGB_REQUIRE(std::isfinite(stable[i]), "figure: the surface table must be finite");
     }
-    MGB_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "figure: clim must be finite with lo < hi");
-    MGB_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "figure: ambient must be in [0, 1]");
-    for (int64_t i = 0; i < R * 3; ++i)
-        MGB_REQUIRE(std::isfinite(origin[i]) && std::isfinite(dir[i]), "figure: origins and directions must be finite");
-    for (int64_t r = 0; r < R; ++r) {
-        double q = 0.0;
-        for (int a = 0; a < 3; ++a) q += dir[r * 3 + a] * dir[r * 3 + a];
-        MGB_REQUIRE(std::fabs(q - 1.0) <= 1e-12, "figure: directions must have unit length");
-    }
+    check_clim("figure", lo, hi);
+    check_ambient("figure", ambient);
+    check_rays("figure", R, 3, origin, dir);
     for (int a = 0; a < 3; ++a)
         MGB_REQUIRE(std::isfinite(box[a]) && std::isfinite(box[3 + a]) && box[a] <= box[3 + a], "figure: bad clip box");
     for (int64_t i = 0; i < (int64_t)p * N * 3; ++i) MGB_REQUIRE(std::isfinite(x[i]), "figure: the mesh must be finite");
@@ -1398,10 +1313,7 @@ int mgbhip_figure_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, 
     in.volume = volume ? 1 : 0;
     in.nlevels = nlevels; in.levels = levels; in.nslices = nslices; in.axes = axes; in.coords = coords;
     in.ntable = ntable; in.vtable = vtable; in.stable = stable; in.lo = lo; in.hi = hi; in.ambient = ambient; in.K = K;
-    std::unique_ptr<mgbhip_figure> f(new mgbhip_figure());
-    f->ctx = ctx;
-    figure_build(f->fig, in, ctx->stream);
-    *out = f.release();
+    create_handle(ctx, out, [&](Figure& F) { figure_build(F, in, ctx->stream); });
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1410,7 +1322,7 @@ int mgbhip_figure_render(mgbhip_figure* f, const double* u, double* out) {
     MGB_API_BEGIN_ON(f)
     MGB_REQUIRE(f != nullptr, "null figure");
     MGB_REQUIRE(u != nullptr && out != nullptr, "null argument");
-    figure_render(f->fig, u, out, f->ctx->stream);
+    figure_render(f->obj, u, out, f->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1420,7 +1332,7 @@ int mgbhip_figure_render_rgba8(mgbhip_figure* f, const double* u, const double* 
     MGB_REQUIRE(f != nullptr, "null figure");
     MGB_REQUIRE(u != nullptr && background != nullptr && out != nullptr, "null argument");
     for (int a = 0; a < 3; ++a) MGB_REQUIRE(std::isfinite(background[a]), "figure: the background must be finite");
-    figure_render_rgba8(f->fig, u, background, out, f->ctx->stream);
+    figure_render_rgba8(f->obj, u, background, out, f->ctx->stream);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1428,19 +1340,12 @@ int mgbhip_figure_render_rgba8(mgbhip_figure* f, const double* u, const double* 
 int mgbhip_figure_counts(const mgbhip_figure* f, int64_t* ntriangles, int64_t* npairs) {
     MGB_API_BEGIN_ON(f)
     MGB_REQUIRE(f != nullptr, "null figure");
-    if (ntriangles) *ntriangles = f->fig.T;
-    if (npairs) *npairs = f->fig.P;
+    if (ntriangles) *ntriangles = f->obj.T;
+    if (npairs) *npairs = f->obj.P;
     return MGBHIP_OK;
     MGB_API_END
 }
 
-int mgbhip_figure_destroy(mgbhip_figure* f) {
-    MGB_API_BEGIN_ON(f)
-    if (!f) return MGBHIP_OK;
-    (void)hipStreamSynchronize(f->ctx->stream);
-    delete f;
-    return MGBHIP_OK;
-    MGB_API_END
-}
+int mgbhip_figure_destroy(mgbhip_figure* f) { return destroy_handle(f); }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "render_device.hpp"
 #include "surface.hpp"
 
 // No fused multiply-adds in the code below or in a file that includes it: see surface.hip.
@@ -27,16 +28,11 @@ namespace mgbhip {
 
 namespace {
 
-constexpr int BLOCK = 256;
 // Every box is widened by PAD_REL * (largest extent of the union + largest |coordinate|) per side before it is cut
 // into cells.  The walk places a ray in a cell with an error of a few eps * (|origin| + |coordinate|) per axis, and a
 // computed hit point leaves the box of what it hit by as little; 2^-26 covers both for origins up to 2^20 box sizes
 // away, and is far below any cell side, so it adds no pairs to speak of.
 constexpr double PAD_REL = 1.4901161193847656e-08;   // 2^-26
-
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-__device__ inline double dnan() { return __builtin_nan(""); }
 
 // cell index of a scaled coordinate; NaN and anything below the box go to cell 0, anything above to the last cell
 __device__ inline int32_t cell_axis(double s, int32_t n) {

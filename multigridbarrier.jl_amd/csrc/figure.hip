@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "figure.hpp"
+#include "render_device.hpp"
 
 // No fused multiply-adds in this file: layers_composite and image_rgba8 then do the operations of their NumPy
 // restatements (surface.composite_layers, tests/figure_twin.py) bit for bit.
@@ -29,10 +30,6 @@
 namespace mgbhip {
 
 namespace {
-
-constexpr int BLOCK = 256;
-
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 // one lane per mesh node: u into column 1 of a slice's two-column field (column 0, the coordinate function, is resident)
 __global__ void __launch_bounds__(BLOCK) carry_column(int64_t rows, const double* __restrict__ u,
@@ -59,17 +56,9 @@ __global__ void __launch_bounds__(BLOCK) layers_composite(int64_t R, int32_t K, 
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     const double* ly = layer + r * K * 4;
-    double T = 1.0, C0 = 0.0, C1 = 0.0, C2 = 0.0;
-    for (int32_t k = 0; k < K; ++k) {
-        C0 = C0 + T * ly[k * 4];
-        C1 = C1 + T * ly[k * 4 + 1];
-        C2 = C2 + T * ly[k * 4 + 2];
-        T = T * (1.0 - ly[k * 4 + 3]);
-    }
-    out[r * 4] = C0;
-    out[r * 4 + 1] = C1;
-    out[r * 4 + 2] = C2;
-    out[r * 4 + 3] = 1.0 - T;
+    Composite acc;
+    for (int32_t k = 0; k < K; ++k) acc.layer(ly + k * 4);
+    acc.store(out + r * 4);
 }
 
 // floor(255 min(1, max(0, c)) + 0.5) as a byte; 0 for a c that is not finite
@@ -149,7 +138,7 @@ const double* frame(Figure& F, const double* u, hipStream_t st) {
     const double* t_hit = F.miss_t.p;
     if (T) {
         surface_trace_device(F.sf, R, F.o.p, F.dn.p, 0.0, std::numeric_limits<double>::infinity(), K, st);
-        surface_shade_device(F.sf, R, K, F.dn.p, F.sf.tri.p, F.sf.u.p, F.sf.v.p, F.values.p, F.in.ntable, F.stable.p,
+        surface_shade_device(F.sf, R, K, F.dn.p, F.sf.id.p, F.sf.par[0].p, F.sf.par[1].p, F.values.p, F.in.ntable, F.stable.p,
                              F.in.lo, F.in.hi, F.in.ambient, F.sf.layer.p, st);
         t_hit = F.sf.t.p;
     } else {

@@ -16,6 +16,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "raycast.hpp"
+#include "render_device.hpp"
 
 // No fused multiply-adds in this file: a plain IEEE transcription of the algorithm (tests/raycast_twin.py) then places
 // every sample at the same bits.
@@ -25,14 +26,11 @@ namespace mgbhip {
 
 namespace {
 
-constexpr int BLOCK = 256;
 constexpr double MAX_COUNT = 2147483648.0;     // a ray's count saturates at 2^31: the total then fails the S check
 
 struct Box {
     double lo[3], hi[3];
 };
-
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 // one lane per ray: the slab test against the clip box, then the number of steps and their length
 template <int D>
@@ -132,33 +130,16 @@ __global__ void __launch_bounds__(BLOCK) ray_composite(int64_t R, int32_t K, con
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     const double hr = h[r], width = hi - lo, km1 = (double)(K - 1);
-    double T = 1.0, C0 = 0.0, C1 = 0.0, C2 = 0.0;
+    Composite acc;
     const int64_t s1 = off[r + 1];
     for (int64_t s = off[r]; s < s1; ++s) {
         const double v = val[s];
         if (!isfinite(v)) continue;
-        const double sc = fmin(1.0, fmax(0.0, (v - lo) / width));
-        const double f = sc * km1;
-        int32_t j = (int32_t)floor(f);           // 0 <= f <= K - 1
-        j = j < K - 2 ? j : K - 2;
-        const double w = f - (double)j;
-        const double* t0 = table + (int64_t)j * 4;
-        const double cr = t0[0] + w * (t0[4] - t0[0]);
-        const double cg = t0[1] + w * (t0[5] - t0[1]);
-        const double cb = t0[2] + w * (t0[6] - t0[2]);
-        const double sg = t0[3] + w * (t0[7] - t0[3]);
-        const double e = exp(-(sg * hr));
-        const double alpha = 1.0 - e;
-        const double ta = T * alpha;
-        C0 += ta * cr;
-        C1 += ta * cg;
-        C2 += ta * cb;
-        T = T * e;
+        double c[4];
+        table_row(v, lo, width, km1, K, table, c);
+        acc.sample(c, hr);
     }
-    out[r * 4] = C0;
-    out[r * 4 + 1] = C1;
-    out[r * 4 + 2] = C2;
-    out[r * 4 + 3] = 1.0 - T;
+    acc.store(out + r * 4);
 }
 
 // ray_composite with up to KH opaque or translucent layers per ray merged into the samples by depth: hit k (t_hit
@@ -176,47 +157,20 @@ __global__ void __launch_bounds__(BLOCK) ray_composite_layers(int64_t R, int32_t
     const double hr = h[r], t0r = tmin[r], width = hi - lo, km1 = (double)(K - 1);
     const double* th = t_hit + r * KH;
     const double* ly = layer + r * KH * 4;
-    double T = 1.0, C0 = 0.0, C1 = 0.0, C2 = 0.0;
+    Composite acc;
     int32_t k = 0;
     const int64_t s0 = off[r], s1 = off[r + 1];
     for (int64_t s = s0; s < s1; ++s) {
         const double ti = t0r + ((double)(s - s0) + 0.5) * hr;
-        for (; k < KH && th[k] <= ti; ++k) {
-            C0 += T * ly[k * 4];
-            C1 += T * ly[k * 4 + 1];
-            C2 += T * ly[k * 4 + 2];
-            T = T * (1.0 - ly[k * 4 + 3]);
-        }
+        for (; k < KH && th[k] <= ti; ++k) acc.layer(ly + k * 4);
         const double v = val[s];
         if (!isfinite(v)) continue;
-        const double sc = fmin(1.0, fmax(0.0, (v - lo) / width));
-        const double f = sc * km1;
-        int32_t j = (int32_t)floor(f);           // 0 <= f <= K - 1
-        j = j < K - 2 ? j : K - 2;
-        const double w = f - (double)j;
-        const double* t0 = table + (int64_t)j * 4;
-        const double cr = t0[0] + w * (t0[4] - t0[0]);
-        const double cg = t0[1] + w * (t0[5] - t0[1]);
-        const double cb = t0[2] + w * (t0[6] - t0[2]);
-        const double sg = t0[3] + w * (t0[7] - t0[3]);
-        const double e = exp(-(sg * hr));
-        const double alpha = 1.0 - e;
-        const double ta = T * alpha;
-        C0 += ta * cr;
-        C1 += ta * cg;
-        C2 += ta * cb;
-        T = T * e;
+        double c[4];
+        table_row(v, lo, width, km1, K, table, c);
+        acc.sample(c, hr);
     }
-    for (; k < KH && th[k] < INFINITY; ++k) {
-        C0 += T * ly[k * 4];
-        C1 += T * ly[k * 4 + 1];
-        C2 += T * ly[k * 4 + 2];
-        T = T * (1.0 - ly[k * 4 + 3]);
-    }
-    out[r * 4] = C0;
-    out[r * 4 + 1] = C1;
-    out[r * 4 + 2] = C2;
-    out[r * 4 + 3] = 1.0 - T;
+    for (; k < KH && th[k] < INFINITY; ++k) acc.layer(ly + k * 4);
+    acc.store(out + r * 4);
 }
 
 template <int D>

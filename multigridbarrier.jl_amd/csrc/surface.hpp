@@ -28,15 +28,21 @@ struct GridWork {
     DevBuf<int32_t> v0;
 };
 
-// Resident: the soup (72 bytes per triangle), the sorted (cell, triangle) pair list (4 bytes per pair) and the cell
-// starts (4 bytes per cell).  The per-call buffers grow to the largest call seen and are kept.
-struct Surface {
-    int64_t T = 0, P = 0;
+// What a soup of n primitives in a grid keeps, whatever the primitive (soup_trace.hpp): the grid, the sorted (cell,
+// primitive) pair list (4 bytes per pair) and the cell starts (4 bytes per cell) are resident; the per-call buffers (the
+// rays, the hits as t, id and up to two parameters of the hit point, the vertex values, the colour table, the layers) grow
+// to the largest call seen and are kept.
+struct Soup {
+    int64_t n = 0, P = 0;
     SurfaceGrid g{};
-    DevBuf<double> pts;                     // T x 3 x 3
     DevBuf<int32_t> start, cand;            // ncell + 1, P
-    DevBuf<double> o, dn, t, u, v, values, table, layer;
-    DevBuf<int32_t> tri;
+    DevBuf<double> o, dn, t, par[2], values, table, layer;
+    DevBuf<int32_t> id;
+};
+
+// the triangles (72 bytes each); the hit parameters are the barycentric u, v
+struct Surface : Soup {
+    DevBuf<double> pts;                     // n x 3 x 3
 };
 
 // boxes, union, count pass, exclusive scan, emit pass, stable sort by cell; complete on return
@@ -47,7 +53,7 @@ void surface_build_device(Surface& S, int64_t T, const double* d_points, GridWor
 // o, dn host R x 3 (dn of unit length); t, u, v host R x K doubles, tri host R x K: the K nearest hits by (t, triangle)
 void surface_trace(Surface& S, int64_t R, const double* o, const double* dn, double t_min, double t_max, int32_t K,
                    double* t, int32_t* tri, double* u, double* v, hipStream_t st);
-// the same for rays on the device, T > 0: the hits are left in S.t, S.tri, S.u, S.v (R x K each); queued on st, not waited for
+// the same for rays on the device, T > 0: the hits are left in S.t, S.id, S.par[0], S.par[1] (R x K each); queued on st, not waited for
 void surface_trace_device(Surface& S, int64_t R, const double* d_o, const double* d_dn, double t_min, double t_max,
                           int32_t K, hipStream_t st);
 // tri, u, v as trace returned them; values host T x 3, table host Kt x 4 (r, g, b, alpha); layer host R x K x 4

@@ -12,15 +12,9 @@ namespace mgbhip {
 
 constexpr int TUBES_MAX_HITS = SURFACE_MAX_HITS;
 
-// Resident: the segments (48 bytes each), their radii, the sorted (cell, segment) pair list (4 bytes per pair) and the
-// cell starts (4 bytes per cell).  The per-call buffers grow to the largest call seen and are kept.
-struct Tubes {
-    int64_t S = 0, P = 0;
-    SurfaceGrid g{};
-    DevBuf<double> pts, rad;                // S x 2 x 3, S
-    DevBuf<int32_t> start, cand;            // ncell + 1, P
-    DevBuf<double> o, dn, t, s, values, table, layer;
-    DevBuf<int32_t> seg;
+// the segments (48 bytes each) and their radii; the hit parameter is the axis parameter s
+struct Tubes : Soup {
+    DevBuf<double> pts, rad;                // n x 2 x 3, n
 };
 
 // boxes (end points widened by the radius), then the grid of box_grid.hpp; complete on return

@@ -18,6 +18,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._handle import DeviceObject
 from .interpolate import _c_f64
 from .multigrid import Geometry
 from .parabolic import ParabolicSOL
@@ -52,7 +53,7 @@ def _fem3d_plan(geom, who: str):
     return family, name, k, p, N, xnodes, table
 
 
-class FigureRenderer:
+class FigureRenderer(DeviceObject):
     """`render_figure(geom, u, eye, target, ...)` for many `u`: the camera, the isosurface levels, the slices, the colour
     limits and the tables are fixed when the renderer is made, and `render(u)` is bitwise what `render_figure` returns
     for the same arguments (the same kernels run on the same inputs; only where the data lives between them differs).
@@ -70,11 +71,12 @@ class FigureRenderer:
     (cell, triangle) pairs).  Use it as a context manager or call `close()`.
     """
 
+    _closed_message = "FigureRenderer: the renderer is closed"
+    _destroy = "mgbhip_figure_destroy"
+
     def __init__(self, geom: Geometry, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0, *, isosurfaces,
                  clim, slices=None, volume: bool = True, surface_alpha: float = 1.0, step: Optional[float] = None,
                  transfer=None, ambient: float = 0.3, device_id: int = 0):
-        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
-        self.closed = False
         who = "FigureRenderer"
         family, self._name, k, self._p, self._N, xnodes, ctable = _fem3d_plan(geom, who)
         W, H = _check_size(size)
@@ -123,30 +125,15 @@ class FigureRenderer:
         self.ntriangles = self.npairs = 0
         self.levels, self.clim, self.slices = lev.copy(), (lo, hi), list(planes)
 
-        from .device import ERR_INVALID, HipContext, MGBHipError, _check, _ptr
+        from .device import _ptr
         O, Dn, box, xnodes, ctable = _c_f64(O), _c_f64(Dn), _c_f64(box), _c_f64(xnodes), _c_f64(ctable)
         table, surf_table, lev = _c_f64(table), _c_f64(surf_table), _c_f64(lev)
         axes = np.ascontiguousarray([a for a, _ in planes], dtype=np.int32)
         coords = _c_f64(np.array([c for _, c in planes], dtype=np.float64))
-        self._ctx = HipContext(device_id)
-        h = C.c_void_p()
-        try:
-            _check(self._ctx.lib, self._ctx.lib.mgbhip_figure_create(
-                self._ctx.handle, family, 3, k, self._p, self._N, _ptr(xnodes), _ptr(ctable), R, _ptr(O), _ptr(Dn),
-                _ptr(box), float(step), 1 if volume else 0, int(lev.shape[0]), _ptr(lev), len(planes),
-                axes.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(coords), int(table.shape[0]), _ptr(table),
-                _ptr(surf_table), lo, hi, ambient, K, C.byref(h)))
-        except Exception as e:
-            self._ctx.close()
-            self._ctx = None
-            if isinstance(e, MGBHipError) and e.status == ERR_INVALID:
-                raise ValueError(str(e)) from None
-            raise
-        self._handle = h
-
-    def _open(self):
-        if self.closed:
-            raise ValueError("FigureRenderer: the renderer is closed")
+        self._create(device_id, "mgbhip_figure_create", family, 3, k, self._p, self._N, _ptr(xnodes), _ptr(ctable), R,
+                     _ptr(O), _ptr(Dn), _ptr(box), float(step), 1 if volume else 0, int(lev.shape[0]), _ptr(lev),
+                     len(planes), axes.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(coords), int(table.shape[0]),
+                     _ptr(table), _ptr(surf_table), lo, hi, ambient, K, invalid_is_value_error=True)
 
     def _field(self, who: str, u) -> np.ndarray:
         U = np.asarray(u, dtype=np.float64)
@@ -187,29 +174,6 @@ class FigureRenderer:
                                                                       out.ctypes.data_as(C.POINTER(C.c_uint8))))
         self._counts()
         return out
-
-    def close(self):
-        """Free the device state; calling it again does nothing."""
-        self.closed = True
-        if self._handle is not None:
-            self._ctx.lib.mgbhip_figure_destroy(self._handle)
-            self._handle = None
-        if self._ctx is not None:
-            self._ctx.close()
-            self._ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def animation_timeline(ts, frame_time: Optional[float] = None, nframes: Optional[int] = None):

@@ -20,6 +20,7 @@ import numpy as np
 from . import fem2d_p1, fem2d_p2
 from .fem2d_p1 import FEM2D_P1
 from .fem2d_p2 import FEM2D_P2
+from ._handle import DeviceObject
 from .multigrid import Geometry
 from .spectral import SPECTRAL1D, SPECTRAL2D, evaluation
 from .tensorfem import TensorFEM, _tf_nodes
@@ -247,7 +248,7 @@ def interpolate(geom: Geometry, z, t, device_id: int = 0, return_element: bool =
     return (vals, g, elem_out) if return_element else (vals, g)
 
 
-class PointLocator:
+class PointLocator(DeviceObject):
     """The points `t` located once in `geom`, for evaluating many `z` at them: `loc.evaluate(z)` is bitwise
     `interpolate(geom, z, t)`, `loc.evaluate(z, gradient=True)` bitwise `interpolate(geom, z, t, gradient=True)` and
     `loc.elements` the elements `return_element=True` reports.
@@ -260,33 +261,21 @@ class PointLocator:
     zero points needs no device and no library.
     """
 
+    _closed_message = "PointLocator: the locator is closed"
+    _destroy = "mgbhip_locator_destroy"
+
     def __init__(self, geom: Geometry, t, device_id: int = 0):
-        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
-        self.closed = False
         self._family, self._name, self._d, k, self._p, self._N, xnodes, table = _plan(geom)
         pts, self._scalar, self._shape = _points(self._name, self._d, self._N, xnodes, t)
         self._basis = _spectral_basis(self._family, geom)
         self.n_points = int(pts.shape[0])
         if self.n_points:
-            from .device import HipContext, _check, _ptr
+            from .device import _ptr
             pts = _c_f64(pts)
             xnodes = None if xnodes is None else _c_f64(xnodes)
             table = None if table is None else _c_f64(table)
-            self._ctx = HipContext(device_id)
-            h = C.c_void_p()
-            try:
-                _check(self._ctx.lib, self._ctx.lib.mgbhip_locator_create(
-                    self._ctx.handle, self._family, self._d, k, self._p, self._N, _ptr(xnodes), _ptr(table),
-                    self.n_points, _ptr(pts), C.byref(h)))
-            except Exception:
-                self._ctx.close()
-                self._ctx = None
-                raise
-            self._handle = h
-
-    def _open(self):
-        if self.closed:
-            raise ValueError("PointLocator: the locator is closed")
+            self._create(device_id, "mgbhip_locator_create", self._family, self._d, k, self._p, self._N, _ptr(xnodes),
+                         _ptr(table), self.n_points, _ptr(pts))
 
     @property
     def elements(self):
@@ -316,26 +305,3 @@ class PointLocator:
                 self._handle, ncomp, _ptr(Zd), _ptr(out), _ptr(grad)))
         vals, g = _shape_values(out, grad, d, single, self._scalar, self._shape)
         return (vals, g) if gradient else vals
-
-    def close(self):
-        """Free the device state; calling it again does nothing."""
-        self.closed = True
-        if self._handle is not None:
-            self._ctx.lib.mgbhip_locator_destroy(self._handle)
-            self._handle = None
-        if self._ctx is not None:
-            self._ctx.close()
-            self._ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

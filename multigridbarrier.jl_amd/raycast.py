@@ -17,6 +17,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._handle import DeviceObject
 from .interpolate import P1, P2, P2C, QK, _c_f64, _columns, _plan
 from .multigrid import Geometry
 from .tensorfem import TensorFEM
@@ -167,7 +168,7 @@ def _check_clim(clim, u: np.ndarray):
     return lo, hi
 
 
-class RayCaster:
+class RayCaster(DeviceObject):
     """The rays `o + t d` sampled through `geom` once, for integrating or rendering many fields along them.
 
     `o` and `d` are `(R, dim)` (one ray may be given as `(dim,)`), with `dim` the dimension of the mesh; origins must be
@@ -198,9 +199,10 @@ class RayCaster:
     Use it as a context manager or call `close()`; a caster of zero rays needs no device and no library.
     """
 
+    _closed_message = "RayCaster: the caster is closed"
+    _destroy = "mgbhip_raycast_destroy"
+
     def __init__(self, geom: Geometry, o, d, step, t_min: float = 0.0, t_max: float = np.inf, device_id: int = 0):
-        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
-        self.closed = False
         self._family, self._name, self._d, k, self._p, self._N, xnodes, table = _raycast_plan(geom)
         dim = self._d
         O, D = np.asarray(o, dtype=np.float64), np.asarray(d, dtype=np.float64)
@@ -235,27 +237,14 @@ class RayCaster:
         self.nsamples = 0
         self._offsets = self._steps = self._lengths = None
         if R:
-            from .device import ERR_INVALID, HipContext, MGBHipError, _check, _ptr
+            from .device import _ptr
             O, Dn = _c_f64(O), _c_f64(Dn)
             box, xnodes, table = _c_f64(self.box), _c_f64(xnodes), _c_f64(table)
-            self._ctx = HipContext(device_id)
-            h, n = C.c_void_p(), C.c_int64(0)
-            try:
-                _check(self._ctx.lib, self._ctx.lib.mgbhip_raycast_create(
-                    self._ctx.handle, self._family, dim, k, self._p, self._N, _ptr(xnodes), _ptr(table), R, _ptr(O),
-                    _ptr(Dn), _ptr(box), step, t_min, t_max, C.byref(h), C.byref(n)))
-            except Exception as e:
-                self._ctx.close()
-                self._ctx = None
-                if isinstance(e, MGBHipError) and e.status == ERR_INVALID:
-                    raise ValueError(str(e)) from None
-                raise
-            self._handle = h
+            n = C.c_int64(0)
+            self._create(device_id, "mgbhip_raycast_create", self._family, dim, k, self._p, self._N, _ptr(xnodes),
+                         _ptr(table), R, _ptr(O), _ptr(Dn), _ptr(box), step, t_min, t_max, outputs=(C.byref(n),),
+                         invalid_is_value_error=True)
             self.nsamples = int(n.value)
-
-    def _open(self):
-        if self.closed:
-            raise ValueError("RayCaster: the caster is closed")
 
     @property
     def offsets(self) -> np.ndarray:
@@ -372,29 +361,6 @@ class RayCaster:
                     self._handle, _ptr(U), int(T.shape[0]), _ptr(T), lo, hi, int(TH.shape[1]), _ptr(TH), _ptr(LY),
                     _ptr(out)))
         return out
-
-    def close(self):
-        """Free the device state; calling it again does nothing."""
-        self.closed = True
-        if self._handle is not None:
-            self._ctx.lib.mgbhip_raycast_destroy(self._handle)
-            self._handle = None
-        if self._ctx is not None:
-            self._ctx.close()
-            self._ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def render_volume(geom: Geometry, u, eye, target, up=(0, 0, 1), size=(800, 600), fov: float = 30.0,

@@ -17,6 +17,7 @@ import math
 
 import numpy as np
 
+from ._handle import DeviceObject
 from .interpolate import _c_f64
 from .multigrid import Geometry
 from .raycast import _raycast_plan
@@ -117,7 +118,7 @@ def _check_trace(d: int, seeds, step, max_steps, direction, normalize, min_speed
     return P, step, int(max_steps), min_speed
 
 
-class StreamTracer:
+class StreamTracer(DeviceObject):
     """The field lines of `v = (z[:, 0], .., z[:, d-1])` (`field="vector"`: `z` is `(p*N, d)`, the columns are the
     velocity components) or of `v = grad u` (`field="gradient"`: `z` is `(p*N,)`), traced on the device.
 
@@ -145,29 +146,17 @@ class StreamTracer:
     Use it as a context manager or call `close()`.
     """
 
+    _closed_message = "StreamTracer: the tracer is closed"
+    _destroy = "mgbhip_stream_destroy"
+
     def __init__(self, geom: Geometry, z, field: str = "vector", device_id: int = 0):
-        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
-        self.closed = False
         self._family, self._name, self._d, k, self._p, self._N, xnodes, table = _raycast_plan(geom, "StreamTracer", curved_p2=True)
         self._kind = _field_kind(field)
         Z = _check_field(self._name, self._d, self._p, self._N, self._kind, z)
-        from .device import HipContext, _check, _ptr
+        from .device import _ptr
         xnodes, table, Z = _c_f64(xnodes), _c_f64(table), _c_f64(Z)
-        self._ctx = HipContext(device_id)
-        h = C.c_void_p()
-        try:
-            _check(self._ctx.lib, self._ctx.lib.mgbhip_stream_create(
-                self._ctx.handle, self._family, self._d, k, self._p, self._N, _ptr(xnodes), _ptr(table), self._kind,
-                _ptr(Z), C.byref(h)))
-        except Exception:
-            self._ctx.close()
-            self._ctx = None
-            raise
-        self._handle = h
-
-    def _open(self):
-        if self.closed:
-            raise ValueError("StreamTracer: the tracer is closed")
+        self._create(device_id, "mgbhip_stream_create", self._family, self._d, k, self._p, self._N, _ptr(xnodes),
+                     _ptr(table), self._kind, _ptr(Z))
 
     def set_field(self, z):
         """Replace the field by `z` (the shape the tracer was built with); the mesh and the grid stay resident."""
@@ -212,29 +201,6 @@ class StreamTracer:
         if direction == "backward":
             return back
         return join_both(back, self._trace_one(P, step, max_steps, bool(normalize), min_speed))
-
-    def close(self):
-        """Free the device state; calling it again does nothing."""
-        self.closed = True
-        if self._handle is not None:
-            self._ctx.lib.mgbhip_stream_destroy(self._handle)
-            self._handle = None
-        if self._ctx is not None:
-            self._ctx.close()
-            self._ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def streamlines(geom: Geometry, z, seeds, step, max_steps: int, field: str = "vector", direction: str = "forward",

@@ -22,6 +22,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._handle import DeviceObject
 from .contour import Contour, Tessellation, isocontour, tessellate
 from .interpolate import _c_f64
 from .multigrid import Geometry
@@ -109,7 +110,52 @@ def composite_layers(layers: np.ndarray) -> np.ndarray:
     return np.concatenate([Cc, (1.0 - T)[:, None]], axis=1)
 
 
-class TriangleCaster:
+def _trace_arguments(who: str, o, d, t_min, t_max, max_hits, npar: int):
+    """What both casters' `trace` check and allocate: the rays, the window, `K`, and the all-miss hit arrays `t`, index
+    and `npar` parameter arrays (`(R, K)` each)."""
+    O, Dn = _check_rays(who, o, d)
+    try:
+        t_min, t_max = float(t_min), float(t_max)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: t_min and t_max must be numbers") from None
+    if not math.isfinite(t_min):
+        raise ValueError(f"{who}: t_min must be finite (got {t_min})")
+    if not t_max > t_min:
+        raise ValueError(f"{who}: t_max must be greater than t_min (got t_min = {t_min}, t_max = {t_max})")
+    K = _check_max_hits(who, max_hits)
+    shape = (int(O.shape[0]), K)
+    return (O, Dn, t_min, t_max, K, np.full(shape, np.inf), np.full(shape, -1, dtype=np.int32),
+            [np.full(shape, np.nan) for _ in range(npar)])
+
+
+def _check_hits(who: str, R: int, n: int, rays: str, field: str, index, **others):
+    """The index array `hits.<field>` of a `shade` call (`(R, K)`, entries in -1..n-1) and the float arrays
+    `hits.<name>` of `others`, which must have its shape."""
+    idx = np.asarray(index)
+    if idx.ndim != 2 or idx.shape[0] != R or not 1 <= idx.shape[1] <= MAX_HITS:
+        raise ValueError(f"{who}: hits hold {idx.shape} entries for {R} {rays}")
+    arrays = [np.asarray(a, dtype=np.float64) for a in others.values()]
+    if any(a.shape != idx.shape for a in arrays):
+        names = " and ".join(f"hits.{name}" for name in others)
+        raise ValueError(f"{who}: {names} must have the shape of hits.{field} {idx.shape}")
+    if idx.size and (idx.min() < -1 or idx.max() >= n):
+        raise ValueError(f"{who}: hits.{field} has an index outside -1..{n - 1}")
+    return idx, arrays
+
+
+def _check_colouring(who: str, values, shape, transfer, clim, ambient):
+    """The vertex values (of `shape`), the colour table, the colour limits and the ambient term of a `shade` call."""
+    V = np.asarray(values, dtype=np.float64)
+    if V.shape != shape:
+        raise ValueError(f"{who}: values must be ({shape[0]}, {shape[1]}) (got shape {V.shape})")
+    T = default_surface_table() if transfer is None else _check_table(who, transfer)
+    if clim is None and shape[0] == 0:
+        clim = (0.0, 1.0)                    # nothing to colour
+    lo, hi = _clim(who, clim, V, "values")
+    return V, T, lo, hi, _check_ambient(who, ambient)
+
+
+class TriangleCaster(DeviceObject):
     """A triangle soup `points` (`(T, 3, 3)`: triangle, vertex, coordinate; finite) sorted once into a uniform grid of
     cells on the device, for tracing many bundles of rays against it.  `T = 0` is allowed: every ray misses and no
     device work is done.
@@ -129,9 +175,10 @@ class TriangleCaster:
     Use it as a context manager or call `close()`.
     """
 
+    _closed_message = "TriangleCaster: the caster is closed"
+    _destroy = "mgbhip_surface_destroy"
+
     def __init__(self, points, device_id: int = 0):
-        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
-        self.closed = False
         P = np.asarray(points, dtype=np.float64)
         if P.ndim != 3 or P.shape[1:] != (3, 3):
             raise ValueError(f"TriangleCaster: points must be (T, 3, 3) (got shape {P.shape})")
@@ -139,41 +186,15 @@ class TriangleCaster:
             raise ValueError("TriangleCaster: every entry of points must be finite")
         self.ntriangles = T = int(P.shape[0])
         if T:
-            from .device import HipContext, _check, _ptr
-            P = _c_f64(P)
-            self._ctx = HipContext(device_id)
-            h = C.c_void_p()
-            try:
-                _check(self._ctx.lib, self._ctx.lib.mgbhip_surface_create(self._ctx.handle, T, _ptr(P), C.byref(h)))
-            except Exception:
-                self._ctx.close()
-                self._ctx = None
-                raise
-            self._handle = h
-
-    def _open(self):
-        if self.closed:
-            raise ValueError("TriangleCaster: the caster is closed")
+            from .device import _ptr
+            self._create(device_id, "mgbhip_surface_create", T, _ptr(_c_f64(P)))
 
     def trace(self, o, d, t_min: float = 0.0, t_max: float = np.inf, max_hits: int = 1) -> Hits:
         """The `max_hits` (1..8) nearest hits of every ray `o + t d` (`(R, 3)` each; one ray may be given as `(3,)`) with
         `t_min <= t <= t_max`; `t` is arc length."""
         self._open()
-        O, Dn = _check_rays("TriangleCaster.trace", o, d)
-        try:
-            t_min, t_max = float(t_min), float(t_max)
-        except (TypeError, ValueError):
-            raise ValueError("TriangleCaster.trace: t_min and t_max must be numbers") from None
-        if not math.isfinite(t_min):
-            raise ValueError(f"TriangleCaster.trace: t_min must be finite (got {t_min})")
-        if not t_max > t_min:
-            raise ValueError(f"TriangleCaster.trace: t_max must be greater than t_min (got t_min = {t_min}, "
-                             f"t_max = {t_max})")
-        K = _check_max_hits("TriangleCaster.trace", max_hits)
+        O, Dn, t_min, t_max, K, t, tri, (u, v) = _trace_arguments("TriangleCaster.trace", o, d, t_min, t_max, max_hits, 2)
         R = int(O.shape[0])
-        t = np.full((R, K), np.inf)
-        tri = np.full((R, K), -1, dtype=np.int32)
-        u, v = np.full((R, K), np.nan), np.full((R, K), np.nan)
         if R and self.ntriangles:
             from .device import _check, _ptr
             O, Dn = _c_f64(O), _c_f64(Dn)
@@ -198,23 +219,9 @@ class TriangleCaster:
             raise ValueError(f"{who}: hits must be what trace() returned (got {type(hits).__name__})")
         _, Dn = _check_rays(who, np.zeros_like(np.asarray(d, dtype=np.float64)), d)
         R = int(Dn.shape[0])
-        tri = np.asarray(hits.triangle)
-        if tri.ndim != 2 or tri.shape[0] != R or not 1 <= tri.shape[1] <= MAX_HITS:
-            raise ValueError(f"{who}: hits hold {tri.shape} entries for {R} directions d")
+        tri, (hu, hv) = _check_hits(who, R, self.ntriangles, "directions d", "triangle", hits.triangle, u=hits.u, v=hits.v)
         K = int(tri.shape[1])
-        hu, hv = np.asarray(hits.u, dtype=np.float64), np.asarray(hits.v, dtype=np.float64)
-        if hu.shape != tri.shape or hv.shape != tri.shape:
-            raise ValueError(f"{who}: hits.u and hits.v must have the shape of hits.triangle {tri.shape}")
-        if tri.size and (tri.min() < -1 or tri.max() >= self.ntriangles):
-            raise ValueError(f"{who}: hits.triangle has an index outside -1..{self.ntriangles - 1}")
-        V = np.asarray(values, dtype=np.float64)
-        if V.shape != (self.ntriangles, 3):
-            raise ValueError(f"{who}: values must be ({self.ntriangles}, 3) (got shape {V.shape})")
-        T = default_surface_table() if transfer is None else _check_table(who, transfer)
-        if clim is None and self.ntriangles == 0:
-            clim = (0.0, 1.0)                    # nothing to colour
-        lo, hi = _clim(who, clim, V, "values")
-        ambient = _check_ambient(who, ambient)
+        V, T, lo, hi, ambient = _check_colouring(who, values, (self.ntriangles, 3), transfer, clim, ambient)
         layer = np.zeros((R, K, 4))
         if R and self.ntriangles:
             from .device import _check, _ptr
@@ -224,29 +231,6 @@ class TriangleCaster:
                 self._handle, R, K, _ptr(Dn), tri.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(hu), _ptr(hv), _ptr(V),
                 int(T.shape[0]), _ptr(T), lo, hi, ambient, _ptr(layer)))
         return layer
-
-    def close(self):
-        """Free the device state; calling it again does nothing."""
-        self.closed = True
-        if self._handle is not None:
-            self._ctx.lib.mgbhip_surface_destroy(self._handle)
-            self._handle = None
-        if self._ctx is not None:
-            self._ctx.close()
-            self._ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _soup(who: str, contours, values, levels):

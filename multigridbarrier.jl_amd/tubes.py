@@ -19,13 +19,14 @@ from typing import Optional
 
 import numpy as np
 
+from ._handle import DeviceObject
 from .contour import Contour
 from .interpolate import _c_f64
 from .multigrid import Geometry
 from .raycast import _check_size, camera_rays
 from .streamlines import Streamlines
-from .surface import (MAX_HITS, _check_ambient, _check_max_hits, _check_rays, _check_table, _clim, composite_layers,
-                      default_surface_table)
+from .surface import (MAX_HITS, _check_ambient, _check_colouring, _check_hits, _check_max_hits, _check_rays, _check_table,
+                      _clim, _trace_arguments, composite_layers, default_surface_table)
 from .tensorfem import TensorFEM
 
 REFERENCE_RADIUS = 0.01     # plot3d.jl:300-301: the tube radius as a fraction of the bounding-box diagonal
@@ -53,7 +54,7 @@ def _check_radius(who: str, radius, S: int, name: str = "radius") -> np.ndarray:
     return r
 
 
-class SegmentCaster:
+class SegmentCaster(DeviceObject):
     """A soup of segments `points` (`(S, 2, 3)`: segment, end point, coordinate; finite) with a `radius` each (a positive
     finite number, or `(S,)` of them), sorted once into a uniform grid of cells on the device, for tracing many bundles
     of rays against the capsules around them.  `S = 0` is allowed: every ray misses and no device work is done.
@@ -78,9 +79,10 @@ class SegmentCaster:
     Use it as a context manager or call `close()`.
     """
 
+    _closed_message = "SegmentCaster: the caster is closed"
+    _destroy = "mgbhip_tubes_destroy"
+
     def __init__(self, points, radius, device_id: int = 0):
-        self._handle = self._ctx = None          # first: __del__ runs even when a check below raises
-        self.closed = False
         P = np.asarray(points, dtype=np.float64)
         if P.ndim != 3 or P.shape[1:] != (2, 3):
             raise ValueError(f"SegmentCaster: points must be (S, 2, 3) (got shape {P.shape})")
@@ -89,41 +91,15 @@ class SegmentCaster:
         self.nsegments = S = int(P.shape[0])
         rad = _check_radius("SegmentCaster", radius, S)
         if S:
-            from .device import HipContext, _check, _ptr
-            P, rad = _c_f64(P), _c_f64(rad)
-            self._ctx = HipContext(device_id)
-            h = C.c_void_p()
-            try:
-                _check(self._ctx.lib, self._ctx.lib.mgbhip_tubes_create(self._ctx.handle, S, _ptr(P), _ptr(rad), C.byref(h)))
-            except Exception:
-                self._ctx.close()
-                self._ctx = None
-                raise
-            self._handle = h
-
-    def _open(self):
-        if self.closed:
-            raise ValueError("SegmentCaster: the caster is closed")
+            from .device import _ptr
+            self._create(device_id, "mgbhip_tubes_create", S, _ptr(_c_f64(P)), _ptr(_c_f64(rad)))
 
     def trace(self, o, d, t_min: float = 0.0, t_max: float = np.inf, max_hits: int = 1) -> TubeHits:
         """The `max_hits` (1..8) nearest hits of every ray `o + t d` (`(R, 3)` each; one ray may be given as `(3,)`) with
         `t_min <= t <= t_max`; `t` is arc length."""
         self._open()
-        who = "SegmentCaster.trace"
-        O, Dn = _check_rays(who, o, d)
-        try:
-            t_min, t_max = float(t_min), float(t_max)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: t_min and t_max must be numbers") from None
-        if not math.isfinite(t_min):
-            raise ValueError(f"{who}: t_min must be finite (got {t_min})")
-        if not t_max > t_min:
-            raise ValueError(f"{who}: t_max must be greater than t_min (got t_min = {t_min}, t_max = {t_max})")
-        K = _check_max_hits(who, max_hits)
+        O, Dn, t_min, t_max, K, t, seg, (s,) = _trace_arguments("SegmentCaster.trace", o, d, t_min, t_max, max_hits, 1)
         R = int(O.shape[0])
-        t = np.full((R, K), np.inf)
-        seg = np.full((R, K), -1, dtype=np.int32)
-        s = np.full((R, K), np.nan)
         if R and self.nsegments:
             from .device import _check, _ptr
             O, Dn = _c_f64(O), _c_f64(Dn)
@@ -148,26 +124,12 @@ class SegmentCaster:
             raise ValueError(f"{who}: hits must be what trace() returned (got {type(hits).__name__})")
         O, Dn = _check_rays(who, o, d)
         R = int(Dn.shape[0])
-        seg = np.asarray(hits.segment)
-        if seg.ndim != 2 or seg.shape[0] != R or not 1 <= seg.shape[1] <= MAX_HITS:
-            raise ValueError(f"{who}: hits hold {seg.shape} entries for {R} rays o, d")
+        seg, (ht, hs) = _check_hits(who, R, self.nsegments, "rays o, d", "segment", hits.segment, t=hits.t, s=hits.s)
         K = int(seg.shape[1])
-        ht, hs = np.asarray(hits.t, dtype=np.float64), np.asarray(hits.s, dtype=np.float64)
-        if ht.shape != seg.shape or hs.shape != seg.shape:
-            raise ValueError(f"{who}: hits.t and hits.s must have the shape of hits.segment {seg.shape}")
-        if seg.size and (seg.min() < -1 or seg.max() >= self.nsegments):
-            raise ValueError(f"{who}: hits.segment has an index outside -1..{self.nsegments - 1}")
         there = seg >= 0
         if not (np.all(np.isfinite(ht[there])) and np.all((hs[there] >= 0.0) & (hs[there] <= 1.0))):
             raise ValueError(f"{who}: every hit of hits needs a finite hits.t and a hits.s in [0, 1]")
-        V = np.asarray(values, dtype=np.float64)
-        if V.shape != (self.nsegments, 2):
-            raise ValueError(f"{who}: values must be ({self.nsegments}, 2) (got shape {V.shape})")
-        T = default_surface_table() if transfer is None else _check_table(who, transfer)
-        if clim is None and self.nsegments == 0:
-            clim = (0.0, 1.0)                    # nothing to colour
-        lo, hi = _clim(who, clim, V, "values")
-        ambient = _check_ambient(who, ambient)
+        V, T, lo, hi, ambient = _check_colouring(who, values, (self.nsegments, 2), transfer, clim, ambient)
         layer = np.zeros((R, K, 4))
         if R and self.nsegments:
             from .device import _check, _ptr
@@ -177,29 +139,6 @@ class SegmentCaster:
                 self._handle, R, K, _ptr(O), _ptr(Dn), _ptr(ht), seg.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(hs),
                 _ptr(V), int(T.shape[0]), _ptr(T), lo, hi, ambient, _ptr(layer)))
         return layer
-
-    def close(self):
-        """Free the device state; calling it again does nothing."""
-        self.closed = True
-        if self._handle is not None:
-            self._ctx.lib.mgbhip_tubes_destroy(self._handle)
-            self._handle = None
-        if self._ctx is not None:
-            self._ctx.close()
-            self._ctx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------------------------------------------

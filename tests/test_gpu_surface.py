@@ -18,7 +18,8 @@ from mgb_amd.surface import TriangleCaster, render_figure, render_surfaces
 from raycast_twin import clip_box_twin, rays_twin
 from surface_twin import composite_twin, normalize_twin, sample_margin, shade_twin, trace_twin
 from test_raycast import CLIM, EPS, TABLE5, smooth
-from test_surface import GPU_CASES, HITS, MARGIN, NRAYS, case_soup, soup_dup, sphere_geom, vertex_values
+from test_surface import (GPU_CASES, HITS, MARGIN, NRAYS, UNIT, case_soup, rays65, soup_dup, soup_span, sphere_geom,
+                          vertex_values)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +52,51 @@ def test_trace_is_bitwise_the_twins(case, R, K):
     again = tc.trace(o[:R], d[:R], t_min, t_max, max_hits=K)
     for a, b in ((h.t, again.t), (h.triangle, again.triangle), (h.u, again.u), (h.v, again.v)):
         assert np.array_equal(a, b, equal_nan=True), "two trace calls are bitwise equal"
+
+
+def assert_hits_are_the_twins(h, twin, K, what):
+    t, tri, u, v = (a[:, :K] for a in twin)                # the K nearest are the first K of the 8 nearest
+    assert h.triangle.shape == (65, K) and np.array_equal(h.triangle, tri), what
+    assert np.array_equal(h.t, t, equal_nan=True), what
+    assert np.array_equal(h.u, u, equal_nan=True) and np.array_equal(h.v, v, equal_nan=True), what
+
+
+@pytest.fixture(params=["dup", "random257"], scope="module")
+def dispatch_case(request):
+    name = request.param
+    pts, o, d, t_min, t_max, tie = case_soup(name)
+    twin = trace_twin(pts, o, d, t_min, t_max, 8)[:4]
+    with TriangleCaster(pts) as tc:
+        yield name, o, d, t_min, t_max, twin, tc
+
+
+@pytest.mark.parametrize("K", range(1, 9))
+def test_every_hit_count_is_bitwise_the_twins(dispatch_case, K):
+    """Every case of the one dispatch over the hit count, at one full wave plus one lane."""
+    name, o, d, t_min, t_max, twin, tc = dispatch_case
+    assert_hits_are_the_twins(tc.trace(o, d, t_min, t_max, max_hits=K), twin, K, (name, K))
+
+
+@pytest.fixture(scope="module")
+def span_case():
+    pts = soup_span()
+    o, d = rays65(*UNIT)
+    twin = trace_twin(pts, o, d, 0.02, 2.35, 8)[:4]
+    with TriangleCaster(pts) as tc:
+        yield o, d, twin, tc
+
+
+@pytest.mark.parametrize("K", [1, 8])
+def test_a_triangle_met_in_several_cells_is_kept_once(span_case, K):
+    """A kept triangle is skipped before it is tested when a later cell lists it again: the hits are the twin's, which has
+    no grid, bit for bit, and the large triangle (index 0) is among them (test_surface.py shows that on the twin)."""
+    o, d, twin, tc = span_case
+    h = tc.trace(o, d, 0.02, 2.35, max_hits=K)
+    assert_hits_are_the_twins(h, twin, K, K)
+    assert (h.triangle == 0).any(), "the large triangle is kept by some ray"
+    for r in range(65):
+        kept = h.triangle[r][h.triangle[r] >= 0]
+        assert len(set(kept.tolist())) == kept.size, "no triangle is kept twice"
 
 
 def test_ties_go_to_the_lower_index():

@@ -65,6 +65,35 @@ def test_trace_matches_the_twin(case, R, K):
         assert np.array_equal(a, b, equal_nan=True), "two trace calls are bitwise equal"
 
 
+@pytest.fixture(params=["dup", "helix"], scope="module")
+def dispatch_case(request):
+    name = request.param
+    pts, rad, o, d, t_min, t_max = case_tubes(name)
+    twin = trace_twin(pts, rad, o, d, t_min, t_max, 8)
+    with SegmentCaster(pts, rad) as sc:
+        yield name, o, d, t_min, t_max, twin, sc
+
+
+@pytest.mark.parametrize("K", range(1, 9))
+def test_every_hit_count_matches_the_twin(dispatch_case, K):
+    """Every case of the one dispatch over the hit count, at one full wave plus one lane, with the bounds of
+    test_trace_matches_the_twin."""
+    name, o, d, t_min, t_max, twin, sc = dispatch_case
+    h = sc.trace(o, d, t_min, t_max, max_hits=K)
+    t, seg, s, piece = (a[:, :K] for a in (twin.t, twin.segment, twin.s, twin.piece))      # the first K of the 8 nearest
+    bt, bs = t_bound(twin)[:, :K], s_bound(twin)[:, :K]
+    assert h.segment.shape == (65, K) and np.array_equal(h.segment, seg), (name, K)
+    assert np.array_equal(piece_of(h.s, h.segment), piece), (name, K)
+    hit = seg >= 0
+    assert hit.any() and np.isinf(h.t[~hit]).all() and (h.t[~hit] > 0).all() and np.isnan(h.s[~hit]).all()
+    side = hit & (bs > 0)
+    rt = float((np.abs(h.t[hit] - t[hit]) / bt[hit]).max())
+    rs = float((np.abs(h.s[side] - s[side]) / bs[side]).max()) if side.any() else 0.0
+    print(f"{name} K = {K}: max error / bound, t {rt:.3e}, s {rs:.3e}")
+    assert rt <= 1.0 and rs <= 1.0, (name, K, rt, rs)
+    assert np.array_equal(h.s[hit & ~side], s[hit & ~side]), "s is 0 or 1 exactly on the caps"
+
+
 def test_ties_go_to_the_lower_index():
     """The deliberate tie, outside the margin condition: a duplicated segment.  Both are reported, the lower index
     first, with equal t."""

@@ -53,6 +53,13 @@ def soup_big():
     return np.concatenate([soup_random(32, 5), big, soup_random(32, 6)])
 
 
+def soup_span():
+    """One triangle across the whole unit box, then 64 small ones: the grid has many cells and the large triangle is in the
+    lists of several cells along one ray, so a ray that keeps it meets it again in later cells."""
+    big = np.array([[[-0.02, -0.03, 0.31], [1.04, 0.02, 0.47], [0.45, 1.05, 0.72]]])
+    return np.concatenate([big, soup_random(64, 7)])
+
+
 def sphere_geom():
     return m.subdivide(m.fem3d(k=1), 3)             # 4 x 4 x 4 elements
 
@@ -154,6 +161,22 @@ def test_gpu_cases_meet_the_margin_condition_on_the_twin(name):
     cut_hi = (inside & (pr.t > t_max)).any()
     if name != "one":
         assert cut_lo or cut_hi, "a hit that t_min or t_max cuts off"
+
+
+def test_span_soup_keeps_its_large_triangle_on_the_twin():
+    """What test_gpu_surface.py's test of a triangle met in several cells relies on, from the twin alone: the margin
+    condition of a bitwise comparison, and rays that keep the large triangle (index 0) for K = 1 and K = 8."""
+    pts = soup_span()
+    o, d = rays65(*UNIT)
+    t, tri, u, v, pr = trace_twin(pts, o, d, 0.02, 2.35, 8)
+    margin, gap = margin_twin(pr, 0.02, 2.35)
+    first, kept = int((tri[:, 0] == 0).sum()), int((tri == 0).any(axis=1).sum())
+    print(f"span: margin {margin:.3e}, gap {gap:.3e}; the large triangle is the nearest hit of {first} rays and among the "
+          f"8 nearest of {kept}")
+    assert margin > MARGIN and gap > MARGIN
+    assert first >= 1 and kept > first, "kept as the nearest hit (K = 1) and behind others (K = 8)"
+    ext = pts[0].max(axis=0) - pts[0].min(axis=0)
+    assert (ext[:2] > 1.0).all() and (pts[1:].max(axis=1) - pts[1:].min(axis=1)).max() < 0.7
 
 
 def test_large_cases_have_rays_with_many_hits():
