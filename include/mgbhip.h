@@ -449,6 +449,34 @@ int mgbhip_tessellate_fetch(const mgbhip_tessellation* t, double* points, int32_
                             double* values /* or NULL */);
 int mgbhip_tessellate_destroy(mgbhip_tessellation* t); /* NULL is a no-op */
 
+/* ---- welding: an indexed mesh, its components and vertex normals from a simplex soup ------------------------------
+ * points is S x nv x e [simplex, corner, coordinate], nv in {2, 3} [segments, triangles], e in {2, 3}; the M = S nv
+ * corners are numbered simplex-major.  group is S int32, or NULL [all zeros].  Two corners are linked iff their simplices
+ * have the same group and fabs(x_a - y_a) <= tol on every axis a [one IEEE subtraction and one compare per axis].  A
+ * vertex is a connected component of the link graph [chains weld]; vertices are numbered by their lowest corner,
+ * first_corner[v], and the position of vertex v is that corner's: nothing is averaged.  cells [S x nv] holds the vertex of
+ * every corner; a simplex with two corners in one vertex is kept.  The component of a vertex is its connected component
+ * in the graph of the simplex edges, numbered by lowest vertex.  With want_normals [nv = e = 3 only] the normal of a
+ * vertex is the sum of cross(p1 - p0, p2 - p0) over the triangles of its corners in ascending corner order, divided by
+ * sqrt((nx nx + ny ny) + nz nz), or all zeros when that root is 0 or not finite [no fused multiply-add].
+ * The corners are put into a uniform grid of cell side max(tol, largest extent / 2^20) and sorted by cell once; more than
+ * 1024 corners in one cell is MGBHIP_ERR_INVALID [the count and tol are named] before any pair is tested, as are a
+ * non-finite coordinate, S <= 0, nv or e outside its set, S nv >= 2^31, a negative or non-finite tol and want_normals
+ * with (nv, e) != (3, 3).  Classes and components are labelled by hooking and shortcutting with integer atomicMin; the
+ * results do not depend on the order of the atomics and two calls return bitwise equal arrays.  create leaves the index
+ * on the device, frees its work buffers and reports V and the number of components; fetch copies it out [normals V x 3,
+ * or NULL]; rounds reports how many labelling rounds the vertex classes and the components took.  The handle belongs to
+ * the context it was created from and must be destroyed before it.  Host pointers; the work runs on ctx's stream and is
+ * complete on return.                                                                                                */
+typedef struct mgbhip_weld mgbhip_weld;
+int mgbhip_weld_create(mgbhip_ctx* ctx, int64_t S, int32_t nv, int32_t e, const double* points,
+                       const int32_t* group /* S, or NULL */, double tol, int32_t want_normals,
+                       mgbhip_weld** out, int64_t* V, int64_t* ncomponents);
+int mgbhip_weld_fetch(const mgbhip_weld* w, int32_t* cells /* S x nv */, int32_t* first_corner /* V */,
+                      int32_t* component /* V */, double* normals /* V x 3, or NULL */);
+int mgbhip_weld_rounds(const mgbhip_weld* w, int32_t* vertex_rounds, int32_t* component_rounds);
+int mgbhip_weld_destroy(mgbhip_weld* w); /* NULL is a no-op */
+
 /* ---- ray casting: line integrals and volume rendering of an element-space function --------------------------------
  * R rays x = origin + t dir [R x d each, row-major; dir of unit length, so t is arc length] are clipped to
  * [t_min, t_max] and against the axis-parallel box [box: 2 d doubles, lo then hi] by the slab test: for an axis a with

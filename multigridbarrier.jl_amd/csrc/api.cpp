@@ -17,6 +17,7 @@
 #include "stream.hpp"
 #include "surface.hpp"
 #include "tubes.hpp"
+#include "weld.hpp"
 
 using namespace mgbhip;
 
@@ -60,6 +61,7 @@ struct Handle {
 struct mgbhip_locator : Handle<Locator> {};            // a point locator (interpolate.hpp)
 struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
 struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
+struct mgbhip_weld : Handle<Weld> {};                  // the index of a welded soup (weld.hpp)
 struct mgbhip_raycast : Handle<RayCaster> {};          // a ray caster (raycast.hpp)
 struct mgbhip_surface : Handle<Surface> {};            // a triangle soup in its grid (surface.hpp)
 struct mgbhip_tubes : Handle<Tubes> {};                // a capsule soup in its grid (tubes.hpp)
@@ -1019,6 +1021,47 @@ int mgbhip_tessellate_fetch(const mgbhip_tessellation* t, double* points, int32_
 }
 
 int mgbhip_tessellate_destroy(mgbhip_tessellation* t) { return destroy_handle(t); }
+
+int mgbhip_weld_create(mgbhip_ctx* ctx, int64_t S, int32_t nv, int32_t e, const double* points, const int32_t* group,
+                       double tol, int32_t want_normals, mgbhip_weld** out, int64_t* V, int64_t* ncomponents) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr && V != nullptr && ncomponents != nullptr, "null output pointer");
+    MGB_REQUIRE(S > 0, "weld: no simplices (S <= 0)");
+    MGB_REQUIRE(nv == 2 || nv == 3, "weld: nv must be 2 (segments) or 3 (triangles)");
+    MGB_REQUIRE(e == 2 || e == 3, "weld: e must be 2 or 3");
+    MGB_REQUIRE(S < ((int64_t)INT32_MAX + 1) / nv, "weld: S x nv corners exceed 32-bit indexing (M >= 2^31)");
+    MGB_REQUIRE(std::isfinite(tol) && tol >= 0.0, "weld: tol must be finite and >= 0");
+    MGB_REQUIRE(!want_normals || (nv == 3 && e == 3), "weld: normals need triangles in R^3 (nv = 3, e = 3)");
+    MGB_REQUIRE(points != nullptr, "weld: null points");
+    WeldIn in;
+    in.S = S; in.nv = nv; in.e = e; in.points = points; in.group = group; in.tol = tol; in.want_normals = want_normals != 0;
+    create_handle(ctx, out, [&](Weld& W) { weld_build(W, in, ctx->stream); });
+    *V = (*out)->obj.V;
+    *ncomponents = (*out)->obj.ncomp;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_weld_fetch(const mgbhip_weld* w, int32_t* cells, int32_t* first_corner, int32_t* component, double* normals) {
+    MGB_API_BEGIN_ON(w)
+    MGB_REQUIRE(w != nullptr, "weld_fetch: null weld");
+    MGB_REQUIRE(cells != nullptr && first_corner != nullptr && component != nullptr, "weld_fetch: null argument");
+    weld_fetch(w->obj, cells, first_corner, component, normals, w->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_weld_rounds(const mgbhip_weld* w, int32_t* vertex_rounds, int32_t* component_rounds) {
+    MGB_API_BEGIN
+    MGB_REQUIRE(w != nullptr && vertex_rounds != nullptr && component_rounds != nullptr, "weld_rounds: null argument");
+    *vertex_rounds = w->obj.vertex_rounds;
+    *component_rounds = w->obj.component_rounds;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_weld_destroy(mgbhip_weld* w) { return destroy_handle(w); }
 
 int mgbhip_raycast_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
                           const double* table, int64_t R, const double* origin, const double* dir, const double* box,

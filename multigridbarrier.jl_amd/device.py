@@ -119,6 +119,7 @@ EXPORTS = [
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
     "mgbhip_tessellate_create", "mgbhip_tessellate_fetch", "mgbhip_tessellate_destroy",
+    "mgbhip_weld_create", "mgbhip_weld_fetch", "mgbhip_weld_rounds", "mgbhip_weld_destroy",
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
     "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy", "mgbhip_raycast_render_layers",
     "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
@@ -221,6 +222,11 @@ def load_library():
     lib.mgbhip_tessellate_destroy.argtypes = [vp]
     lib.mgbhip_contour_fetch.argtypes = [vp, _dp, _ip, _ip, _dp]
     lib.mgbhip_contour_destroy.argtypes = [vp]
+    lib.mgbhip_weld_create.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, _dp, _ip, C.c_double, C.c_int32, C.POINTER(vp),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mgbhip_weld_fetch.argtypes = [vp, _ip, _ip, _ip, _dp]
+    lib.mgbhip_weld_rounds.argtypes = [vp, _ip, _ip]
+    lib.mgbhip_weld_destroy.argtypes = [vp]
     lib.mgbhip_raycast_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int64,
                                           _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.POINTER(vp),
                                           C.POINTER(C.c_int64)]
