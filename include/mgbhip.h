@@ -381,6 +381,33 @@ int mgbhip_locator_evaluate(mgbhip_locator* loc, int32_t ncomp, const double* z 
                             double* grad /* M x ncomp x d, or NULL: values only */);
 int mgbhip_locator_destroy(mgbhip_locator* loc); /* NULL is a no-op */
 
+/* ---- closest point: evaluate element-space functions on embedded curves and surfaces ----------------------------
+ * N Q_k elements of dimension d in e > d coordinates [(d, e) = (1, 2), (1, 3) or (2, 3); 1 <= k <= 8; x: (p N) x e with
+ * p = (k + 1)^d nodes per element, axis 0 fastest; nodes: the k + 1 reference nodes in [-1, 1]].  create projects the M
+ * points [pts: M x e] once: per point, among the elements that come within max_distance [finite, >= 0] of it, the point
+ * of least distance [the foot], found per candidate element by a projected Newton iteration on |x(xi) - pt|^2 over
+ * [-1, 1]^d from the element's node nearest to the point [at most 64 iterations; a candidate that does not converge
+ * competes with the distance at its last iterate].  Candidates are visited in ascending element index and a later one
+ * wins only on a strictly smaller distance.  A point with no foot within max_distance, outside the padded box of the
+ * mesh or with a non-finite coordinate has element -1.  x, nodes and pts are copied.  M = 0 is allowed: every call is
+ * then a no-op.  A handle belongs to the context it was created from and must be destroyed before it.
+ *  - fetch [any output may be NULL], by point: elem [M], xi [M x d, the reference coordinates of the foot], foot [M x e],
+ *    dist [M], flag [M: 1 where the winning candidate's iteration met its stopping test]; NaN where elem is -1.
+ *  - evaluate: out[q][c] = sum_i phi_i(xi_q) z[i][c] over the nodes of point q's element; grad [M x ncomp x e, or NULL:
+ *    values only] the tangential gradient J (J^T J)^-1 grad_xi u with J = dx/dxi at the foot [a curve: (du/dxi) x' /
+ *    |x'|^2].  The values are bitwise the same with and without grad; a point without an element has NaN everywhere.
+ *    ncomp may differ from call to call.                                                                            */
+typedef struct mgbhip_closest mgbhip_closest;
+int mgbhip_closest_create(mgbhip_ctx* ctx, int32_t d, int32_t e, int32_t k, int64_t N, const double* x,
+                          const double* nodes, int64_t M, const double* pts, double max_distance,
+                          mgbhip_closest** out);
+int mgbhip_closest_fetch(const mgbhip_closest* cp, int32_t* elem /* M */, double* xi /* M x d */,
+                         double* foot /* M x e */, double* dist /* M */, int32_t* flag /* M */);
+int mgbhip_closest_evaluate(mgbhip_closest* cp, int32_t ncomp, const double* z /* (p*N) x ncomp */,
+                            double* out /* M x ncomp, may be NULL when grad is given */,
+                            double* grad /* M x ncomp x e, or NULL: values only */);
+int mgbhip_closest_destroy(mgbhip_closest* cp); /* NULL is a no-op */
+
 /* ---- level sets: level curves (d = 2) and isosurfaces (d = 3) of an element-space function ------------------------
  * Every element is sampled on a uniform reference lattice of refine + 1 points per axis (Q_k; axis 0 fastest) or on
  * the barycentric lattice of the refine-fold uniform subdivision (P1 / P2) with its own basis; a lattice square is

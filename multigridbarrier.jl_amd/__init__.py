@@ -26,6 +26,7 @@ try:  # the device layer needs the built shared library; importing the setup lay
                          default_device, default_device_set, mgb_cleanup, library_path)
     from .solve import mgb_solve, MGBSOL, MGBConvergenceFailure
     from .interpolate import interpolate, PointLocator
+    from .closest import closest_point, ClosestPointLocator
     from .contour import isocontour, Contour, tessellate, Tessellation
     from .raycast import RayCaster, camera_rays, render_volume
     from .surface import TriangleCaster, Hits, render_surfaces, render_figure

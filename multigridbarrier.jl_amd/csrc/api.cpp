@@ -9,6 +9,7 @@
 #include <memory>
 #include <string>
 
+#include "closest.hpp"
 #include "contour.hpp"
 #include "figure.hpp"
 #include "interpolate.hpp"
@@ -59,6 +60,7 @@ struct Handle {
     T obj;
 };
 struct mgbhip_locator : Handle<Locator> {};            // a point locator (interpolate.hpp)
+struct mgbhip_closest : Handle<Closest> {};            // a closest-point locator (closest.hpp)
 struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
 struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
 struct mgbhip_weld : Handle<Weld> {};                  // the index of a welded soup (weld.hpp)
@@ -931,6 +933,49 @@ int mgbhip_locator_evaluate(mgbhip_locator* loc, int32_t ncomp, const double* z,
 }
 
 int mgbhip_locator_destroy(mgbhip_locator* loc) { return destroy_handle(loc); }
+
+int mgbhip_closest_create(mgbhip_ctx* ctx, int32_t d, int32_t e, int32_t k, int64_t N, const double* x,
+                          const double* nodes, int64_t M, const double* pts, double max_distance,
+                          mgbhip_closest** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE((d == 1 && (e == 2 || e == 3)) || (d == 2 && e == 3),
+                "closest_point: (d, e) must be (1, 2), (1, 3) or (2, 3)");
+    MGB_REQUIRE(k >= 1 && k <= INTERP_MAX_DEGREE, "closest_point: element degree out of range");
+    MGB_REQUIRE(N > 0, "closest_point: no elements (N = 0)");
+    MGB_REQUIRE(M >= 0, "closest_point: bad sizes");
+    MGB_REQUIRE(x != nullptr && nodes != nullptr && (M == 0 || pts != nullptr), "null argument");
+    MGB_REQUIRE(std::isfinite(max_distance) && max_distance >= 0.0, "closest_point: max_distance must be finite and >= 0");
+    const int64_t p = d == 1 ? k + 1 : (int64_t)(k + 1) * (k + 1);
+    MGB_REQUIRE(p * N * e < (int64_t)INT32_MAX && M * e < (int64_t)INT32_MAX, "closest_point: sizes exceed 32-bit indexing");
+    create_handle(ctx, out, [&](Closest& Cl) { closest_build(Cl, d, e, k, N, x, nodes, M, pts, max_distance, ctx->stream); });
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_closest_fetch(const mgbhip_closest* cp, int32_t* elem, double* xi, double* foot, double* dist, int32_t* flag) {
+    MGB_API_BEGIN_ON(cp)
+    MGB_REQUIRE(cp != nullptr, "null closest-point locator");
+    closest_fetch(cp->obj, elem, xi, foot, dist, flag, cp->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_closest_evaluate(mgbhip_closest* cp, int32_t ncomp, const double* z, double* out, double* grad) {
+    MGB_API_BEGIN_ON(cp)
+    MGB_REQUIRE(cp != nullptr, "null closest-point locator");
+    const Closest& Cl = cp->obj;
+    MGB_REQUIRE(ncomp >= 1, "closest_point: bad sizes");
+    MGB_REQUIRE(z != nullptr && (Cl.M == 0 || out != nullptr || grad != nullptr), "null argument");
+    MGB_REQUIRE(Cl.M * ncomp * (grad ? Cl.e : 1) < (int64_t)INT32_MAX && (int64_t)Cl.p * Cl.N * ncomp < (int64_t)INT32_MAX,
+                "closest_point: sizes exceed 32-bit indexing");
+    closest_evaluate(cp->obj, ncomp, z, out, grad, cp->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_closest_destroy(mgbhip_closest* cp) { return destroy_handle(cp); }
 
 int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
                                    const double* x, const double* table, int32_t nfield, const double* fields,

@@ -36,9 +36,11 @@ namespace {
 // location grid (2-D and 3-D FEM)
 // ---------------------------------------------------------------------------------------------------------------
 
-// one thread per element: the bounding box of its nodes, padded by pad * (largest extent) plus the containment tolerance
+// one thread per element: the bounding box of its p nodes in D coordinates (the element's own dimension plays no part),
+// padded by pad * (largest extent) plus the containment tolerance plus `reach` (absolute)
 template <int D>
-__global__ void elem_boxes(int64_t N, int32_t p, const double* __restrict__ x, double pad, double* __restrict__ box) {
+__global__ void elem_boxes(int64_t N, int32_t p, const double* __restrict__ x, double pad, double reach,
+                           double* __restrict__ box) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     double lo[D], hi[D];
@@ -56,7 +58,7 @@ __global__ void elem_boxes(int64_t N, int32_t p, const double* __restrict__ x, d
     }
     // a point accepted within the containment tolerance lies at most ~ROUND_FACTOR eps max|x| (or ACCEPT_TOL of the
     // extent) outside the element
-    const double w = (pad + 4 * ACCEPT_TOL) * ext + 4 * ROUND_FACTOR * EPS * xs;
+    const double w = (pad + 4 * ACCEPT_TOL) * ext + 4 * ROUND_FACTOR * EPS * xs + reach;
     for (int a = 0; a < D; ++a) {
         box[e * 2 * D + a] = lo[a] - w;
         box[e * 2 * D + D + a] = hi[a] + w;
@@ -610,10 +612,11 @@ void launch_spectral(int32_t family, Pass pass, const QueryArgs& a, int32_t n, h
     MGB_HIP_CHECK(hipGetLastError());
 }
 
-// the uniform grid over the union of the element boxes and its candidate lists (cell -> elements in ascending order)
+// the uniform grid over the union of the element boxes and its candidate lists (cell -> elements in ascending order);
+// D counts coordinates and in.p nodes per element, so the elements may be of a lower dimension than D (closest.hip)
 template <int D>
 void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, DevBuf<int32_t>& start,
-                DevBuf<int32_t>& cand, DevBuf<double>& box) {
+                DevBuf<int32_t>& cand, DevBuf<double>& box, double reach = 0.0) {
     const int64_t N = in.N;
     DevBuf<double> ubox;
     box.alloc((size_t)N * 2 * D);
@@ -624,7 +627,7 @@ void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, 
     // their spread (ends 0 and 1 with mid-node 1 peak at 9/8), so 1/8 of the largest extent always suffices.
     const bool curved = (in.family == MGBHIP_INTERP_QK && in.k >= 2) || in.family == MGBHIP_INTERP_P2C;
     const double pad = curved ? QK_BOX_PAD : 0.0;
-    hipLaunchKernelGGL((elem_boxes<D>), dim3(grid_1d(N)), dim3(BLOCK), 0, st, N, in.p, d_x, pad, box.p);
+    hipLaunchKernelGGL((elem_boxes<D>), dim3(grid_1d(N)), dim3(BLOCK), 0, st, N, in.p, d_x, pad, reach, box.p);
     hipLaunchKernelGGL((union_box<D>), dim3(1), dim3(1024), 0, st, N, box.p, ubox.p);
     MGB_HIP_CHECK(hipGetLastError());
     double hb[2 * D];
@@ -687,6 +690,25 @@ void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, 
     // the temporaries are freed at scope exit; hipFree waits for the work that uses them
 }
 
+// order[i] = the point lane i processes: the M points sorted by cell (a point without a cell sorts last).  A wave then
+// reads the same few candidate lists and runs a similar number of Newton steps (all kernels of a call, P2 at L = 9 with
+// 4 M random points: 0.69 ms against 0.87 ms unsorted; fem3d k = 3 at L = 5 with 1 M points: 3.0 ms against 5.8 ms).
+template <int D>
+void sort_points(const Grid& g, int64_t M, const double* d_pts, DevBuf<int32_t>& order, hipStream_t st) {
+    DevBuf<uint32_t> k0, k1;
+    DevBuf<int32_t> i0;
+    k0.alloc((size_t)M); k1.alloc((size_t)M); i0.alloc((size_t)M); order.alloc((size_t)M);
+    hipLaunchKernelGGL((query_keys<D>), dim3(grid_1d(M)), dim3(BLOCK), 0, st, M, g, d_pts, k0.p, i0.p);
+    unsigned bits = 1;
+    while (bits < 32 && ((uint64_t)g.ncell >> bits) != 0) ++bits;
+    size_t sort_bytes = 0;
+    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)M, 0u, bits, st));
+    DevBuf<char> tmp;
+    tmp.alloc(sort_bytes + 16);
+    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)M, 0u, bits, st));
+    MGB_HIP_CHECK(hipStreamSynchronize(st));        // the sort buffers are freed on return
+}
+
 // The located families: build the grid, sort the points by cell and run the fused query (pass FUSED) or the locate
 // kernel alone (pass LOCATE: l receives the result in cell order and `order` is left to the caller, who keeps it).  The
 // grid, the candidate lists, the boxes and the sort buffers are freed on return.
@@ -700,20 +722,7 @@ void run_located(const InterpIn& in, Pass pass, QueryArgs a, const LocArgs& l, c
     a.start = start.p;
     a.cand = cand.p;
     a.box = box.p;
-    // queries sorted by cell: a wave reads the same few candidate lists and runs a similar number of Newton steps
-    // (all kernels of a call, P2 at L = 9 with 4 M random points: 0.69 ms against 0.87 ms unsorted; fem3d k = 3 at
-    // L = 5 with 1 M points: 3.0 ms against 5.8 ms)
-    DevBuf<uint32_t> k0, k1;
-    DevBuf<int32_t> i0;
-    k0.alloc((size_t)a.M); k1.alloc((size_t)a.M); i0.alloc((size_t)a.M); order.alloc((size_t)a.M);
-    hipLaunchKernelGGL((query_keys<D>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a.M, g, a.pts, k0.p, i0.p);
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)g.ncell >> bits) != 0) ++bits;
-    size_t sort_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)a.M, 0u, bits, st));
-    DevBuf<char> tmp;
-    tmp.alloc(sort_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)a.M, 0u, bits, st));
+    sort_points<D>(g, a.M, a.pts, order, st);
     a.order = order.p;
     launch_located<D>(in.family, in.k, pass, a, g, l, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
@@ -726,6 +735,22 @@ void location_grid_build(LocationGrid& G, const InterpIn& in, const double* d_x,
     if (in.d == 2) build_grid<2>(in, d_x, st, G.g, G.start, G.cand, G.box);
     else build_grid<3>(in, d_x, st, G.g, G.start, G.cand, G.box);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void location_grid_build_embedded(LocationGrid& G, int32_t e, int32_t k, int32_t p, int64_t N, const double* d_x,
+                                  double reach, hipStream_t st) {
+    MGB_REQUIRE(e == 2 || e == 3, "closest_point: a location grid needs e = 2 or 3");
+    InterpIn in;
+    in.family = MGBHIP_INTERP_QK; in.d = e; in.k = k; in.p = p; in.N = N;
+    if (e == 2) build_grid<2>(in, d_x, st, G.g, G.start, G.cand, G.box, reach);
+    else build_grid<3>(in, d_x, st, G.g, G.start, G.cand, G.box, reach);
+    MGB_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void location_grid_sort_points(const LocationGrid& G, int32_t e, int64_t M, const double* d_pts, DevBuf<int32_t>& order,
+                               hipStream_t st) {
+    if (e == 2) sort_points<2>(G.g, M, d_pts, order, st);
+    else sort_points<3>(G.g, M, d_pts, order, st);
 }
 
 void interpolate_run(const InterpIn& in, hipStream_t st) {

@@ -50,6 +50,15 @@ struct LocationGrid {
 
 // in: family, d (2 or 3), k, p, N; d_x the node coordinates on the device ((p*N) x d); complete on return
 void location_grid_build(LocationGrid& G, const InterpIn& in, const double* d_x, hipStream_t st);
+// The same grid over N Q_k elements of p nodes each in e = 2 or 3 coordinates, whatever their own dimension (curves and
+// surfaces: closest.hip).  The node boxes are padded as for Q_k (by QK_BOX_PAD x extent for k >= 2) and by `reach` more
+// on every side, so a cell lists every element that comes within `reach` of one of its points.
+void location_grid_build_embedded(LocationGrid& G, int32_t e, int32_t k, int32_t p, int64_t N, const double* d_x,
+                                  double reach, hipStream_t st);
+// order[i] = the point lane i of a query kernel processes: the M points (d_pts, M x e, on the device) sorted by their
+// cell of G, as interpolate_run sorts its points; complete on return
+void location_grid_sort_points(const LocationGrid& G, int32_t e, int64_t M, const double* d_pts, DevBuf<int32_t>& order,
+                               hipStream_t st);
 
 // one launch sequence on st; complete (results on the host) on return
 void interpolate_run(const InterpIn& in, hipStream_t st);
