@@ -504,6 +504,46 @@ int mgbhip_weld_fetch(const mgbhip_weld* w, int32_t* cells /* S x nv */, int32_t
 int mgbhip_weld_rounds(const mgbhip_weld* w, int32_t* vertex_rounds, int32_t* component_rounds);
 int mgbhip_weld_destroy(mgbhip_weld* w); /* NULL is a no-op */
 
+/* ---- polylines: the segments of an indexed curve mesh ordered into lines -------------------------------------------
+ * vertices is V x e, e in {2, 3}; cells is S x 2 int32 with entries in [0, V), 2 S < 2^31.  Segment s is dropped if its two
+ * vertices are equal, or if a lower-numbered segment that is not dropped has the same unordered pair; the others are
+ * edges.  A vertex with two edges is interior, one with one edge [an end] or three and more [a junction] is a node.  Two
+ * edges that share an interior vertex belong to the same line: a line is an open path between two nodes [which may be
+ * the same junction] or a cycle of interior vertices [closed].  Lines are numbered by their lowest segment.  An open line
+ * starts at the end node with the smaller vertex number, or with equal ends along the end edge with the lower segment
+ * number; a closed line starts at its lowest vertex and goes on to the smaller of that vertex's two neighbours.
+ * Line l of n edges owns the n + 1 points offsets[l] .. offsets[l + 1] - 1 [offsets is L + 1 int64]; a closed line repeats
+ * its first vertex as its last point.  vertex [P] is the vertex of every point, segment [P] the segment from point j to
+ * j + 1 and -1 at the last point of a line, closed [L] is 0 or 1.  arclength [P] is 0 at the first point of a line and then
+ * the sum of the lengths sqrt((dx dx + dy dy) [+ dz dz]) of the edges before the point [no fused multiply-add], added
+ * within the line alone in the order of a balanced tree; length [L] is the arc length at the last point of every line.
+ * The lines are ranked by pointer doubling, one lane per directed half-edge, in two passes of ceil(log2(2 S)) + 1 rounds
+ * each [the lowest vertex of every cycle; then rank, ends, lowest segment and length]; rounds reports the rounds of each
+ * pass [nphases = 2 entries].  No atomics are used and two calls return bitwise equal arrays.  A NULL pointer, e outside
+ * {2, 3}, 2 S >= 2^31, an entry of cells outside [0, V) and a non-finite coordinate are MGBHIP_ERR_INVALID with a message
+ * that names the argument; S = 0 gives L = P = 0.  create leaves the lines on the device, frees its work buffers and
+ * reports L, P and the number of dropped segments; fetch copies them out.  The handle belongs to the context it was
+ * created from and must be destroyed before it.
+ * sample is stateless: for Q queries [line, s] on lines given by points [P x e], data [P x C, or NULL with C = 0],
+ * offsets and arclength as above, s is clamped to [0, length of the line], j is the largest edge of the line whose first
+ * point has arclength a[j] <= s, t = (s - a[j]) / (a[j + 1] - a[j]) or 0 when that difference is 0, and out_points
+ * [Q x e] and out_data [Q x C] are x_j + t (x_{j+1} - x_j) per column [no fused multiply-add].  A line outside [0, L), a
+ * non-finite s or arclength and offsets that do not give every line two points within P are MGBHIP_ERR_INVALID.
+ * Host pointers; the work runs on ctx's stream and is complete on return.                                            */
+typedef struct mgbhip_polyline mgbhip_polyline;
+int mgbhip_polyline_create(mgbhip_ctx* ctx, int64_t V, int32_t e, const double* vertices /* V x e */, int64_t S,
+                           const int32_t* cells /* S x 2 */, mgbhip_polyline** out, int64_t* L, int64_t* P,
+                           int64_t* ndropped);
+int mgbhip_polyline_fetch(const mgbhip_polyline* pl, int64_t* offsets /* L + 1 */, int32_t* vertex /* P */,
+                          int32_t* segment /* P */, uint8_t* closed /* L */, double* arclength /* P */,
+                          double* length /* L */);
+int mgbhip_polyline_rounds(const mgbhip_polyline* pl, int32_t* rounds /* one per iterated phase */, int32_t* nphases);
+int mgbhip_polyline_destroy(mgbhip_polyline* pl); /* NULL is a no-op */
+int mgbhip_polyline_sample(mgbhip_ctx* ctx, int32_t e, int64_t P, const double* points, int32_t C,
+                           const double* data /* P x C, or NULL */, int64_t L, const int64_t* offsets,
+                           const double* arclength, int64_t Q, const int32_t* line, const double* s,
+                           double* out_points, double* out_data /* Q x C, or NULL */);
+
 /* ---- ray casting: line integrals and volume rendering of an element-space function --------------------------------
  * R rays x = origin + t dir [R x d each, row-major; dir of unit length, so t is arc length] are clipped to
  * [t_min, t_max] and against the axis-parallel box [box: 2 d doubles, lo then hi] by the slab test: for an axis a with

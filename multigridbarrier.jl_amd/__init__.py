@@ -33,6 +33,7 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .figure import FigureRenderer, animation_timeline, render_animation
     from .streamlines import StreamTracer, Streamlines, streamlines
     from .weld import weld, IndexedMesh
+    from .polyline import polylines, Polylines
     from .tubes import (SegmentCaster, TubeHits, segments, curve_segments, merge_layers, render_lines, render_curve)
 except ImportError as _e:  # pragma: no cover - only while the device layer is being built
     _device_import_error = _e

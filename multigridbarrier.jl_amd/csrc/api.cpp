@@ -13,6 +13,7 @@
 #include "contour.hpp"
 #include "figure.hpp"
 #include "interpolate.hpp"
+#include "polyline.hpp"
 #include "problem.hpp"
 #include "raycast.hpp"
 #include "stream.hpp"
@@ -64,6 +65,7 @@ struct mgbhip_closest : Handle<Closest> {};            // a closest-point locato
 struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
 struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
 struct mgbhip_weld : Handle<Weld> {};                  // the index of a welded soup (weld.hpp)
+struct mgbhip_polyline : Handle<Polyline> {};          // the lines of a segment mesh (polyline.hpp)
 struct mgbhip_raycast : Handle<RayCaster> {};          // a ray caster (raycast.hpp)
 struct mgbhip_surface : Handle<Surface> {};            // a triangle soup in its grid (surface.hpp)
 struct mgbhip_tubes : Handle<Tubes> {};                // a capsule soup in its grid (tubes.hpp)
@@ -1107,6 +1109,84 @@ int mgbhip_weld_rounds(const mgbhip_weld* w, int32_t* vertex_rounds, int32_t* co
 }
 
 int mgbhip_weld_destroy(mgbhip_weld* w) { return destroy_handle(w); }
+
+int mgbhip_polyline_create(mgbhip_ctx* ctx, int64_t V, int32_t e, const double* vertices, int64_t S, const int32_t* cells,
+                           mgbhip_polyline** out, int64_t* L, int64_t* P, int64_t* ndropped) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr && L != nullptr && P != nullptr && ndropped != nullptr, "polylines: null output pointer");
+    MGB_REQUIRE(e == 2 || e == 3, "polylines: e must be 2 or 3");
+    MGB_REQUIRE(V >= 0 && V <= (int64_t)INT32_MAX, "polylines: V must be in [0, 2^31)");
+    MGB_REQUIRE(S >= 0, "polylines: S must be >= 0");
+    MGB_REQUIRE(S < ((int64_t)INT32_MAX + 1) / 2, "polylines: S x 2 half-edges exceed 32-bit indexing (2 S >= 2^31)");
+    MGB_REQUIRE(V == 0 || vertices != nullptr, "polylines: null vertices");
+    MGB_REQUIRE(S == 0 || cells != nullptr, "polylines: null cells");
+    for (int64_t i = 0; i < 2 * S; ++i)
+        MGB_REQUIRE(cells[i] >= 0 && cells[i] < V, "polylines: an entry of cells lies outside [0, V)");
+    for (int64_t i = 0; i < V * e; ++i) MGB_REQUIRE(std::isfinite(vertices[i]), "polylines: vertices has a non-finite coordinate");
+    PolylineIn in;
+    in.V = V; in.S = S; in.e = e; in.vertices = vertices; in.cells = cells;
+    create_handle(ctx, out, [&](Polyline& Pl) { polyline_build(Pl, in, ctx->stream); });
+    *L = (*out)->obj.L;
+    *P = (*out)->obj.P;
+    *ndropped = (*out)->obj.ndropped;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_polyline_fetch(const mgbhip_polyline* pl, int64_t* offsets, int32_t* vertex, int32_t* segment, uint8_t* closed,
+                          double* arclength, double* length) {
+    MGB_API_BEGIN_ON(pl)
+    MGB_REQUIRE(pl != nullptr, "polyline_fetch: null polyline");
+    MGB_REQUIRE(offsets != nullptr, "polyline_fetch: null offsets");
+    MGB_REQUIRE(pl->obj.P == 0 || (vertex != nullptr && segment != nullptr && arclength != nullptr),
+                "polyline_fetch: null vertex, segment or arclength");
+    MGB_REQUIRE(pl->obj.L == 0 || (closed != nullptr && length != nullptr), "polyline_fetch: null closed or length");
+    polyline_fetch(pl->obj, offsets, vertex, segment, closed, arclength, length, pl->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_polyline_rounds(const mgbhip_polyline* pl, int32_t* rounds, int32_t* nphases) {
+    MGB_API_BEGIN
+    MGB_REQUIRE(pl != nullptr && rounds != nullptr && nphases != nullptr, "polyline_rounds: null argument");
+    rounds[0] = pl->obj.rounds[0];
+    rounds[1] = pl->obj.rounds[1];
+    *nphases = 2;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_polyline_destroy(mgbhip_polyline* pl) { return destroy_handle(pl); }
+
+int mgbhip_polyline_sample(mgbhip_ctx* ctx, int32_t e, int64_t P, const double* points, int32_t C, const double* data,
+                           int64_t L, const int64_t* offsets, const double* arclength, int64_t Q, const int32_t* line,
+                           const double* s, double* out_points, double* out_data) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(e == 2 || e == 3, "polyline_sample: e must be 2 or 3");
+    MGB_REQUIRE(P >= 0 && P <= (int64_t)INT32_MAX && L >= 0 && Q >= 0 && C >= 0, "polyline_sample: bad sizes");
+    MGB_REQUIRE(Q * (int64_t)(e > C ? e : C) <= (int64_t)INT32_MAX, "polyline_sample: sizes exceed 32-bit indexing");
+    MGB_REQUIRE(offsets != nullptr, "polyline_sample: null offsets");
+    MGB_REQUIRE(P == 0 || (points != nullptr && arclength != nullptr), "polyline_sample: null points or arclength");
+    MGB_REQUIRE(C == 0 || P == 0 || data != nullptr, "polyline_sample: null data with C > 0");
+    MGB_REQUIRE(Q == 0 || (line != nullptr && s != nullptr && out_points != nullptr), "polyline_sample: null line, s or out_points");
+    MGB_REQUIRE(C == 0 || Q == 0 || out_data != nullptr, "polyline_sample: null out_data with C > 0");
+    MGB_REQUIRE(offsets[0] == 0 && offsets[L] == P, "polyline_sample: offsets must run from 0 to P");
+    for (int64_t l = 0; l < L; ++l)
+        MGB_REQUIRE(offsets[l + 1] - offsets[l] >= 2, "polyline_sample: offsets must give every line at least two points");
+    for (int64_t i = 0; i < P; ++i) MGB_REQUIRE(std::isfinite(arclength[i]), "polyline_sample: arclength must be finite");
+    for (int64_t q = 0; q < Q; ++q) {
+        MGB_REQUIRE(line[q] >= 0 && line[q] < L, "polyline_sample: an entry of line lies outside [0, L)");
+        MGB_REQUIRE(std::isfinite(s[q]), "polyline_sample: s must be finite");
+    }
+    PolylineSampleIn in;
+    in.e = e; in.C = C; in.P = P; in.L = L; in.Q = Q; in.points = points; in.data = C ? data : nullptr; in.offsets = offsets;
+    in.arclength = arclength; in.line = line; in.s = s;
+    polyline_sample(in, out_points, out_data, ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
 
 int mgbhip_raycast_create(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t k, int32_t p, int64_t N, const double* x,
                           const double* table, int64_t R, const double* origin, const double* dir, const double* box,

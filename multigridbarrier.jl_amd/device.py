@@ -121,6 +121,8 @@ EXPORTS = [
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
     "mgbhip_tessellate_create", "mgbhip_tessellate_fetch", "mgbhip_tessellate_destroy",
     "mgbhip_weld_create", "mgbhip_weld_fetch", "mgbhip_weld_rounds", "mgbhip_weld_destroy",
+    "mgbhip_polyline_create", "mgbhip_polyline_fetch", "mgbhip_polyline_rounds", "mgbhip_polyline_destroy",
+    "mgbhip_polyline_sample",
     "mgbhip_raycast_create", "mgbhip_raycast_offsets", "mgbhip_raycast_samples", "mgbhip_raycast_lengths",
     "mgbhip_raycast_integrate", "mgbhip_raycast_render", "mgbhip_raycast_destroy", "mgbhip_raycast_render_layers",
     "mgbhip_surface_create", "mgbhip_surface_trace", "mgbhip_surface_shade", "mgbhip_surface_destroy",
@@ -233,6 +235,13 @@ def load_library():
     lib.mgbhip_weld_fetch.argtypes = [vp, _ip, _ip, _ip, _dp]
     lib.mgbhip_weld_rounds.argtypes = [vp, _ip, _ip]
     lib.mgbhip_weld_destroy.argtypes = [vp]
+    _lp = C.POINTER(C.c_int64)
+    lib.mgbhip_polyline_create.argtypes = [vp, C.c_int64, C.c_int32, _dp, C.c_int64, _ip, C.POINTER(vp), _lp, _lp, _lp]
+    lib.mgbhip_polyline_fetch.argtypes = [vp, _lp, _ip, _ip, C.POINTER(C.c_uint8), _dp, _dp]
+    lib.mgbhip_polyline_rounds.argtypes = [vp, _ip, _ip]
+    lib.mgbhip_polyline_destroy.argtypes = [vp]
+    lib.mgbhip_polyline_sample.argtypes = [vp, C.c_int32, C.c_int64, _dp, C.c_int32, _dp, C.c_int64, _lp, _dp, C.c_int64,
+                                           _ip, _dp, _dp, _dp]
     lib.mgbhip_raycast_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int64,
                                           _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.POINTER(vp),
                                           C.POINTER(C.c_int64)]

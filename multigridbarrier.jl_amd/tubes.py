@@ -23,6 +23,7 @@ from ._handle import DeviceObject
 from .contour import Contour
 from .interpolate import _c_f64
 from .multigrid import Geometry
+from .polyline import Polylines
 from .raycast import _check_size, camera_rays
 from .streamlines import Streamlines
 from .surface import (MAX_HITS, _check_ambient, _check_colouring, _check_hits, _check_max_hits, _check_rays, _check_table,
@@ -149,7 +150,21 @@ _FLAT = "the lines of a flat 2-D mesh are not in R^3"
 
 
 def _segments_of(who: str, item, values):
-    """`(points (S, 2, 3), values (S, 2) or None)` of one `Streamlines`, `Contour` or array."""
+    """`(points (S, 2, 3), values (S, 2) or None)` of one `Streamlines`, `Polylines`, `Contour` or array."""
+    if isinstance(item, Polylines):
+        P = np.asarray(item.points, dtype=np.float64)
+        if P.ndim != 2 or P.shape[1] != 3:
+            raise ValueError(f"{who}: {_FLAT} (got Polylines with points of shape {P.shape})")
+        if values is None and item.vertex_data is not None:
+            values = item.vertex_data[:, 0]
+        j = np.nonzero(item.segment >= 0)[0]                      # point j and j + 1 are neighbours on one line
+        V = None
+        if values is not None:
+            V = np.asarray(values, dtype=np.float64)
+            if V.shape != (P.shape[0],):
+                raise ValueError(f"{who}: values of a Polylines must be ({P.shape[0]},), one per point (got shape {V.shape})")
+            V = np.stack([V[j], V[j + 1]], axis=1)
+        return np.stack([P[j], P[j + 1]], axis=1).reshape(-1, 2, 3), V
     if isinstance(item, Streamlines):
         P = np.asarray(item.points, dtype=np.float64)
         if P.ndim != 3 or P.shape[2] != 3:
@@ -202,6 +217,8 @@ def segments(lines, values=None, who: str = "segments"):
 
     - a `Streamlines` with `d = 3`: the consecutive valid points of every line; `values`, if given, has the shape of
       `points[..., 0]`, one value per line point;
+    - a `Polylines` in R^3: the consecutive points of every line; `values` is `(P,)`, one per point, and defaults to
+      `vertex_data[:, 0]` when the lines have it;
     - a `Contour` whose points are `(S, 2, 3)` (the level curves of a `fem2d` surface in R^3); `values` (`(S,)` or
       `(S, 2)`) defaults to `carried[..., 0]` when it carries fields;
     - an `(S, 2, 3)` array, with `values` `(S,)` or `(S, 2)`;
