@@ -427,8 +427,6 @@ __global__ void __launch_bounds__(BLOCK) closest_eval(EvalArgs a) {
     }
 }
 
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 template <int DR, int E, int S>
 void launch_closest(const ClosestArgs& a, const Grid& g, hipStream_t st) {
     hipLaunchKernelGGL((closest_qk<DR, E, S>), dim3(grid_1d(a.M)), dim3(BLOCK), 0, st, a, g);

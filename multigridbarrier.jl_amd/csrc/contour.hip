@@ -27,9 +27,8 @@
 #include <cmath>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "contour.hpp"
+#include "device_prims.hpp"
 
 // No fused multiply-adds in this file: a plain IEEE transcription of the algorithm (tests/contour_twin.py) then
 // classifies every lattice value the same way and computes the same crossings.
@@ -39,7 +38,6 @@ namespace mgbhip {
 
 namespace {
 
-constexpr int MAX_BLOCK = 256;
 constexpr int KIND_Q2 = 0, KIND_Q3 = 1, KIND_TRI = 2;
 // what form_lattice samples: the contoured value alone; value, position, carried fields; position, fields
 constexpr int MODE_COUNT = 0, MODE_EMIT = 1, MODE_TESS = 2;
@@ -172,11 +170,11 @@ __device__ __forceinline__ void form_lattice(const ContourArgs& a, int64_t e, do
 // EMIT = false: a.count[e] = simplices of element e.  EMIT = true: the simplices of element e from a.off[e] on.
 // LDS: the lattice of form_lattice (MODE_COUNT / MODE_EMIT), then the table.  E = D but for a Q_k 2-D surface (E = 3).
 template <int KIND, int E, bool EMIT>
-__global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
+__global__ void __launch_bounds__(BLOCK) contour_kernel(ContourArgs a) {
     constexpr int D = KIND == KIND_Q3 ? 3 : 2;
     constexpr int NSLOT = EMIT ? E + CONTOUR_MAX_FIELDS : 1;
     extern __shared__ double lds[];
-    __shared__ int64_t sc[MAX_BLOCK];
+    __shared__ int64_t sc[BLOCK];
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int64_t e = blockIdx.x;
     const int npts = a.npts, r = a.r, nf = a.nfield;
@@ -287,7 +285,7 @@ __global__ void __launch_bounds__(MAX_BLOCK) contour_kernel(ContourArgs a) {
 // Every lattice triangle of element e: triangle s goes to e * a.nsimp + s, its vertices in ascending lattice index.
 // LDS: the lattice of form_lattice (MODE_TESS), then the table.  KIND_Q2 (E = 2 or 3) and KIND_TRI.
 template <int KIND, int E>
-__global__ void __launch_bounds__(MAX_BLOCK) tessellate_kernel(ContourArgs a) {
+__global__ void __launch_bounds__(BLOCK) tessellate_kernel(ContourArgs a) {
     static_assert(KIND != KIND_Q3, "a tessellation is of 2-D elements");
     extern __shared__ double lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -388,23 +386,14 @@ void contour_build_device(Contour& C, const ContourIn& in, const double* d_x, co
     lattice_sizes(kind, r, a);
     a.table_len = table_len;
     // one wave for an element of few simplices, a workgroup of four otherwise
-    const unsigned block = a.nsimp <= 128 ? 64 : MAX_BLOCK;
+    const unsigned block = a.nsimp <= 128 ? 64 : BLOCK;
     a.chunk = (a.nsimp + (int)block - 1) / (int)block;
     a.x = d_x; a.table = d_table; a.fields = d_fields; a.levels = d_levels;
     a.count = w.count.p;
     launch_kind(kind, e, false, block, ((size_t)a.npts + (size_t)table_len) * sizeof(double), a, st);
 
-    size_t scan_bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, w.count.p, w.off.p, (int64_t)0, (size_t)in.N,
-                                          rocprim::plus<int64_t>(), st));
-    w.tmp.ensure(scan_bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)w.tmp.p, scan_bytes, w.count.p, w.off.p, (int64_t)0, (size_t)in.N,
-                                          rocprim::plus<int64_t>(), st));
-    int64_t last_off = 0, last_count = 0;
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_off, w.off.p + (in.N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_count, w.count.p + (in.N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    const int64_t S = last_off + last_count;
+    exclusive_scan(w.count.p, w.off.p, in.N, w.tmp, st);
+    const int64_t S = scan_total(w.count.p, w.off.p, in.N, st);
     MGB_REQUIRE(S >= 0 && S < (int64_t)INT32_MAX, "contour: the number of simplices exceeds 32-bit indexing");
     if (S == 0) return;
 
@@ -479,7 +468,7 @@ void tessellate_build(Tessellation& T, const ContourIn& in, hipStream_t st) {
     a.x = d_x.p; a.table = d_table.p; a.fields = d_fields.p;
     a.points = T.points.p; a.element = T.element.p; a.values = T.values.p;
     // the launch shape of the contour kernels: one wave for an element of few triangles, a workgroup of four otherwise
-    const unsigned block = a.nsimp <= 128 ? 64 : MAX_BLOCK;
+    const unsigned block = a.nsimp <= 128 ? 64 : BLOCK;
     const size_t lds_bytes = ((size_t)a.npts * (e + in.nfield) + table.size()) * sizeof(double);
     if (kind == KIND_Q2 && e == 3) launch_tess<KIND_Q2, 3>(block, lds_bytes, a, st);
     else if (kind == KIND_Q2) launch_tess<KIND_Q2, 2>(block, lds_bytes, a, st);

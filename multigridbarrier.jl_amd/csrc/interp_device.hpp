@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "cell_lists.hpp"         // Grid, cell_axis, BLOCK
 #include "interpolate.hpp"
 
 // No fused multiply-adds in the code below or in a file that includes it: see interpolate.hip.
@@ -20,7 +21,6 @@ namespace mgbhip {
 
 namespace {
 
-constexpr int BLOCK = 256;
 constexpr int NEWTON_MAXIT = 32;
 constexpr int BISECT_MAXIT = 128;
 constexpr double ACCEPT_TOL = 1e-11;       // containment tolerance in reference coordinates (at least)
@@ -33,14 +33,6 @@ constexpr double EPS = 2.220446049250313e-16;
 constexpr double QK_BOX_PAD = 0.125;       // a curved Q_k image can leave its nodes' box: pad by 1/8 of the extent
 
 __device__ inline double dnan() { return __builtin_nan(""); }
-
-// cell index of a scaled coordinate u = (v - lo) * inv; the caller has checked that v is finite and in the grid box
-__device__ inline int32_t cell_axis(double u, int32_t n) {
-    if (!(u >= 0.0)) return 0;
-    if (u >= (double)n) return n - 1;
-    const int32_t c = (int32_t)u;
-    return c < n - 1 ? c : n - 1;
-}
 
 // cell of a point, or -1 if it is not finite or outside the grid box
 template <int D>

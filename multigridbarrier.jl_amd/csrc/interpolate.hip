@@ -3,10 +3,9 @@
 //
 // reference: `interpolate`, src/utils.jl:16-58 (1-D Q_k: src/TensorFEM.jl:967-1014; spectral1d: src/spectral1d.jl:140-170;
 // spectral2d: src/spectral2d.jl:85-125).  The reference has no 2-D / 3-D FEM method; here those locate every point
-// through a uniform grid of element bounding boxes built on the device, the same sort-by-key pattern as the assembly
-// plans (plan_device.hip): (cell, element) pairs are emitted in element order and radix-sorted stably by cell, so each
-// cell's candidate list is in ascending element order and the first element that accepts a point is the lowest-index
-// one, whatever the launch configuration.  Each query lane then inverts the element map of its candidates in order.
+// through a uniform grid of element bounding boxes built on the device (cell_lists.hpp), the same sort-by-key pattern as
+// the assembly plans (plan_device.hip): each cell's candidate list is in ascending element order, so the first element
+// that accepts a point is the lowest-index one, whatever the launch configuration.  Each query lane then inverts the element map of its candidates in order.
 //
 // Every loop is bounded (Newton iterations, bisection halvings, the candidate list of one cell, the 1-D scans), and
 // a coordinate becomes a cell index only after it is known to be finite and inside the grid box.
@@ -17,9 +16,6 @@
 #include <cstring>
 #include <limits>
 #include <vector>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "interp_device.hpp"      // the locate and evaluate device functions and their constants (shared with stream.hip)
 #include "interpolate.hpp"
@@ -63,82 +59,6 @@ __global__ void elem_boxes(int64_t N, int32_t p, const double* __restrict__ x, d
         box[e * 2 * D + a] = lo[a] - w;
         box[e * 2 * D + D + a] = hi[a] + w;
     }
-}
-
-// one block: the union of all boxes (2*D doubles: lo then hi)
-template <int D>
-__global__ void __launch_bounds__(1024) union_box(int64_t N, const double* __restrict__ box, double* __restrict__ out) {
-    __shared__ double s[2 * D][1024];
-    double lo[D], hi[D];
-    for (int a = 0; a < D; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
-    for (int64_t e = threadIdx.x; e < N; e += blockDim.x)
-        for (int a = 0; a < D; ++a) {
-            lo[a] = fmin(lo[a], box[e * 2 * D + a]);
-            hi[a] = fmax(hi[a], box[e * 2 * D + D + a]);
-        }
-    for (int a = 0; a < D; ++a) { s[a][threadIdx.x] = lo[a]; s[D + a][threadIdx.x] = hi[a]; }
-    __syncthreads();
-    for (int h = blockDim.x / 2; h > 0; h /= 2) {
-        if ((int)threadIdx.x < h)
-            for (int a = 0; a < D; ++a) {
-                s[a][threadIdx.x] = fmin(s[a][threadIdx.x], s[a][threadIdx.x + h]);
-                s[D + a][threadIdx.x] = fmax(s[D + a][threadIdx.x], s[D + a][threadIdx.x + h]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 2 * D) out[threadIdx.x] = s[threadIdx.x][0];
-}
-
-template <int D>
-__device__ inline void box_cells(const Grid& g, const double* b, int32_t* c0, int32_t* c1) {
-    for (int a = 0; a < D; ++a) {
-        c0[a] = cell_axis((b[a] - g.lo[a]) * g.inv[a], g.n[a]);
-        c1[a] = cell_axis((b[D + a] - g.lo[a]) * g.inv[a], g.n[a]);
-    }
-}
-
-template <int D>
-__global__ void box_counts(int64_t N, Grid g, const double* __restrict__ box, int64_t* __restrict__ count) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    int32_t c0[D], c1[D];
-    box_cells<D>(g, box + e * 2 * D, c0, c1);
-    int64_t c = 1;
-    for (int a = 0; a < D; ++a) c *= (int64_t)(c1[a] - c0[a] + 1);
-    count[e] = c;
-}
-
-template <int D>
-__global__ void emit_pairs(int64_t N, Grid g, const double* __restrict__ box, const int64_t* __restrict__ off,
-                           uint32_t* __restrict__ keys, int32_t* __restrict__ vals) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    int32_t c0[D], c1[D];
-    box_cells<D>(g, box + e * 2 * D, c0, c1);
-    int64_t o = off[e];
-    if constexpr (D == 2) {
-        for (int32_t j = c0[1]; j <= c1[1]; ++j)
-            for (int32_t i = c0[0]; i <= c1[0]; ++i, ++o) {
-                keys[o] = (uint32_t)((int64_t)j * g.n[0] + i);
-                vals[o] = (int32_t)e;
-            }
-    } else {
-        for (int32_t l = c0[2]; l <= c1[2]; ++l)
-            for (int32_t j = c0[1]; j <= c1[1]; ++j)
-                for (int32_t i = c0[0]; i <= c1[0]; ++i, ++o) {
-                    keys[o] = (uint32_t)(((int64_t)l * g.n[1] + j) * g.n[0] + i);
-                    vals[o] = (int32_t)e;
-                }
-    }
-}
-
-// start[c] = first sorted pair of cell c (start[ncell] = P): every cell is written exactly once
-__global__ void cell_starts(int64_t P, int64_t ncell, const uint32_t* __restrict__ keys, int32_t* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > P) return;
-    const int64_t a = i == 0 ? -1 : (int64_t)keys[i - 1];
-    const int64_t b = i == P ? ncell : (int64_t)keys[i];
-    for (int64_t c = a + 1; c <= b; ++c) start[c] = (int32_t)i;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -498,8 +418,6 @@ __global__ void query_keys(int64_t M, Grid g, const double* __restrict__ pts, ui
     idx[q] = (int32_t)q;
 }
 
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 // which kernels a launch sequence runs: the fused query (mgbhip_interpolate*), or one half of it for a point locator
 enum class Pass { FUSED, LOCATE, EVAL };
 
@@ -613,14 +531,13 @@ void launch_spectral(int32_t family, Pass pass, const QueryArgs& a, int32_t n, h
 }
 
 // the uniform grid over the union of the element boxes and its candidate lists (cell -> elements in ascending order);
-// D counts coordinates and in.p nodes per element, so the elements may be of a lower dimension than D (closest.hip)
+// D counts coordinates and in.p nodes per element, so the elements may be of a lower dimension than D (closest.hip).
+// Complete on return.
 template <int D>
 void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, DevBuf<int32_t>& start,
                 DevBuf<int32_t>& cand, DevBuf<double>& box, double reach = 0.0) {
     const int64_t N = in.N;
-    DevBuf<double> ubox;
     box.alloc((size_t)N * 2 * D);
-    ubox.alloc(2 * D);
     // Curved P2 takes the Q_k pad: the image of a valid element (det J > 0 throughout) is bounded by its three edge
     // curves, the bubble vanishes on the edges, and each edge is the quadratic through its three nodes.  A quadratic
     // Lagrange interpolant on three equispaced parameters leaves the interval of its node values by at most 1/8 of
@@ -628,66 +545,8 @@ void build_grid(const InterpIn& in, const double* d_x, hipStream_t st, Grid& g, 
     const bool curved = (in.family == MGBHIP_INTERP_QK && in.k >= 2) || in.family == MGBHIP_INTERP_P2C;
     const double pad = curved ? QK_BOX_PAD : 0.0;
     hipLaunchKernelGGL((elem_boxes<D>), dim3(grid_1d(N)), dim3(BLOCK), 0, st, N, in.p, d_x, pad, reach, box.p);
-    hipLaunchKernelGGL((union_box<D>), dim3(1), dim3(1024), 0, st, N, box.p, ubox.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    double hb[2 * D];
-    ubox.download(hb, 2 * D, st);
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    // about one element per cell: cells of side h with h^(#axes of positive extent) = volume / N
-    double vol = 1.0;
-    int nz = 0;
-    for (int a = 0; a < D; ++a) {
-        MGB_REQUIRE(std::isfinite(hb[a]) && std::isfinite(hb[D + a]), "interpolate: non-finite element box");
-        if (hb[D + a] > hb[a]) { vol *= hb[D + a] - hb[a]; ++nz; }
-    }
-    const double h = nz ? std::pow(vol / (double)N, 1.0 / nz) : 1.0;
-    g = Grid{};
-    g.ncell = 1;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = g.hi[a] = 0.0; g.inv[a] = 0.0; g.n[a] = 1; }
-    for (int a = 0; a < D; ++a) {
-        const double ext = hb[D + a] - hb[a];
-        g.lo[a] = hb[a];
-        g.hi[a] = hb[D + a];
-        int64_t n = ext > 0 && h > 0 ? (int64_t)std::ceil(ext / h) : 1;
-        n = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)4 * N + 1));
-        g.n[a] = (int32_t)n;
-        g.inv[a] = ext > 0 ? (double)n / ext : 0.0;
-        g.ncell *= n;
-    }
-    MGB_REQUIRE(g.ncell < (int64_t)INT32_MAX, "interpolate: location grid exceeds 32-bit cell indexing");
-    DevBuf<int64_t> count, off;
-    count.alloc((size_t)N);
-    off.alloc((size_t)N);
-    hipLaunchKernelGGL((box_counts<D>), dim3(grid_1d(N)), dim3(BLOCK), 0, st, N, g, box.p, count.p);
-    size_t scan_bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, count.p, off.p, (int64_t)0, (size_t)N,
-                                          rocprim::plus<int64_t>(), st));
-    DevBuf<char> tmp;
-    tmp.alloc(scan_bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, scan_bytes, count.p, off.p, (int64_t)0, (size_t)N,
-                                          rocprim::plus<int64_t>(), st));
-    int64_t last_off = 0, last_count = 0;
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_off, off.p + (N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_count, count.p + (N - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    const int64_t P = last_off + last_count;
-    MGB_REQUIRE(P > 0 && P < (int64_t)INT32_MAX, "interpolate: (cell, element) pair count exceeds 32-bit indexing");
-    DevBuf<uint32_t> k0, k1;
-    DevBuf<int32_t> v0;
-    k0.alloc((size_t)P); k1.alloc((size_t)P); v0.alloc((size_t)P);
-    cand.alloc((size_t)P);
-    hipLaunchKernelGGL((emit_pairs<D>), dim3(grid_1d(N)), dim3(BLOCK), 0, st, N, g, box.p, off.p, k0.p, v0.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)g.ncell >> bits) != 0) ++bits;
-    size_t sort_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, v0.p, cand.p, (size_t)P, 0u, bits, st));
-    tmp.ensure(sort_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, v0.p, cand.p, (size_t)P, 0u, bits, st));
-    start.alloc((size_t)g.ncell + 1);
-    hipLaunchKernelGGL(cell_starts, dim3(grid_1d(P + 1)), dim3(BLOCK), 0, st, P, g.ncell, k1.p, start.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    // the temporaries are freed at scope exit; hipFree waits for the work that uses them
+    cell_lists_from_boxes<D>("interpolate", "element", N, box.p, LOCATION_CELLS<D>, g, start, cand, st);
+    // the work buffers were freed on return; hipFree waits for the work that uses them
 }
 
 // order[i] = the point lane i processes: the M points sorted by cell (a point without a cell sorts last).  A wave then
@@ -699,13 +558,8 @@ void sort_points(const Grid& g, int64_t M, const double* d_pts, DevBuf<int32_t>&
     DevBuf<int32_t> i0;
     k0.alloc((size_t)M); k1.alloc((size_t)M); i0.alloc((size_t)M); order.alloc((size_t)M);
     hipLaunchKernelGGL((query_keys<D>), dim3(grid_1d(M)), dim3(BLOCK), 0, st, M, g, d_pts, k0.p, i0.p);
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)g.ncell >> bits) != 0) ++bits;
-    size_t sort_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)M, 0u, bits, st));
     DevBuf<char> tmp;
-    tmp.alloc(sort_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, sort_bytes, k0.p, k1.p, i0.p, order.p, (size_t)M, 0u, bits, st));
+    sort_pairs(k0.p, k1.p, i0.p, order.p, M, key_bits((uint64_t)g.ncell), tmp, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));        // the sort buffers are freed on return
 }
 
@@ -734,7 +588,6 @@ void location_grid_build(LocationGrid& G, const InterpIn& in, const double* d_x,
     MGB_REQUIRE(in.d == 2 || in.d == 3, "interpolate: a location grid needs d = 2 or 3");
     if (in.d == 2) build_grid<2>(in, d_x, st, G.g, G.start, G.cand, G.box);
     else build_grid<3>(in, d_x, st, G.g, G.start, G.cand, G.box);
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 void location_grid_build_embedded(LocationGrid& G, int32_t e, int32_t k, int32_t p, int64_t N, const double* d_x,
@@ -744,7 +597,6 @@ void location_grid_build_embedded(LocationGrid& G, int32_t e, int32_t k, int32_t
     in.family = MGBHIP_INTERP_QK; in.d = e; in.k = k; in.p = p; in.N = N;
     if (e == 2) build_grid<2>(in, d_x, st, G.g, G.start, G.cand, G.box, reach);
     else build_grid<3>(in, d_x, st, G.g, G.start, G.cand, G.box, reach);
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 void location_grid_sort_points(const LocationGrid& G, int32_t e, int64_t M, const double* d_pts, DevBuf<int32_t>& order,

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "../../include/mgbhip.h"
+#include "cell_grid.hpp"
 #include "common.hpp"
 
 namespace mgbhip {
@@ -32,14 +33,8 @@ struct InterpIn {
     int32_t* elem = nullptr;      // host M, or NULL
 };
 
-// the uniform grid of cells over the union of the padded element boxes (2-D and 3-D FEM): kernels take it by value
-struct Grid {
-    double lo[3], hi[3], inv[3];
-    int32_t n[3];
-    int64_t ncell;
-};
-
-// A location grid that stays resident: the cells, per cell its candidate elements in ascending element order (cell c
+// A location grid that stays resident: the cells (a Grid over the union of the padded element boxes, cell_grid.hpp), per
+// cell its candidate elements in ascending element order (cell c
 // owns cand[start[c] .. start[c+1]-1]) and the padded element boxes (lo then hi per element).  interpolate_run and
 // locator_build free theirs once the points are located; a field-line tracer (stream.hpp) keeps one for its lifetime.
 struct LocationGrid {

@@ -10,9 +10,7 @@
 
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "device_prims.hpp"
 #include "plan_device.hpp"
 
 namespace mgbhip {
@@ -150,14 +148,6 @@ __global__ void value_map(const int32_t* __restrict__ cptr, const int32_t* __res
     }
 }
 
-struct PlusU32 {
-    __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
-};
-
-struct PlusU64 {
-    __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-
 }  // namespace
 
 int64_t plan_device_pairs(const PlanDeviceIn& in) {
@@ -190,13 +180,8 @@ void build_plan_device(const PlanDeviceIn& in, Level& L, hipStream_t st) {
     hipLaunchKernelGGL(pairs_diagonal, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, m, k0.p + body, v0.p + body);
     MGB_HIP_CHECK(hipGetLastError());
     // stable sort by (row, col): keys are < m*m (+1 for the invalid marker)
-    unsigned bits = 1;
-    while (bits < 64 && (((uint64_t)m * (uint64_t)m) >> bits) != 0) ++bits;
-    size_t tmp_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0.p, k1.p, v0.p, v1.p, (size_t)P, 0u, bits, st));
     DevBuf<char> tmp;
-    tmp.alloc(tmp_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, k0.p, k1.p, v0.p, v1.p, (size_t)P, 0u, bits, st));
+    sort_pairs(k0.p, k1.p, v0.p, v1.p, P, key_bits((uint64_t)m * (uint64_t)m), tmp, st);
     hipLaunchKernelGGL(count_valid, dim3(1), dim3(64), 0, st, k1.p, P, (uint64_t)m * (uint64_t)m, d_nvalid.p);
     int64_t nvalid = 0;
     int32_t err = 0;
@@ -210,15 +195,8 @@ void build_plan_device(const PlanDeviceIn& in, Level& L, hipStream_t st) {
     scan.alloc((size_t)nvalid);
     const int64_t blocks = std::min<int64_t>((nvalid + 255) / 256, 1 << 16);
     hipLaunchKernelGGL(run_flags, dim3((unsigned)blocks), dim3(256), 0, st, k1.p, v1.p, nvalid, flags.p);
-    size_t scan_bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, flags.p, scan.p, (uint64_t)0, (size_t)nvalid, PlusU64(), st));
-    tmp.ensure(scan_bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, scan_bytes, flags.p, scan.p, (uint64_t)0, (size_t)nvalid, PlusU64(), st));
-    uint64_t last_scan = 0, last_flag = 0;
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_scan, scan.p + (nvalid - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_flag, flags.p + (nvalid - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t tot = last_scan + last_flag;
+    exclusive_scan(flags.p, scan.p, nvalid, tmp, st);
+    const uint64_t tot = scan_total(flags.p, scan.p, nvalid, st);
     const int64_t nnz = (int64_t)(tot >> 32), total = (int64_t)(tot & 0xFFFFFFFFull);
     MGB_REQUIRE(nnz < (int64_t)INT32_MAX, "Hessian pattern exceeds 32-bit indexing");
     MGB_REQUIRE(total < (int64_t)INT32_MAX, "contribution list exceeds 32-bit indexing");
@@ -249,10 +227,7 @@ void build_plan_device(const PlanDeviceIn& in, Level& L, hipStream_t st) {
         L.sh_q.alloc((size_t)nnz);          // upper bound; only the first nshared entries are used
         const int64_t qb = std::min<int64_t>((nnz + 255) / 256, 1 << 16);
         hipLaunchKernelGGL(shared_flags, dim3((unsigned)qb), dim3(256), 0, st, L.cptr.p, nnz, fl.p);
-        size_t sb = 0;
-        MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, sb, fl.p, rk.p, (uint32_t)0, (size_t)nnz, PlusU32(), st));
-        tmp.ensure(sb + 16);
-        MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, sb, fl.p, rk.p, (uint32_t)0, (size_t)nnz, PlusU32(), st));
+        exclusive_scan(fl.p, rk.p, nnz, tmp, st);
         hipLaunchKernelGGL(value_map, dim3((unsigned)qb), dim3(256), 0, st, L.cptr.p, L.cidx.p, fl.p, rk.p, nnz, (int32_t)in.extra_base,
                            vmap.p, L.sh_q.p);
         uint32_t lr = 0, lf = 0;
@@ -326,14 +301,9 @@ int32_t transpose_csr_device(int64_t rows, int64_t cols, int64_t nnz, const int3
     d_max.zero(st, 1);
     hipLaunchKernelGGL(expand_rows, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, rows, Rptr, rowidx.p);
     hipLaunchKernelGGL(iota32, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, v0.p);
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)cols >> bits) != 0) ++bits;
     const uint32_t* k0 = reinterpret_cast<const uint32_t*>(Rcol);           // column indices are non-negative
-    size_t tmp_bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1.p, v0.p, v1.p, (size_t)nnz, 0u, bits, st));
     DevBuf<char> tmp;
-    tmp.alloc(tmp_bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, k0, k1.p, v0.p, v1.p, (size_t)nnz, 0u, bits, st));
+    sort_pairs(k0, k1.p, v0.p, v1.p, nnz, key_bits((uint64_t)cols), tmp, st);
     hipLaunchKernelGGL(transpose_fill, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, cols, k1.p, v1.p, rowidx.p, Rval,
                        Tptr.p, Tcol.p, Tval.p);
     hipLaunchKernelGGL(max_row_length, dim3((unsigned)std::min<int64_t>((cols + 255) / 256, 1024)), dim3(256), 0, st, cols, Tptr.p, d_max.p);

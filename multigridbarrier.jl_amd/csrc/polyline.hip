@@ -9,7 +9,7 @@
 //     its two vertices are equal or if the sorted position before it holds the same key (the lower-numbered copy is kept).
 //     Edges keep their segment numbers, so "the lowest segment of a line" needs no translation.
 //  2. Vertex lists.  A second stable sort of (tail vertex, half-edge) over the half-edges of the edges (those of dropped
-//     segments sort behind vertex V - 1) and vertex_starts(): the half-edges that leave v are list[start[v] .. start[v+1]),
+//     segments sort behind vertex V - 1) and segment_starts(): the half-edges that leave v are list[start[v] .. start[v+1]),
 //     ascending, and val[v] is their number.
 //  3. Successors.  h heads to v.  With val[v] == 2 succ(h) is the half-edge leaving v that is not the twin h ^ 1; else h
 //     is terminal, succ(h) = NIL.  An open line is two NIL-terminated lists (one per direction), a closed line two cycles.
@@ -38,9 +38,7 @@
 #include <cmath>
 #include <utility>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#include "device_prims.hpp"
 #include "polyline.hpp"
 
 // No fused multiply-adds in this file: the twin (tests/polyline_twin.py) evaluates the same lengths and the same interpolant.
@@ -50,16 +48,7 @@ namespace mgbhip {
 
 namespace {
 
-constexpr int BLOCK = 256;
 constexpr int32_t NIL = -1;
-
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-unsigned bits_of(uint64_t n) {
-    unsigned bits = 1;
-    while (bits < 64 && (n >> bits) != 0) ++bits;
-    return bits;
-}
 
 __device__ inline int32_t tail_of(const int32_t* __restrict__ cells, int32_t h) { return cells[h]; }
 __device__ inline int32_t head_of(const int32_t* __restrict__ cells, int32_t h) { return cells[h ^ 1]; }
@@ -96,16 +85,6 @@ __global__ void __launch_bounds__(BLOCK) tail_keys(int64_t H, int64_t V, const i
     if (h >= H) return;
     keys[h] = kept[h >> 1] ? cells[h] : (int32_t)V;
     half[h] = (int32_t)h;
-}
-
-// start[c] = first sorted position with key >= c, for c in [0, K] (start[K] = M); keys lie in [0, K)
-__global__ void __launch_bounds__(BLOCK) vertex_starts(int64_t M, int64_t K, const int32_t* __restrict__ keys,
-                                                       int32_t* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > M) return;
-    const int64_t a = i == 0 ? -1 : (int64_t)keys[i - 1];
-    const int64_t b = i == M ? K : (int64_t)keys[i];
-    for (int64_t c = a + 1; c <= b; ++c) start[c] = (int32_t)i;
 }
 
 // ---- 3. successors, and the length of every half-edge
@@ -271,14 +250,6 @@ __global__ void __launch_bounds__(BLOCK) scatter_points(int64_t H, const int32_t
     }
 }
 
-template <class T>
-void exclusive_scan(const T* in, T* out, int64_t n, DevBuf<char>& tmp, hipStream_t st) {
-    size_t bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), st));
-    tmp.ensure(bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), st));
-}
-
 struct RankBuf {
     DevBuf<int32_t> next, last, count, low;
     DevBuf<double> length;
@@ -302,11 +273,7 @@ void build(Polyline& Pl, const PolylineIn& in, hipStream_t st) {
     k0.alloc((size_t)S); keys.alloc((size_t)S); s0.alloc((size_t)S); seg.alloc((size_t)S); kept.alloc((size_t)S);
     hipLaunchKernelGGL(edge_keys, grS, bl, 0, st, S, V, (const int32_t*)cells.p, k0.p, s0.p);
     MGB_HIP_CHECK(hipGetLastError());
-    const unsigned kbits = bits_of((uint64_t)V * (uint64_t)V);
-    size_t bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, k0.p, keys.p, s0.p, seg.p, (size_t)S, 0u, kbits, st));
-    tmp.ensure(bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, bytes, k0.p, keys.p, s0.p, seg.p, (size_t)S, 0u, kbits, st));
+    sort_pairs(k0.p, keys.p, s0.p, seg.p, S, key_bits((uint64_t)V * (uint64_t)V), tmp, st);
     hipLaunchKernelGGL(edge_flags, grS, bl, 0, st, S, (const uint64_t*)keys.p, (const int32_t*)seg.p,
                        (const int32_t*)cells.p, kept.p);
     MGB_HIP_CHECK(hipGetLastError());
@@ -316,11 +283,8 @@ void build(Polyline& Pl, const PolylineIn& in, hipStream_t st) {
     t0.alloc((size_t)H); tkey.alloc((size_t)H); h0.alloc((size_t)H); list.alloc((size_t)H); start.alloc((size_t)V + 2);
     hipLaunchKernelGGL(tail_keys, grH, bl, 0, st, H, V, (const int32_t*)cells.p, (const int32_t*)kept.p, t0.p, h0.p);
     MGB_HIP_CHECK(hipGetLastError());
-    const unsigned vbits = bits_of((uint64_t)V);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, t0.p, tkey.p, h0.p, list.p, (size_t)H, 0u, vbits, st));
-    tmp.ensure(bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, bytes, t0.p, tkey.p, h0.p, list.p, (size_t)H, 0u, vbits, st));
-    hipLaunchKernelGGL(vertex_starts, dim3(grid_1d(H + 1)), bl, 0, st, H, V + 1, (const int32_t*)tkey.p, start.p);
+    sort_pairs(t0.p, tkey.p, h0.p, list.p, H, key_bits((uint64_t)V), tmp, st);
+    hipLaunchKernelGGL(segment_starts<int32_t>, dim3(grid_1d(H + 1)), bl, 0, st, H, V + 1, (const int32_t*)tkey.p, start.p);
     MGB_HIP_CHECK(hipGetLastError());
 
     // ---- 3. successors
@@ -332,7 +296,7 @@ void build(Polyline& Pl, const PolylineIn& in, hipStream_t st) {
     MGB_HIP_CHECK(hipGetLastError());
 
     // ---- 4. pointer doubling: 2^rounds >= 2 H exceeds the length of every list and of every cycle
-    const int32_t rounds = (int32_t)bits_of((uint64_t)(H - 1)) + 1;      // ceil(log2 H) + 1 for H >= 2
+    const int32_t rounds = (int32_t)key_bits((uint64_t)(H - 1)) + 1;      // ceil(log2 H) + 1 for H >= 2
     RankBuf ra, rb;
     ra.alloc((size_t)H); rb.alloc((size_t)H);
     DevBuf<uint8_t> on;
@@ -367,12 +331,8 @@ void build(Polyline& Pl, const PolylineIn& in, hipStream_t st) {
     flag.alloc((size_t)S); id.alloc((size_t)S);
     hipLaunchKernelGGL(line_flags, grS, bl, 0, st, S, (const int32_t*)kept.p, (const int32_t*)a.low, flag.p);
     MGB_HIP_CHECK(hipGetLastError());
-    exclusive_scan<int32_t>(flag.p, id.p, S, tmp, st);
-    int32_t last_id = 0, last_flag = 0;
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_id, id.p + (S - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_flag, flag.p + (S - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    const int64_t L = (int64_t)last_id + last_flag;
+    exclusive_scan(flag.p, id.p, S, tmp, st);
+    const int64_t L = scan_total(flag.p, id.p, S, st);
     Pl.L = L;
     Pl.offsets.alloc((size_t)L + 1);
     Pl.closed.alloc((size_t)L);
@@ -389,7 +349,7 @@ void build(Polyline& Pl, const PolylineIn& in, hipStream_t st) {
     hipLaunchKernelGGL(line_sizes, grS, bl, 0, st, S, (const int32_t*)flag.p, (const int32_t*)id.p,
                        (const int32_t*)a.count, (const uint8_t*)on.p, npoints.p, Pl.closed.p);
     MGB_HIP_CHECK(hipGetLastError());
-    exclusive_scan<int64_t>(npoints.p, Pl.offsets.p, L + 1, tmp, st);
+    exclusive_scan(npoints.p, Pl.offsets.p, L + 1, tmp, st);
     int64_t P = 0;
     MGB_HIP_CHECK(hipMemcpyAsync(&P, Pl.offsets.p + L, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     MGB_HIP_CHECK(hipStreamSynchronize(st));

@@ -13,8 +13,6 @@
 #include <cmath>
 #include <string>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "raycast.hpp"
 #include "render_device.hpp"
 
@@ -207,13 +205,8 @@ void raycast_build(RayCaster& RC, const RayIn& in, hipStream_t st) {
         hipLaunchKernelGGL((ray_count<3>), dim3(grid_1d(R)), dim3(BLOCK), 0, st, R, RC.origin.p, RC.dir.p, b, in.step,
                            in.t_min, in.t_max, RC.tmin.p, RC.h.p, count.p);
     MGB_HIP_CHECK(hipGetLastError());
-    size_t scan_bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, count.p, RC.off.p, (int64_t)0, (size_t)R + 1,
-                                          rocprim::plus<int64_t>(), st));
     DevBuf<char> tmp;
-    tmp.alloc(scan_bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)tmp.p, scan_bytes, count.p, RC.off.p, (int64_t)0, (size_t)R + 1,
-                                          rocprim::plus<int64_t>(), st));
+    exclusive_scan(count.p, RC.off.p, R + 1, tmp, st);
     int64_t S = 0;
     MGB_HIP_CHECK(hipMemcpyAsync(&S, RC.off.p + R, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     MGB_HIP_CHECK(hipStreamSynchronize(st));

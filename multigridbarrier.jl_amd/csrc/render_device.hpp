@@ -1,5 +1,5 @@
 // render_device.hpp -- what the rendering translation units (surface.hip, tubes.hip, raycast.hip, figure.hip) share on
-// the device, one definition each: the launch shape, the 3-vector products, the colour-table lookup, the tail of a shade
+// the device, one definition each: the 3-vector products, the colour-table lookup, the tail of a shade
 // kernel and the two front-to-back compositing steps.  The NumPy twins of the tests transcribe these operations in this
 // order, and a frame of the figure pipeline is bitwise the host chain's frame only while every user runs the same text.
 //
@@ -10,16 +10,14 @@
 #include <cmath>
 #include <cstdint>
 
+#include "device_prims.hpp"        // BLOCK, grid_1d
+
 // No fused multiply-adds in the code below or in a file that includes it.
 #pragma clang fp contract(off)
 
 namespace mgbhip {
 
 namespace {
-
-constexpr int BLOCK = 256;
-
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 __device__ inline double dnan() { return __builtin_nan(""); }
 

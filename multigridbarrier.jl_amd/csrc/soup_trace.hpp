@@ -1,4 +1,4 @@
-// soup_trace.hpp -- rays against a soup of primitives in the grid of box_grid.hpp, whatever the primitive: the one trace
+// soup_trace.hpp -- rays against a soup of primitives in the grid of cell_lists.hpp, whatever the primitive: the one trace
 // kernel, its one dispatch over the hit count, and the host paths around the trace and shade kernels.  surface.hip
 // (triangles) and tubes.hip (capsules) include it and bring the primitive: a small struct passed to the kernel by value
 // that holds its device pointers, declares NPAR, the number of parameters that place a hit on the primitive (u, v: 2;
@@ -14,7 +14,9 @@
 #include <limits>
 #include <string>
 
-#include "box_grid.hpp"
+#include "cell_lists.hpp"
+#include "render_device.hpp"
+#include "surface.hpp"
 
 // No fused multiply-adds in the code below or in a file that includes it: see surface.hip.
 #pragma clang fp contract(off)
@@ -41,7 +43,7 @@ struct SoupHits {
 template <class Prim, int K>
 __global__ void __launch_bounds__(BLOCK) soup_trace_k(int64_t R, const double* __restrict__ org,
                                                       const double* __restrict__ dir, double t_min, double t_max,
-                                                      SurfaceGrid g, const int32_t* __restrict__ start,
+                                                      Grid g, const int32_t* __restrict__ start,
                                                       const int32_t* __restrict__ cand, Prim prim,
                                                       SoupHits<Prim::NPAR> out) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -128,8 +128,6 @@ __global__ void __launch_bounds__(BLOCK) trace_lines(QueryArgs a, Grid g, TraceA
     t.status[q] = status;
 }
 
-inline unsigned grid_1d(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 template <class F>
 void launch(const QueryArgs& a, const Grid& g, const TraceArgs& t, hipStream_t st) {
     hipLaunchKernelGGL((trace_lines<F>), dim3(grid_1d(t.S)), dim3(BLOCK), 0, st, a, g, t);

@@ -6,7 +6,7 @@
 // the element families and their containment tolerances): one thread per triangle forms its box, one block reduces
 // the union, the host picks the cell counts, a count pass and an exclusive scan size the (cell, triangle) pair list, an
 // emit pass writes it in triangle order and a stable radix sort by cell leaves every cell's list ascending in
-// triangle index.  No atomics.  Everything after the boxes lives in box_grid.hpp, and the walk of a ray through the
+// triangle index.  No atomics.  Everything after the boxes lives in cell_lists.hpp, and the walk of a ray through the
 // cells, with its list of the K nearest hits, in soup_trace.hpp; tubes.hip includes both too.  This file brings the
 // triangle: its box, its test and its shading.
 #include <hip/hip_runtime.h>
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(BLOCK) surface_shade_k(int64_t n, int32_t K, c
 void surface_build_device(Surface& S, int64_t T, const double* d_points, GridWork& w, hipStream_t st) {
     S.n = T;
     S.P = 0;
-    S.g = SurfaceGrid{};
+    S.g = Grid{};
     if (T == 0) return;
     if (d_points != S.pts.p) {
         S.pts.ensure((size_t)T * 9);
@@ -122,7 +122,7 @@ void surface_build_device(Surface& S, int64_t T, const double* d_points, GridWor
     }
     w.box.ensure((size_t)T * 6);
     hipLaunchKernelGGL(tri_boxes, dim3(grid_1d(T)), dim3(BLOCK), 0, st, T, S.pts.p, w.box.p);
-    S.P = grid_from_boxes("surface", "triangle", T, w.box.p, S.g, S.start, S.cand, w, st);
+    S.P = cell_lists_from_boxes<3>("surface", "triangle", T, w.box.p, SOUP_CELLS, S.g, S.start, S.cand, w, st);
 }
 
 void surface_build(Surface& S, int64_t T, const double* points, hipStream_t st) {

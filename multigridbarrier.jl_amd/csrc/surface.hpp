@@ -4,29 +4,12 @@
 #include <cstdint>
 
 #include "../../include/mgbhip.h"
+#include "cell_grid.hpp"
 #include "common.hpp"
 
 namespace mgbhip {
 
 constexpr int SURFACE_MAX_HITS = 8;
-
-struct SurfaceGrid {
-    double lo[3], hi[3], inv[3], size[3];   // the padded union box, cells per unit length, cell side
-    double pad;                             // every triangle's box is widened by this much on every side
-    int32_t n[3];
-    int64_t ncell;
-};
-
-// What building a grid needs besides its result: the boxes, their union, the per-box counts and their scan, the unsorted
-// pairs and the scratch of the scan and the sort.  A caller that builds again and again (figure.hip) keeps one, and its
-// buffers grow to the largest soup seen.
-struct GridWork {
-    DevBuf<double> box, ubox;
-    DevBuf<int64_t> count, off;
-    DevBuf<char> tmp;
-    DevBuf<uint32_t> k0, k1;
-    DevBuf<int32_t> v0;
-};
 
 // What a soup of n primitives in a grid keeps, whatever the primitive (soup_trace.hpp): the grid, the sorted (cell,
 // primitive) pair list (4 bytes per pair) and the cell starts (4 bytes per cell) are resident; the per-call buffers (the
@@ -34,7 +17,7 @@ struct GridWork {
 // to the largest call seen and are kept.
 struct Soup {
     int64_t n = 0, P = 0;
-    SurfaceGrid g{};
+    Grid g{};
     DevBuf<int32_t> start, cand;            // ncell + 1, P
     DevBuf<double> o, dn, t, par[2], values, table, layer;
     DevBuf<int32_t> id;

@@ -4,7 +4,7 @@
 // the CPU).  Here a curve is a soup of segments, each with a radius: a capsule, the set of points within r of the
 // segment [a, b] -- a cylinder body with a spherical cap at each end, so consecutive segments of a polyline join
 // without a gap.  One thread per segment forms the box of its two end points widened by its radius; from there the grid
-// is that of surface.hip (csrc/box_grid.hpp) and so is the walk of a ray through its cells (csrc/soup_trace.hpp), the
+// is that of surface.hip (csrc/cell_lists.hpp) and so is the walk of a ray through its cells (csrc/soup_trace.hpp), the
 // one copy of each that both files include.  This file brings the capsule: its box, its test and its shading.
 //
 // The capsule test reports where the ray enters the capsule, as the smallest of up to three candidates: the first root
@@ -147,14 +147,14 @@ __global__ void __launch_bounds__(BLOCK) tube_shade_k(int64_t n, int32_t K, cons
 void tubes_build(Tubes& T, int64_t S, const double* points, const double* radii, hipStream_t st) {
     T.n = S;
     T.P = 0;
-    T.g = SurfaceGrid{};
+    T.g = Grid{};
     if (S == 0) return;
     T.pts.upload(points, (size_t)S * 6, st);
     T.rad.upload(radii, (size_t)S, st);
     DevBuf<double> box;
     box.alloc((size_t)S * 6);
     hipLaunchKernelGGL(seg_boxes, dim3(grid_1d(S)), dim3(BLOCK), 0, st, S, T.pts.p, T.rad.p, box.p);
-    T.P = grid_from_boxes("tubes", "segment", S, box, T.g, T.start, T.cand, st);
+    T.P = cell_lists_from_boxes<3>("tubes", "segment", S, box.p, SOUP_CELLS, T.g, T.start, T.cand, st);
 }
 
 void tubes_trace(Tubes& T, int64_t R, const double* o, const double* dn, double t_min, double t_max, int32_t K, double* t,

@@ -1,5 +1,5 @@
 // tubes.hpp -- rays against a soup of capsules (segments with a radius) behind mgbhip_tubes_* (tubes.hip): the uniform
-// grid of box_grid.hpp over the capsules' boxes, a per-ray traversal kernel that keeps the K nearest entry points, and a
+// grid of cell_lists.hpp over the capsules' boxes, a per-ray traversal kernel that keeps the K nearest entry points, and a
 // per-hit shading kernel.
 #pragma once
 #include <cstdint>
@@ -17,7 +17,7 @@ struct Tubes : Soup {
     DevBuf<double> pts, rad;                // n x 2 x 3, n
 };
 
-// boxes (end points widened by the radius), then the grid of box_grid.hpp; complete on return
+// boxes (end points widened by the radius), then the grid of cell_lists.hpp; complete on return
 void tubes_build(Tubes& T, int64_t S, const double* points, const double* radii, hipStream_t st);
 // o, dn host R x 3 (dn of unit length); t, s host R x K doubles, seg host R x K: the K nearest entries by (t, segment)
 void tubes_trace(Tubes& T, int64_t R, const double* o, const double* dn, double t_min, double t_max, int32_t K, double* t,

@@ -34,9 +34,6 @@
 
 #include <cmath>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "render_device.hpp"
 #include "weld.hpp"
 
@@ -281,32 +278,13 @@ int64_t rank_roots(int64_t n, const int32_t* label, ScanWork& w, hipStream_t st)
     w.flag.ensure((size_t)n); w.rank.ensure((size_t)n);
     hipLaunchKernelGGL(root_flags, dim3(grid_1d(n)), dim3(BLOCK), 0, st, n, label, w.flag.p);
     MGB_HIP_CHECK(hipGetLastError());
-    size_t bytes = 0;
-    MGB_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, w.flag.p, w.rank.p, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(),
-                                          st));
-    w.tmp.ensure(bytes + 16);
-    MGB_HIP_CHECK(rocprim::exclusive_scan((void*)w.tmp.p, bytes, w.flag.p, w.rank.p, (int32_t)0, (size_t)n,
-                                          rocprim::plus<int32_t>(), st));
-    int32_t last_rank = 0, last_flag = 0;
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_rank, w.rank.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipMemcpyAsync(&last_flag, w.flag.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    MGB_HIP_CHECK(hipStreamSynchronize(st));
-    return (int64_t)last_rank + last_flag;
+    exclusive_scan(w.flag.p, w.rank.p, n, w.tmp, st);
+    return scan_total(w.flag.p, w.rank.p, n, st);
 }
 
 __global__ void __launch_bounds__(BLOCK) iota(int64_t n, int32_t* __restrict__ v) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = (int32_t)i;
-}
-
-// start[v] = first sorted position of vertex v (start[V] = M); every vertex has a corner, so each entry is written once
-__global__ void __launch_bounds__(BLOCK) vertex_starts(int64_t M, int64_t V, const int32_t* __restrict__ keys,
-                                                       int32_t* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > M) return;
-    const int64_t a = i == 0 ? -1 : (int64_t)keys[i - 1];
-    const int64_t b = i == M ? V : (int64_t)keys[i];
-    for (int64_t c = a + 1; c <= b; ++c) start[c] = (int32_t)i;
 }
 
 // One lane per vertex: the sum of the face normals cross3(p1 - p0, p2 - p0) of the triangles of its corners, in ascending
@@ -330,12 +308,6 @@ __global__ void __launch_bounds__(BLOCK) vertex_normals(int64_t V, const double*
     const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
     const bool ok = len > 0.0 && isfinite(len);
     for (int k = 0; k < 3; ++k) normals[v * 3 + k] = ok ? n[k] / len : 0.0;
-}
-
-unsigned bits_of(uint64_t n) {
-    unsigned bits = 1;
-    while (bits < 64 && (n >> bits) != 0) ++bits;
-    return bits;
 }
 
 template <int E>
@@ -372,12 +344,7 @@ void build(Weld& W, const WeldIn& in, hipStream_t st) {
     k0.alloc((size_t)M); keys.alloc((size_t)M); c0.alloc((size_t)M); corner.alloc((size_t)M);
     hipLaunchKernelGGL(corner_keys<E>, grM, bl, 0, st, M, g, (const double*)x.p, k0.p, c0.p);
     MGB_HIP_CHECK(hipGetLastError());
-    size_t bytes = 0;
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, k0.p, keys.p, c0.p, corner.p, (size_t)M, 0u,
-                                            (unsigned)(E * WELD_AXIS_BITS), st));
-    tmp.ensure(bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, bytes, k0.p, keys.p, c0.p, corner.p, (size_t)M, 0u,
-                                            (unsigned)(E * WELD_AXIS_BITS), st));
+    sort_pairs(k0.p, keys.p, c0.p, corner.p, M, (unsigned)(E * WELD_AXIS_BITS), tmp, st);
 
     // ---- occupancy guard, before any pair is tested
     DevBuf<int32_t> most;
@@ -413,11 +380,9 @@ void build(Weld& W, const WeldIn& in, hipStream_t st) {
     vkey.alloc((size_t)M); vlist.alloc((size_t)M); vstart.alloc((size_t)W.V + 1);
     hipLaunchKernelGGL(iota, grM, bl, 0, st, M, c0.p);
     MGB_HIP_CHECK(hipGetLastError());
-    const unsigned vbits = bits_of((uint64_t)W.V);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, W.cells.p, vkey.p, c0.p, vlist.p, (size_t)M, 0u, vbits, st));
-    tmp.ensure(bytes + 16);
-    MGB_HIP_CHECK(rocprim::radix_sort_pairs((void*)tmp.p, bytes, W.cells.p, vkey.p, c0.p, vlist.p, (size_t)M, 0u, vbits, st));
-    hipLaunchKernelGGL(vertex_starts, dim3(grid_1d(M + 1)), bl, 0, st, M, W.V, (const int32_t*)vkey.p, vstart.p);
+    sort_pairs(W.cells.p, vkey.p, c0.p, vlist.p, M, key_bits((uint64_t)W.V), tmp, st);
+    // every vertex has a corner, so no segment is empty
+    hipLaunchKernelGGL(segment_starts<int32_t>, dim3(grid_1d(M + 1)), bl, 0, st, M, W.V, (const int32_t*)vkey.p, vstart.p);
     MGB_HIP_CHECK(hipGetLastError());
 
     // ---- components of the welded mesh: the same primitive over the simplex edges
