@@ -7,7 +7,8 @@ differ for EVERY element: entry (r, c) of element e = a(r) b(c) |weight(.. + 7 e
 mixed sign patterns.  u0, the columns of the coarse R and s carry the sign b(c) of their local node, so no row of D z cancels.
 c and w differ per node and row; the slack row of c is negative (the terms of f0 do not cancel).  The slack of z0 is an integer
 >= 8 |q|^p at every node, level and evaluation point (pieces with A, b: the same margin on A y + b; linear rows stay >= 64):
-this file is about the machinery around the cone and the cone formulas at interior points, not about the cone wall.
+this file is about the machinery around the cone and the cone formulas at interior points, not about the cone wall.  The wall
+itself (slack down to 2^-40 of s^(2/p), bounds that follow the conditioning of the residual) is tests/wall_cases.py.
 
 Two levels per case: level 0 is R = blockdiag(dense rounded blocks), not a selection level (prolong kernel, real restriction,
 diag_mask = 0); level 1 is the finest one: the identity for the slack states and for u a selection with empty rows (local
