@@ -160,7 +160,7 @@ int mgbhip_create(mgbhip_ctx** out, int device_id, void* hip_stream) {
     MGB_REQUIRE(out != nullptr, "null output pointer");
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    const bool dbg2 = [] { const char* e = getenv("MGBHIP_DEBUG"); return e && atoi(e) >= 2; }();
+    const bool dbg2 = debug_level() >= 2;
     int count = 0;
     MGB_HIP_CHECK(hipGetDeviceCount(&count));
     MGB_REQUIRE(count > 0, "no HIP device visible: this library has no CPU fallback");

@@ -9,12 +9,11 @@
 #include <string>
 #include <vector>
 
+#include "host_util.hpp"     // InvalidArgument, MGB_REQUIRE, env_on, debug_level, Stopwatch
+
 namespace mgbhip {
 
 struct HipError : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-struct InvalidArgument : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
 
@@ -27,11 +26,6 @@ struct InvalidArgument : std::runtime_error {
                      __FILE__, __LINE__);                                                    \
             throw ::mgbhip::HipError(_buf);                                                  \
         }                                                                                    \
-    } while (0)
-
-#define MGB_REQUIRE(cond, msg)                                   \
-    do {                                                         \
-        if (!(cond)) throw ::mgbhip::InvalidArgument(msg);       \
     } while (0)
 
 // Owning device buffer (hipMalloc / hipFree); never allocated inside a timed loop.

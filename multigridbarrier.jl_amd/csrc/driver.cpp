@@ -22,7 +22,7 @@ constexpr double EPS = std::numeric_limits<double>::epsilon();
 // MGBHIP_DEBUG=1 prints the scalars the Newton control flow branches on (the reference's
 // @mgblog lines, src/newton.jl:256) to stderr.
 bool debug_on() {
-    static const bool on = [] { const char* e = getenv("MGBHIP_DEBUG"); return e && e[0] == '1'; }();
+    static const bool on = env_on("MGBHIP_DEBUG");
     return on;
 }
 #define DBG(...) do { if (debug_on()) { fprintf(stderr, __VA_ARGS__); } } while (0)
@@ -102,7 +102,7 @@ bool trial_values(NewtonCtx& C, double& ynext, double& gnorm_next, int32_t* move
     // the element kernel leaves its workgroup partials of f0; their sum, |g|^2, the non-finite count and the step kernel's
     // "moved" stamp are finished by ONE launch that also stores them in the pinned block (no reduce / copy launches)
     const bool fused = !P->dense;
-    static const bool fuse_restrict = [] { const char* e = getenv("MGBHIP_NO_FUSED_RESTRICT"); return !(e && e[0] == '1'); }();
+    static const bool fuse_restrict = !env_on("MGBHIP_NO_FUSED_RESTRICT");
     P->trial_fuse = mgbhip_problem::TrialFuse();
     if (fused && fuse_restrict) {           // restriction + |g|^2 partials (+ the deferred step) in one launch where the level allows it
         P->trial_fuse.want = true;

@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "cone.hpp"
 #include "elem_layout.hpp"   // ElemMode, elem_group, WIDE_F2_THREADS, the LDS layout of the element kernels
+#include "panel_layout.hpp"  // hel_blocks / hel_block_index / hel_layout, PANEL_ACC_LDS_MAX and the panel staging sizes
 
 namespace mgbhip {
 
@@ -67,21 +68,6 @@ static_assert(sizeof(ElemParams) <= 4096 - 64, "ElemParams must stay well inside
 // update block -- straight into the solver's arena: the element blocks never reach HBM, the leaf level of the
 // factorization and the shared-entry sums of the assembly disappear.  Returns false when no specialisation applies.
 bool launch_elem_f2_condense(const ElemParams& P, hipStream_t st);
-
-// element Hessian slab layout: block-major [block][element][p*p]; blocks (a,b), a <= b, in
-// row-major order of the upper block triangle, each p x p column-major.
-inline int hel_blocks(int nu) { return nu * (nu + 1) / 2; }
-inline int hel_block_index(int a, int b, int nu) { return a * nu - a * (a - 1) / 2 + (b - a); }
-// Offsets of the blocks in the slab: full blocks hold p*p doubles per element, blocks flagged in
-// diag_mask (both states carry identity operators only) hold their p diagonal entries.
-inline int64_t hel_layout(int nu, int64_t N, int p, int diag_mask, int64_t* off) {
-    int64_t total = 0;
-    for (int blk = 0; blk < hel_blocks(nu); ++blk) {
-        off[blk] = total;
-        total += ((diag_mask >> blk) & 1) ? N * p : N * (int64_t)p * p;
-    }
-    return total;
-}
 
 int64_t elem_grid(int p, int64_t N);                     // workgroups
 // dynamic LDS of a generic launch (elem_layout.hpp: one layout for every element kernel, narrow and wide)
@@ -189,11 +175,8 @@ void launch_invert_lists(const int32_t* cidx, int64_t total, int32_t* spos, hipS
 void launch_panel_project(const PanelParams& P, hipStream_t st);
 // small coarse levels with wide supports: element streams x chunks of the packed upper triangle of H
 // accumulated in LDS, then a fixed-order sum over the streams.  H is the dense m x m array (both
-// triangles written); partial holds nstream * m(m+1)/2 doubles; chunk * nsplit >= m(m+1)/2.
-constexpr size_t PANEL_ACC_LDS_MAX = 144 * 1024;
-size_t panel_accumulate_lds(int p, int nu, int ctmax);     // slab variant: 4 waves x one element's staging
-size_t panel_stage_doubles(int p, int nu, int ctmax);      // one element's staging in doubles
-bool panel_accumulate_fits(int p, int nu, int ctmax);       // register-staging limits of the accumulate kernel
+// triangles written); partial holds nstream * m(m+1)/2 doubles; chunk * nsplit >= m(m+1)/2.  (LDS budget and staging
+// sizes: panel_layout.hpp.)
 void launch_panel_accumulate(const PanelParams& P, const int32_t* ecols, int32_t m, int32_t nstream, int32_t nsplit,
                              int32_t chunk, int32_t ctmax, double* partial, double* H, hipStream_t st);
 // same projection as launch_panel_project from LDS-staged panels

@@ -1,6 +1,7 @@
 // mf_analysis.cpp -- ordering + symbolic factorization for the device multifrontal
 // Cholesky (see mf_analysis.hpp).  Host only.
 #include "mf_analysis.hpp"
+#include "host_util.hpp"     // debug_level
 
 #include <algorithm>
 #include <cstring>
@@ -122,7 +123,7 @@ struct Builder {
     void peel(MfPlan& plan) {
         const int64_t n = g.n;
         std::vector<char> sel(n, 0), simp;
-        const bool timing = [] { const char* e = getenv("MGBHIP_DEBUG"); return e && atoi(e) >= 3; }() && n > 200000;
+        const bool timing = debug_level() >= 3 && n > 200000;
         auto t_prev = std::chrono::steady_clock::now();
         auto sub = [&](int round, const char* name) {
             if (!timing) return;
@@ -413,7 +414,7 @@ void mf_analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, const M
     if (n == 0) { plan.level_ptr.assign(1, 0); return; }
     if (n > INT32_MAX) throw std::runtime_error("mf_analyze: n exceeds 32-bit indexing");
     // MGBHIP_DEBUG >= 3: wall-clock of the phases (development aid for the time-to-first-solution breakdown)
-    const bool phase_timing = [] { const char* e = getenv("MGBHIP_DEBUG"); return e && atoi(e) >= 3; }();
+    const bool phase_timing = debug_level() >= 3;
     auto t_prev = std::chrono::steady_clock::now();
     auto phase = [&](const char* name) {
         if (!phase_timing) return;

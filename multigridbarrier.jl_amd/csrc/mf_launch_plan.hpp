@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "host_util.hpp"     // env_on
 #include "mf_analysis.hpp"
 
 namespace mgbhip {
@@ -53,11 +54,10 @@ struct MfSwitches {
     int gather_ct;          // MGBHIP_GATHER_CT=8/16/32: destination columns per workgroup of every mf_big_gather launch on the
                             // static maps (default 0: big_gather_ct chooses per launch)
     static MfSwitches from_env() {
-        auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
         auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-        return {on("MGBHIP_NO_GEO"), on("MGBHIP_OLD_BIG"), !on("MGBHIP_NO_MERGE_GROUPS"), !on("MGBHIP_NO_PACKED_LEAVES"),
-                !on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0),
-                on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0)};
+        return {env_on("MGBHIP_NO_GEO"), env_on("MGBHIP_OLD_BIG"), !env_on("MGBHIP_NO_MERGE_GROUPS"), !env_on("MGBHIP_NO_PACKED_LEAVES"),
+                !env_on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0),
+                env_on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0)};
     }
 };
 

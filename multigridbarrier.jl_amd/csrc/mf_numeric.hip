@@ -134,7 +134,7 @@ struct LevelScope {
     char nm[32];
     StageScope scope;
     static StageTimers& timers_or_dummy(StageTimers* t) {
-        static const bool on = [] { const char* e = getenv("MGBHIP_LEVEL_TIMING"); return e && e[0] == '1'; }();
+        static const bool on = env_on("MGBHIP_LEVEL_TIMING");
         return (t && on) ? *t : g_dummy_timers;
     }
     LevelScope(StageTimers* t, const char* sweep, int level)
@@ -216,7 +216,7 @@ void MfSolver::analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, 
     h_fronts = fd;
     h_a_dst = remap_a_dst(plan, level_launches);
     d_a_dst.upload(h_a_dst, st);
-    if (const char* e = getenv("MGBHIP_DEBUG"); e && atoi(e) >= 2) dump_plan(plan, level_launches);
+    if (debug_level() >= 2) dump_plan(plan, level_launches);
     analyzed = true;
     MGB_HIP_CHECK(hipStreamSynchronize(st));   // host staging vectors go out of scope
 }
@@ -412,7 +412,7 @@ bool MfSolver::enable_condensed(int64_t N, int P, const int32_t* ucol, int64_t s
                                 hipStream_t st) {
     condensed_ok = false;
     int why = 0;
-    struct Report { int& w; ~Report() { if (w) if (const char* e = getenv("MGBHIP_DEBUG"); e && atoi(e) >= 2) fprintf(stderr, "[mgbhip] condensed leaves: plan shape check %d failed\n", w); } } report{why};
+    struct Report { int& w; ~Report() { if (w) if (debug_level() >= 2) fprintf(stderr, "[mgbhip] condensed leaves: plan shape check %d failed\n", w); } } report{why};
     const int32_t nlev = (int32_t)plan.level_ptr.size() - 1;
     if (!analyzed || !plan.border || nlev < 2 || P > 7) { why = 1; return false; }
     const int32_t n0 = plan.level_ptr[1];

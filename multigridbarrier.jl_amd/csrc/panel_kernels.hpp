@@ -412,19 +412,6 @@ __global__ __launch_bounds__(256) void invert_lists_kernel(const int32_t* __rest
 
 }  // namespace
 
-size_t panel_accumulate_lds(int p, int nu, int ctmax) {      // staging of one element, four waves (slab variant)
-    const size_t per_wave = (size_t)p * ctmax + (size_t)(nu * (nu + 1) / 2) * p * p + (size_t)nu * p * ctmax + ctmax;
-    return 4 * per_wave * sizeof(double);
-}
-
-bool panel_accumulate_fits(int p, int nu, int ctmax) {        // register staging limits of panel_accumulate_kernel
-    return p * ctmax <= 4 * 256 && (nu * (nu + 1) / 2) * p * p <= 3 * 256 && ctmax <= 256;
-}
-
-size_t panel_stage_doubles(int p, int nu, int ctmax) {        // staging of one element, one workgroup
-    return (size_t)p * ctmax + (size_t)(nu * (nu + 1) / 2) * p * p + (size_t)nu * p * ctmax + ctmax;
-}
-
 void launch_panel_accumulate(const PanelParams& P, const int32_t* ecols, int32_t m, int32_t nstream, int32_t nsplit,
                              int32_t chunk, int32_t ctmax, double* partial, double* H, hipStream_t st) {
     if (m == 0) return;
@@ -464,7 +451,7 @@ bool launch_panel_project_mfma(const PanelParams& P, hipStream_t st) {
     const int ctpad = P.nu * pp_round_up(P.cmax, 16);            // every state's range padded to a tile
     const PanelMfmaLayout Y = panel_mfma_layout(P.p, P.nu, ctpad);
     const size_t lds = (size_t)Y.total * sizeof(double);
-    static const bool off = [] { const char* e = getenv("MGBHIP_NO_MFMA_PROJECT"); return e && e[0] == '1'; }();
+    static const bool off = env_on("MGBHIP_NO_MFMA_PROJECT");
     // narrow supports (2-D hierarchies: a dozen columns per element) are faster through the staged loop kernel, four elements
     // per workgroup (L = 9: 120 us per launch); wide ones (3-D) are not
     if (off || lds > 64 * 1024 || ctpad < 48) return false;

@@ -1,11 +1,11 @@
 // problem.cpp -- native_to_device for one (AMG, Convex) pair, the per-level R'HR assembly
 // plans, and the device-resident f0/f1/f2/solve primitives behind the C ABI.
 #include "problem.hpp"
+#include "assembly_plan.hpp"
 #include "plan_device.hpp"
 #include "dense.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <atomic>
@@ -17,8 +17,6 @@
 #include <numeric>
 
 using namespace mgbhip;
-
-static constexpr int64_t ACC_MAX_M = 384;
 
 
 // ---------------------------------------------------------------------------------------------
@@ -47,7 +45,7 @@ static void upload_csr(const mgbhip_csr& R, Level& L, hipStream_t st) {
     // transpose (CSR of R') for the gather form of R' * v: on the device from the uploaded R (one stable radix sort by
     // column: rows ascending inside a column, as the host loop it replaced produced them) -- MGBHIP_HOST_TRANSPOSE=1 keeps the
     // host loop, which also sent the transposed arrays over PCIe (0.65 GB at L = 9)
-    static const bool host_T = [] { const char* e = getenv("MGBHIP_HOST_TRANSPOSE"); return e && e[0] == '1'; }();
+    static const bool host_T = env_on("MGBHIP_HOST_TRANSPOSE");
     std::vector<int32_t> tp, tc;
     std::vector<double> tv;
     int32_t maxrow = 0;
@@ -111,9 +109,8 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
     MGB_REQUIRE(d->n_ops >= 1 && d->n_ops <= MGBHIP_MAX_OPS, "operator count out of range");
     MGB_REQUIRE(d->L >= 1 && d->R && d->w, "missing hierarchy or weights");
     MGB_HIP_CHECK(hipSetDevice(ctx->device));
-    const auto t_create0 = std::chrono::steady_clock::now();
-    const bool dbg2 = [] { const char* e = getenv("MGBHIP_DEBUG"); return e && atoi(e) >= 2; }();
-    auto since0 = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create0).count(); };
+    const Stopwatch create_sw;
+    const bool dbg2 = debug_level() >= 2;
     std::unique_ptr<mgbhip_problem> P(new mgbhip_problem());
     P->ctx = ctx;
     P->p = d->p;
@@ -226,7 +223,7 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         P->bw.upload(d->barrier_weights, (size_t)P->n, st);
         P->has_bw = true;
     }
-    if (dbg2) fprintf(stderr, "[mgbhip] problem_create: operators, weights and cone grids on the device after %.3f s\n", since0());
+    if (dbg2) fprintf(stderr, "[mgbhip] problem_create: operators, weights and cone grids on the device after %.3f s\n", create_sw.seconds());
     // hierarchy
     P->levels.resize(d->L);
     for (int l = 0; l < d->L; ++l) MGB_REQUIRE(d->R[l].rows == (int64_t)P->nu * P->n, "prolongation row count must be nu*n");
@@ -238,10 +235,10 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
             (void)hipSetDevice(ctx->device);
             for (int l = next.fetch_add(1); l < d->L; l = next.fetch_add(1)) {
                 try {
-                    const double t0 = since0();
+                    const double t0 = create_sw.seconds();
                     upload_csr(d->R[l], P->levels[l], st);
                     if (dbg2) fprintf(stderr, "[mgbhip] problem_create: level %d (nnz %lld) %.3f -> %.3f s\n", l,
-                                      (long long)d->R[l].rowptr[d->R[l].rows], t0, since0());
+                                      (long long)d->R[l].rowptr[d->R[l].rows], t0, create_sw.seconds());
                 } catch (...) {
                     errors[(size_t)l] = std::current_exception();
                 }
@@ -255,7 +252,7 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
         for (const auto& e : errors)
             if (e) std::rethrow_exception(e);
     }
-    if (dbg2) fprintf(stderr, "[mgbhip] problem_create: %d levels uploaded after %.3f s\n", d->L, since0());
+    if (dbg2) fprintf(stderr, "[mgbhip] problem_create: %d levels uploaded after %.3f s\n", d->L, create_sw.seconds());
     // workspace
     int64_t mmax = 1;
     for (auto& L : P->levels) mmax = std::max(mmax, L.m);
@@ -288,7 +285,7 @@ mgbhip_problem* problem_create(mgbhip_ctx* ctx, const mgbhip_problem_desc* d, mg
     P->d_flag.alloc(4);
     P->d_flag.zero(st);                    // the "moved" stamp of launch_step: no stamp of a later step may be there by chance
     MGB_HIP_CHECK(hipStreamSynchronize(st));
-    if (dbg2) fprintf(stderr, "[mgbhip] problem_create: done after %.3f s\n", since0());
+    if (dbg2) fprintf(stderr, "[mgbhip] problem_create: done after %.3f s\n", create_sw.seconds());
     return P.release();
 }
 
@@ -304,11 +301,7 @@ void mgbhip_problem::ensure_plan_dense(int level) {
     hipStream_t st = stream();
     const int64_t m = L.m, nn = n;
     MGB_REQUIRE(m * m < (int64_t)INT32_MAX, "dense Hessian exceeds 32-bit indexing");
-    L.hHptr.resize(m + 1);
-    L.hHcol.resize((size_t)(m * m));
-    for (int64_t i = 0; i <= m; ++i) L.hHptr[i] = (int32_t)(i * m);
-    for (int64_t i = 0; i < m; ++i)
-        for (int64_t j = 0; j < m; ++j) L.hHcol[i * m + j] = (int32_t)j;
+    dense_pattern(m, L.hHptr, L.hHcol);
     L.nnz = m * m;
     L.Hptr.upload(L.hHptr, st);
     L.Hcol.upload(L.hHcol, st);
@@ -352,128 +345,68 @@ void mgbhip_problem::ensure_plan(int level) {
     Level& L = levels[level];
     if (L.planned) return;
     if (dense) { ensure_plan_dense(level); return; }
-    const auto t_plan0 = std::chrono::steady_clock::now();
     struct PlanTimer {
-        std::chrono::steady_clock::time_point t0; int level;
+        Stopwatch sw; int level;
         ~PlanTimer() {
-            if (const char* dbg = getenv("MGBHIP_DEBUG"); dbg && atoi(dbg) >= 2)
-                fprintf(stderr, "[mgbhip] assembly plan level %d built in %.2f s\n", level,
-                        std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            if (debug_level() >= 2) fprintf(stderr, "[mgbhip] assembly plan level %d built in %.2f s\n", level, sw.seconds());
         }
-    } plan_timer{t_plan0, level};
+    } plan_timer{{}, level};
     hipStream_t st = stream();
-    const int64_t NE = N;
-    const int pp = p;
-    const int64_t nn = n;
-    // 1. per (element, state) column sets
-    bool selection = true;
-    for (size_t q = 0; q < L.hRval.size() && selection; ++q) selection = (L.hRval[q] == 1.0);
-    for (int64_t i = 0; i < L.rows && selection; ++i) selection = (L.hRptr[i + 1] - L.hRptr[i] <= 1);
-    std::vector<int32_t> ecol_ptr((size_t)NE * nu + 1, 0);
-    std::vector<int32_t> ecols;
-    ecols.reserve((size_t)NE * nu * pp);
-    std::vector<int32_t> tmp;
-    for (int64_t e = 0; e < NE; ++e)
-        for (int a = 0; a < nu; ++a) {
-            tmp.clear();
-            for (int r = 0; r < pp; ++r) {
-                const int64_t row = (int64_t)a * nn + e * pp + r;
-                for (int32_t q = L.hRptr[row]; q < L.hRptr[row + 1]; ++q) tmp.push_back(L.hRcol[q]);
-            }
-            std::sort(tmp.begin(), tmp.end());
-            tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-            ecols.insert(ecols.end(), tmp.begin(), tmp.end());
-            ecol_ptr[e * nu + a + 1] = (int32_t)ecols.size();
-            MGB_REQUIRE(ecols.size() < (size_t)INT32_MAX, "assembly plan exceeds 32-bit indexing");
-        }
-    // Blocks (a, b) whose D rows are all identity operators are diagonal per element
-    // (Hel_ab[i, j] = sum_r delta_ri Y_r delta_rj): on selection levels their off-diagonal slots
-    // are structural zeros, exactly as in the reference's sparse products, and stay out of the
-    // pattern.  (With default_D this decouples the broken slack unknowns of an element.)
-    bool state_id[MGBHIP_MAX_NU];
-    for (int a = 0; a < nu; ++a) {
-        state_id[a] = true;
-        for (int k = 0; k < nD; ++k)
-            if (D_state[k] == a && !store->identity[D_op[k]]) state_id[a] = false;
-    }
-    auto structural = [&](int a, int i, int b, int j) { return !(selection && state_id[a] && state_id[b] && i != j); };
-    auto colof = [&](int a, int64_t e, int r) -> int32_t {
-        const int64_t row = (int64_t)a * nn + e * pp + r;
-        return L.hRptr[row + 1] > L.hRptr[row] ? L.hRcol[L.hRptr[row]] : -1;
-    };
-    // 2. output pattern
     const int64_t m = L.m;
-    L.hHptr.assign(m + 1, 0);
-    L.hHcol.clear();
-    // Small general levels with wide supports: dense H through LDS accumulators (launch_panel_accumulate)
-    int32_t cmax_all = 1;
-    for (size_t q = 0; q + 1 < ecol_ptr.size(); ++q) cmax_all = std::max(cmax_all, ecol_ptr[q + 1] - ecol_ptr[q]);
-    {
-        int64_t slab_est = 0, ctmax = 1;
-        for (int64_t e = 0; e < NE; ++e) {
-            const int64_t ct = ecol_ptr[(e + 1) * nu] - ecol_ptr[e * nu];
-            slab_est += ct * ct;
-            ctmax = std::max(ctmax, ct);
-        }
-        L.acc_ctmax = (int32_t)ctmax;
-        // LDS accumulate (launch_panel_accumulate): chunks of the packed upper triangle sized so that
-        // chunk + one element's staging fit the LDS budget; element streams fill the GPU once
-        const int64_t mt = m * (m + 1) / 2;
-        const int64_t stage = (int64_t)panel_stage_doubles(pp, nu, (int)ctmax);
-        const int64_t room = (int64_t)(PANEL_ACC_LDS_MAX / sizeof(double)) - stage;
-        int64_t nsplit = room > 0 ? (mt + room - 1) / room : 1 << 20;
-        if (nsplit < 1) nsplit = 1;
-        const int64_t chunk = (mt + nsplit - 1) / nsplit;
-        const int64_t waves = std::max<int64_t>(8, std::min<int64_t>(NE, (nsplit == 1 ? 512 : 256) / nsplit));
-        L.acc_waves = (int32_t)waves;
-        L.acc_split = (int32_t)nsplit;
-        L.acc_chunk = (int32_t)chunk;
-        // wide coarse supports only (3-D hierarchies): many contributions per entry, few enough
-        // elements per stream; narrow supports are faster through slab + gather
-        constexpr int64_t acc_ne_max = 65536;
-        L.acc = !selection && m > 0 && m <= ACC_MAX_M && room > 0 && nsplit <= 4 && NE <= acc_ne_max && slab_est >= 16 * mt &&
-                panel_accumulate_fits(pp, nu, (int)ctmax);
-        if (const char* dbg = getenv("MGBHIP_DEBUG"); dbg && atoi(dbg) >= 2)
-            fprintf(stderr, "[mgbhip] assembly plan level %d: m=%lld selection=%d cmax=%d slab=%lld doubles, accumulators=%lld -> %s\n", level,
-                    (long long)m, (int)selection, cmax_all, (long long)slab_est, (long long)(waves * mt), L.acc ? "LDS accumulate" : "slab + gather");
+    PlanShape S{N, n, m, p, nu, L.rows, L.hRptr.data(), L.hRcol.data(), L.hRval.data(), (int64_t)L.hRval.size(), 0u, diag_mask_sel};
+    for (int a = 0; a < nu; ++a) {
+        bool id = true;
+        for (int k = 0; k < nD; ++k)
+            if (D_state[k] == a && !store->identity[D_op[k]]) id = false;
+        if (id) S.state_id_mask |= 1u << a;
     }
-    // Pattern + contribution lists: one stable radix sort on the device (plan_device.hip) unless the pair
-    // count is out of its range or MGBHIP_HOST_PLAN=1 asks for the host builder below (kept as the
-    // cross-check: tests compare the two bit for bit).
-    std::vector<int64_t> eoff;
+    // 1. per (element, state) column sets
+    const ElementColumns C = element_columns(S);
+    const bool selection = C.selection;
+    // 2. small general levels with wide supports: dense H through LDS accumulators (launch_panel_accumulate)
+    const AccumulateDecision A = decide_accumulate(p, nu, N, m, selection, C.ctmax, C.slab_est);
+    L.selection = selection;
+    L.acc = A.acc;
+    L.acc_ctmax = (int32_t)C.ctmax;
+    L.acc_waves = A.waves;
+    L.acc_split = A.split;
+    L.acc_chunk = A.chunk;
+    if (debug_level() >= 2)
+        fprintf(stderr, "[mgbhip] assembly plan level %d: m=%lld selection=%d cmax=%d slab=%lld doubles, accumulators=%lld -> %s\n", level,
+                (long long)m, (int)selection, C.cmax, (long long)C.slab_est, (long long)(A.waves * A.tri), L.acc ? "LDS accumulate" : "slab + gather");
+    // uploads of the column sets, once, for the device builder and the projection kernels alike
+    std::vector<int32_t> eoff32{0};          // slab offsets of the projected blocks: general levels without accumulators only
     if (!selection && !L.acc) {
-        eoff.assign((size_t)NE + 1, 0);
-        for (int64_t e = 0; e < NE; ++e) {
-            const int64_t ct = ecol_ptr[(e + 1) * nu] - ecol_ptr[e * nu];
-            eoff[e + 1] = eoff[e] + ct * ct;
-        }
-        MGB_REQUIRE(eoff[NE] < (int64_t)INT32_MAX, "projected slab exceeds 32-bit indexing");
-        L.slab_doubles = eoff[NE];
+        MGB_REQUIRE(C.slab_est < (int64_t)INT32_MAX, "projected slab exceeds 32-bit indexing");
+        L.slab_doubles = C.slab_est;
+        eoff32.assign(C.eoff.begin(), C.eoff.end());
     }
+    if (!selection) {
+        L.cmax = C.cmax;
+        L.eoff.upload(eoff32, st);
+        L.ecol_ptr.upload(C.ecol_ptr, st);
+        L.ecols.upload(C.ecols.data(), C.ecols.size(), st);
+        if (C.ecols.empty()) L.ecols.alloc(1);
+        MGB_HIP_CHECK(hipStreamSynchronize(st));     // eoff32 and C are locals
+    }
+    // 3. pattern + contribution lists: one stable radix sort on the device (plan_device.hip) unless the pair
+    // count is out of its range or MGBHIP_HOST_PLAN=1 asks for the host builder (assembly_plan.cpp, kept as the
+    // cross-check: tests compare the two bit for bit).  Accumulate levels have the dense pattern and no lists.
     bool device_plan = false;
     if (!L.acc && m > 0) {
-        static const bool host_plan = [] { const char* e = getenv("MGBHIP_HOST_PLAN"); return e && e[0] == '1'; }();
+        static const bool host_plan = env_on("MGBHIP_HOST_PLAN");
+        static const bool no_direct = env_on("MGBHIP_NO_DIRECT");
         PlanDeviceIn in;
         std::memset(&in, 0, sizeof(in));
-        in.selection = selection; in.NE = NE; in.n = nn; in.m = m; in.p = pp; in.nu = nu;
+        in.selection = selection; in.NE = N; in.n = n; in.m = m; in.p = p; in.nu = nu;
         in.slab_doubles = L.slab_doubles;
         in.diag_mask_sel = diag_mask_sel;
-        for (int a = 0; a < nu; ++a) if (state_id[a]) in.state_id_mask |= 1u << a;
-        hel_layout(nu, NE, pp, diag_mask_sel, in.sel_off);
-        static const bool no_direct = [] { const char* e = getenv("MGBHIP_NO_DIRECT"); return e && e[0] == '1'; }();
+        in.state_id_mask = S.state_id_mask;
+        hel_layout(nu, N, p, diag_mask_sel, in.sel_off);
         in.extra_base = (selection && !no_direct && hel_cap > 0) ? hel_cap : 0;
         if (!host_plan && plan_device_pairs(in) <= PLAN_DEVICE_MAX_PAIRS) {
-            if (selection) {
-                in.Rptr = L.Rptr.p; in.Rcol = L.Rcol.p;
-            } else {
-                std::vector<int32_t> eoff32(eoff.begin(), eoff.end());
-                L.eoff.upload(eoff32, st);
-                L.ecol_ptr.upload(ecol_ptr, st);
-                L.ecols.upload(ecols.data(), ecols.size(), st);
-                if (ecols.empty()) L.ecols.alloc(1);
-                MGB_HIP_CHECK(hipStreamSynchronize(st));     // eoff32 is a local
-                in.ecol_ptr = L.ecol_ptr.p; in.ecols = L.ecols.p; in.eoff = L.eoff.p;
-            }
+            if (selection) { in.Rptr = L.Rptr.p; in.Rcol = L.Rcol.p; }
+            else { in.ecol_ptr = L.ecol_ptr.p; in.ecols = L.ecols.p; in.eoff = L.eoff.p; }
             build_plan_device(in, L, st);
             device_plan = true;
             if (L.direct) {          // room for the shared sums and the border column behind the slab
@@ -483,235 +416,63 @@ void mgbhip_problem::ensure_plan(int level) {
             }
         }
     }
-    if (device_plan) {
-        // pattern, lists and their host copies are in place
-    } else if (L.acc) {
-        L.hHcol.resize((size_t)(m * m));
-        for (int64_t i = 0; i <= m; ++i) L.hHptr[i] = (int32_t)(i * m);
-        for (int64_t i = 0; i < m; ++i)
-            for (int64_t j = 0; j < m; ++j) L.hHcol[i * m + j] = (int32_t)j;
-    } else if (selection) {
-        // (row, col) pairs of every structural element contribution, bucketed by row
-        std::vector<int32_t> rc(m + 1, 0);
-        auto each_pair = [&](auto&& emit) {
-            for (int64_t e = 0; e < NE; ++e)
-                for (int a = 0; a < nu; ++a)
-                    for (int i = 0; i < pp; ++i) {
-                        const int32_t ci = colof(a, e, i);
-                        if (ci < 0) continue;
-                        for (int b = 0; b < nu; ++b)
-                            for (int j = 0; j < pp; ++j) {
-                                if (!structural(a, i, b, j)) continue;
-                                const int32_t cj = colof(b, e, j);
-                                if (cj >= 0) emit(ci, cj);
-                            }
-                    }
-        };
-        each_pair([&](int32_t ci, int32_t) { rc[ci + 1]++; });
-        std::vector<int64_t> off(m + 1, 0);
-        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + rc[i + 1];
-        std::vector<int32_t> cols((size_t)off[m]);
-        {
-            std::vector<int64_t> fill(off.begin(), off.end() - 1);
-            each_pair([&](int32_t ci, int32_t cj) { cols[(size_t)fill[ci]++] = cj; });
-        }
-        for (int64_t i = 0; i < m; ++i) {
-            int32_t* lo = cols.data() + off[i];
-            int32_t* hi = cols.data() + off[i + 1];
-            std::sort(lo, hi);
-            hi = std::unique(lo, hi);
-            if (lo == hi) L.hHcol.push_back((int32_t)i);     // unknown untouched by any element: keep a diagonal slot
-            else L.hHcol.insert(L.hHcol.end(), lo, hi);
-            MGB_REQUIRE(L.hHcol.size() < (size_t)INT32_MAX, "Hessian pattern exceeds 32-bit indexing");
-            L.hHptr[i + 1] = (int32_t)L.hHcol.size();
-        }
-    } else {
-        // union over elements of (all columns of e) x (all columns of e)
-        std::vector<int32_t> cnt(m + 1, 0);
-        for (int64_t e = 0; e < NE; ++e)
-            for (int32_t q = ecol_ptr[e * nu]; q < ecol_ptr[(e + 1) * nu]; ++q) cnt[ecols[q] + 1]++;
-        for (int64_t j = 0; j < m; ++j) cnt[j + 1] += cnt[j];
-        std::vector<int32_t> c2e(cnt[m]);
-        {
-            std::vector<int32_t> fill(cnt.begin(), cnt.end() - 1);
-            for (int64_t e = 0; e < NE; ++e)
-                for (int32_t q = ecol_ptr[e * nu]; q < ecol_ptr[(e + 1) * nu]; ++q) c2e[fill[ecols[q]]++] = (int32_t)e;
-        }
-        std::vector<int32_t> rowbuf;
-        for (int64_t i = 0; i < m; ++i) {
-            rowbuf.clear();
-            for (int32_t t = cnt[i]; t < cnt[i + 1]; ++t) {
-                const int64_t e = c2e[t];
-                rowbuf.insert(rowbuf.end(), ecols.begin() + ecol_ptr[e * nu], ecols.begin() + ecol_ptr[(e + 1) * nu]);
-            }
-            if (rowbuf.empty()) rowbuf.push_back((int32_t)i);   // unknown untouched by any element: keep a diagonal slot
-            std::sort(rowbuf.begin(), rowbuf.end());
-            rowbuf.erase(std::unique(rowbuf.begin(), rowbuf.end()), rowbuf.end());
-            L.hHcol.insert(L.hHcol.end(), rowbuf.begin(), rowbuf.end());
-            MGB_REQUIRE(L.hHcol.size() < (size_t)INT32_MAX, "Hessian pattern exceeds 32-bit indexing");
-            L.hHptr[i + 1] = (int32_t)L.hHcol.size();
-        }
-    }
     if (!device_plan) {
+        if (L.acc) dense_pattern(m, L.hHptr, L.hHcol);
+        else host_pattern(S, C, L.hHptr, L.hHcol);
         L.nnz = (int64_t)L.hHcol.size();
         L.Hptr.upload(L.hHptr, st);
         L.Hcol.upload(L.hHcol, st);
+        if (!L.acc) {
+            const HostLists lists = host_lists(S, C, L.hHptr, L.hHcol);
+            L.long_lists = lists.long_lists;
+            L.list_total = lists.total;
+            L.cptr.upload(lists.cptr, st);
+            L.cidx.upload(lists.cidx.data(), lists.cidx.size(), st);
+            if (lists.cidx.empty()) L.cidx.alloc(1);
+            MGB_HIP_CHECK(hipStreamSynchronize(st));     // lists is a local
+        }
     }
     L.Hval.alloc((size_t)(L.nnz + L.m + 1));        // + the border column of the bordered factorization (mf_solver.hpp)
-    L.selection = selection;
-    const int NB = hel_blocks(nu);
-    // 3. contribution lists: every structural nonzero of H gathers its summands from a slab in
-    //    element order (no atomics).  Selection levels read the element-block slab written by
-    //    the f2 kernel directly; general levels read the projected slab panel' * Hel * panel.
-    auto find = [&](int32_t row, int32_t col) {
-        const int32_t* lo = L.hHcol.data() + L.hHptr[row];
-        const int32_t* hi = L.hHcol.data() + L.hHptr[row + 1];
-        return (int32_t)(std::lower_bound(lo, hi, col) - L.hHcol.data());
-    };
-    int64_t sel_off[MGBHIP_MAX_NU * (MGBHIP_MAX_NU + 1) / 2];
-    hel_layout(nu, NE, pp, diag_mask_sel, sel_off);
-    auto for_each = [&](auto&& emit) {
-        if (selection) {
-            for (int64_t e = 0; e < NE; ++e)
-                for (int a = 0; a < nu; ++a)
-                    for (int i = 0; i < pp; ++i) {
-                        const int32_t ci = colof(a, e, i);
-                        if (ci < 0) continue;
-                        for (int b = 0; b < nu; ++b)
-                            for (int j = 0; j < pp; ++j) {
-                                if (!structural(a, i, b, j)) continue;
-                                const int32_t cj = colof(b, e, j);
-                                if (cj < 0) continue;
-                                int64_t src;   // slab index of Hel_ab[i, j] (upper block triangle stored)
-                                const int blk = a <= b ? hel_block_index(a, b, nu) : hel_block_index(b, a, nu);
-                                if ((diag_mask_sel >> blk) & 1) src = sel_off[blk] + e * pp + i;            // i == j here
-                                else if (a <= b) src = sel_off[blk] + (e * pp + j) * (int64_t)pp + i;
-                                else src = sel_off[blk] + (e * pp + i) * (int64_t)pp + j;
-                                emit(find(ci, cj), src);
-                            }
-                    }
-        } else {
-            for (int64_t e = 0; e < NE; ++e) {
-                const int32_t base = ecol_ptr[e * nu];
-                const int32_t ct = ecol_ptr[(e + 1) * nu] - base;
-                for (int32_t gj = 0; gj < ct; ++gj)
-                    for (int32_t gi = 0; gi < ct; ++gi)
-                        emit(find(ecols[base + gi], ecols[base + gj]), eoff[e] + gi + (int64_t)ct * gj);
-            }
-        }
-    };
-    if (!L.acc && !device_plan) {
-        // one pass over the contributions: remember (position, source) pairs so that the binary
-        // searches behind `find` run once, then bucket them by position
-        std::vector<int32_t> ccount(L.nnz + 1, 0);
-        std::vector<int32_t> ppos, psrc;
-        for_each([&](int32_t pos, int64_t src) {
-            MGB_REQUIRE(src < (int64_t)INT32_MAX, "slab exceeds 32-bit indexing");
-            ccount[pos + 1]++;
-            ppos.push_back(pos);
-            psrc.push_back((int32_t)src);
-        });
-        int64_t total = 0;
-        for (int64_t q = 0; q < L.nnz; ++q) {
-            total += ccount[q + 1];
-            MGB_REQUIRE(total < (int64_t)INT32_MAX, "contribution list exceeds 32-bit indexing");
-            ccount[q + 1] += ccount[q];
-        }
-        L.long_lists = L.nnz > 0 && total / L.nnz > 48;
-        L.list_total = total;
-        std::vector<int32_t> fill(ccount.begin(), ccount.end() - 1);
-        std::vector<int32_t> cidx((size_t)total);
-        for (size_t t = 0; t < ppos.size(); ++t) cidx[fill[ppos[t]]++] = psrc[t];   // element order within a list
-        L.cptr.upload(ccount, st);
-        L.cidx.upload(cidx.data(), cidx.size(), st);
-        if (cidx.empty()) L.cidx.alloc(1);
-        MGB_HIP_CHECK(hipStreamSynchronize(st));
-    }
     if (!L.acc && L.long_lists && L.nnz > 0) {
-        // very long lists (average > 2048 contributions): split every list into <= 64 fixed chunks
+        // 4. very long lists (average > 2048 contributions): split every list into <= 64 fixed chunks
         std::vector<int32_t> hc((size_t)L.nnz + 1);
         L.cptr.download(hc.data(), hc.size(), st);
         MGB_HIP_CHECK(hipStreamSynchronize(st));
-        int64_t maxlen = 0;
-        for (int64_t q = 0; q < L.nnz; ++q) maxlen = std::max<int64_t>(maxlen, hc[q + 1] - hc[q]);
-        if (hc[L.nnz] / L.nnz > 2048) {
-            L.gather_chunk = (int32_t)std::max<int64_t>(1024, (maxlen + 63) / 64);
-            L.gather_nchunk = (int32_t)((maxlen + L.gather_chunk - 1) / L.gather_chunk);
+        const GatherChunks G = decide_gather_chunks(hc.data(), L.nnz);
+        if (G.gather_nchunk > 0) {
+            L.gather_chunk = G.gather_chunk;
+            L.gather_nchunk = G.gather_nchunk;
             L.gather_part.alloc(2 * (size_t)L.nnz * (size_t)L.gather_nchunk);      // (sum, carried error) per chunk
         }
     }
     if (!selection && !L.acc && L.nnz > 0) {
-        // positions of the upper triangle: `symmetric(H)` (src/newton.jl:253) and the factorization read nothing else, so the
-        // Newton loop projects and gathers only those (half the slab stores, half the gather traffic)
-        // ... in COLUMN-major order (column j, rows i <= j ascending): the summands of (i, j) and (i + 1, j) sit next to each
-        // other in every element block that holds both (block entry ci + ct cj, columns sorted), so neighbouring waves of the
-        // gather share their cache lines; in row-major order every 8-byte summand was a line of its own.  The order of the
-        // POSITIONS changes, not the order inside a sum: same values.
-        std::vector<int32_t> up;
-        {
-            std::vector<int32_t> cnt((size_t)m + 1, 0);
-            for (int64_t i = 0; i < m; ++i)
-                for (int32_t q = L.hHptr[i]; q < L.hHptr[i + 1]; ++q)
-                    if (L.hHcol[q] >= i) cnt[(size_t)L.hHcol[q] + 1]++;
-            for (int64_t j = 0; j < m; ++j) cnt[(size_t)j + 1] += cnt[(size_t)j];
-            up.resize((size_t)cnt[(size_t)m]);
-            static const bool row_major = [] { const char* e = getenv("MGBHIP_UPPER_ROW_MAJOR"); return e && e[0] == '1'; }();
-            size_t w = 0;
-            for (int64_t i = 0; i < m; ++i)
-                for (int32_t q = L.hHptr[i]; q < L.hHptr[i + 1]; ++q)
-                    if (L.hHcol[q] >= i) {
-                        if (row_major) up[w++] = q;
-                        else up[(size_t)cnt[(size_t)L.hHcol[q]]++] = q;
-                    }
-        }
+        // 5. positions of the upper triangle: all the Newton loop assembles on a projected level
+        static const bool row_major = env_on("MGBHIP_UPPER_ROW_MAJOR");
+        const std::vector<int32_t> up = upper_positions(L.hHptr, L.hHcol, m, row_major);
         L.nup = (int64_t)up.size();
         L.upq.upload(up, st);
-        MGB_HIP_CHECK(hipStreamSynchronize(st));
+        MGB_HIP_CHECK(hipStreamSynchronize(st));         // up is a local
     }
     if (!selection) {
-        // dense R panels per (element, state): p x c, column-major
-        std::vector<double> panels((size_t)pp * ecols.size(), 0.0);
-        for (int64_t e = 0; e < NE; ++e)
-            for (int a = 0; a < nu; ++a) {
-                const int32_t o = ecol_ptr[e * nu + a], c = ecol_ptr[e * nu + a + 1] - o;
-                for (int r = 0; r < pp; ++r) {
-                    const int64_t row = (int64_t)a * nn + e * pp + r;
-                    for (int32_t q = L.hRptr[row]; q < L.hRptr[row + 1]; ++q) {
-                        const int32_t* lo = ecols.data() + o;
-                        const int32_t ia = (int32_t)(std::lower_bound(lo, lo + c, L.hRcol[q]) - lo);
-                        panels[(size_t)pp * o + r + (size_t)pp * ia] += L.hRval[q];
-                    }
-                }
-            }
-        L.cmax = 1;
-        for (size_t q = 0; q + 1 < ecol_ptr.size(); ++q) L.cmax = std::max(L.cmax, ecol_ptr[q + 1] - ecol_ptr[q]);
-        std::vector<int32_t> eoff32(eoff.begin(), eoff.end());
-        if (eoff32.empty()) eoff32.push_back(0);
-        L.eoff.upload(eoff32, st);
-        L.ecol_ptr.upload(ecol_ptr, st);
-        L.ecols.upload(ecols.data(), ecols.size(), st);
+        // 6. dense R panels, the projected slab and its list order, the accumulators
+        const std::vector<double> panels = element_panels(S, C);
         L.panels.upload(panels.data(), panels.size(), st);
-        if (ecols.empty()) { L.ecols.alloc(1); L.panels.alloc(1); }
+        if (panels.empty()) L.panels.alloc(1);
         L.slab.alloc((size_t)std::max<int64_t>(L.slab_doubles, 1));
-        static const bool no_sorted = [] { const char* e = getenv("MGBHIP_NO_SORTED_SLAB"); return e && e[0] == '1'; }();
+        static const bool no_sorted = env_on("MGBHIP_NO_SORTED_SLAB");
         if (!L.acc && L.nnz > 0 && L.slab_doubles > 0 && !no_sorted) {
             // Every entry of an element's projected block contributes to exactly one Hessian entry: the lists are a
             // permutation of the slab.  Store the slab in LIST order (the projection scatters through spos, 4 B per entry)
             // and a contribution list is a contiguous run: the gather streams it instead of fetching one cache line per
             // 8-byte summand (fem3d L = 6 phase I, m = 1 349: 23 M summands per assembly).
-            int32_t total = 0;
-            MGB_HIP_CHECK(hipMemcpyAsync(&total, L.cptr.p + L.nnz, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            MGB_HIP_CHECK(hipStreamSynchronize(st));
-            if ((int64_t)total == L.slab_doubles) {
+            if (L.list_total == L.slab_doubles) {
                 L.spos.alloc((size_t)L.slab_doubles);
                 launch_invert_lists(L.cidx.p, L.slab_doubles, L.spos.p, st);
                 L.sorted_slab = true;
             }
         }
-        if (L.acc) {
-            L.acc_copies.alloc((size_t)L.acc_waves * (size_t)(m * (m + 1) / 2));
-        }
-        MGB_HIP_CHECK(hipStreamSynchronize(st));
+        if (L.acc) L.acc_copies.alloc((size_t)L.acc_waves * (size_t)A.tri);
+        MGB_HIP_CHECK(hipStreamSynchronize(st));         // panels is a local
     }
     MGB_HIP_CHECK(hipStreamSynchronize(st));
     L.planned = true;
@@ -881,7 +642,7 @@ void mgbhip_problem::eval_f01_launch(int level, const double* d_s, const double*
 
 bool mgbhip_problem::try_enable_condensed(int level) {
     Level& L = levels[level];
-    static const bool off = [] { const char* e = getenv("MGBHIP_NO_CONDENSE"); return e && e[0] == '1'; }();
+    static const bool off = env_on("MGBHIP_NO_CONDENSE");
     if (off || dense || !L.selection || !L.direct || nu != 2 || p != 7 || L.hRptr.empty()) return false;
     if (!L.solver.analyzed || !L.solver.has_direct_map()) return false;
     // R of a selection level: row (state, node) has at most one entry, equal to 1.  Slack unknowns must be numbered
@@ -897,7 +658,7 @@ bool mgbhip_problem::try_enable_condensed(int level) {
         if (L.hRptr[rs + 1] - L.hRptr[rs] != 1 || (int64_t)L.hRcol[L.hRptr[rs]] != slack0 + node) return false;
     }
     const bool ok = L.solver.enable_condensed(N, p, ucol.data(), slack0, L.nnz, hel_cap + L.nshared, stream());
-    if (const char* dbg = getenv("MGBHIP_DEBUG"); dbg && atoi(dbg) >= 2)
+    if (debug_level() >= 2)
         fprintf(stderr, "[mgbhip] level %d: condensed leaves %s\n", level, ok ? "enabled" : "not applicable");
     return ok;
 }
@@ -971,7 +732,7 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
             PP.ecol_ptr = L.ecol_ptr.p; PP.panels = L.panels.p; PP.eoff = L.eoff.p;
             PP.hel = d_hel.p; PP.slab = L.slab.p; PP.cmax = L.cmax; PP.spos = nullptr;
             // Newton loop (materialize = false with a right-hand side): only the upper triangle of H is formed
-            static const bool full_h = [] { const char* e = getenv("MGBHIP_FULL_COARSE_H"); return e && e[0] == '1'; }();
+            static const bool full_h = env_on("MGBHIP_FULL_COARSE_H");
             const bool upper = !materialize && rhs != nullptr && L.nup > 0 && !L.acc && !full_h;
             PP.upper_only = upper ? 1 : 0;
             if (L.acc) {
@@ -1004,17 +765,16 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
 }
 
 void mgbhip_problem::wait_results(double seq) {
-    static const bool poll = [] { const char* e = getenv("MGBHIP_NO_POLL"); return !(e && e[0] == '1'); }();
+    static const bool poll = !env_on("MGBHIP_NO_POLL");
     hipStream_t st = stream();
     if (poll && seq != 0.0) {
         volatile const double* stamp = pin.d + 15;
-        const auto t0 = std::chrono::steady_clock::now();
+        const Stopwatch sw;
         for (int spins = 0;; ++spins) {
             if (__atomic_load_n(reinterpret_cast<const volatile uint64_t*>(stamp), __ATOMIC_ACQUIRE) ==
                 *reinterpret_cast<const uint64_t*>(&seq))
                 return;
-            if ((spins & 1023) == 1023 &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 1e-3)
+            if ((spins & 1023) == 1023 && sw.seconds() > 1e-3)
                 break;                                   // a long kernel or an error: let the runtime wait (and report)
         }
     }
@@ -1028,7 +788,7 @@ void mgbhip_problem::read_scalars(int lo, int n) {
 }
 
 bool mgbhip_problem::can_fuse_step(int level) const {
-    static const bool off = [] { const char* e = getenv("MGBHIP_NO_FUSED_STEP"); return e && e[0] == '1'; }();
+    static const bool off = env_on("MGBHIP_NO_FUSED_STEP");
     return !off && !dense && !sharded() && levels[level].R_unit;
 }
 
@@ -1036,7 +796,7 @@ void mgbhip_problem::ensure_analysis(int level) {
     Level& L = levels[level];
     if (L.solver.analyzed) return;
     hipStream_t st = stream();
-    const auto t0 = std::chrono::steady_clock::now();
+    const Stopwatch sw;
     // ordering hint: the centroid of every level-J basis function, sum_i |R_ij| x_i / sum_i |R_ij|
     std::vector<double> cen;
     if (!hx.empty() && xdim > 0 && !L.hRptr.empty()) {
@@ -1062,9 +822,9 @@ void mgbhip_problem::ensure_analysis(int level) {
     }
     L.solver.analyze(L.m, L.hHptr.data(), L.hHcol.data(), st, cen.empty() ? nullptr : cen.data(), xdim, leaves,
                      L.sharded ? L.h_iface.data() : nullptr, L.sharded ? (int64_t)L.h_iface.size() : 0);
-    if (const char* dbg = getenv("MGBHIP_DEBUG"); dbg && atoi(dbg) >= 2)
+    if (debug_level() >= 2)
         fprintf(stderr, "[mgbhip] symbolic analysis level %d (m=%lld, nnz=%lld): %.2f s\n", level, (long long)L.m,
-                (long long)L.nnz, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                (long long)L.nnz, sw.seconds());
 }
 
 // Everything the first Newton iteration of every level would build lazily -- assembly plan, symbolic analysis, direct value map,
@@ -1073,10 +833,10 @@ void mgbhip_problem::ensure_analysis(int level) {
 void mgbhip_problem::prepare_all() {
     if (prepared) return;
     prepared = true;
-    static const bool off = [] { const char* e = getenv("MGBHIP_LAZY_PLANS"); return e && e[0] == '1'; }();
+    static const bool off = env_on("MGBHIP_LAZY_PLANS");
     if (off || dense || sharded() || levels.size() < 2) return;     // sharded levels order their collectives: stay lazy
     const int Ln = (int)levels.size();
-    const auto t_prep0 = std::chrono::steady_clock::now();
+    const Stopwatch prep_sw;
     std::vector<std::exception_ptr> errors((size_t)Ln);
     std::atomic<int> next{Ln - 1};
     auto worker = [&] {
@@ -1102,15 +862,14 @@ void mgbhip_problem::prepare_all() {
     for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
     worker();
     for (auto& t : pool) t.join();
-    if (const char* dbg = getenv("MGBHIP_DEBUG"); dbg && atoi(dbg) >= 2)
-        fprintf(stderr, "[mgbhip] prepare_all: %d levels in %.3f s\n", Ln,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_prep0).count());
+    if (debug_level() >= 2)
+        fprintf(stderr, "[mgbhip] prepare_all: %d levels in %.3f s\n", Ln, prep_sw.seconds());
     // A level that could not be prepared (its plan exceeds an index range, the device is out of memory) is left to the lazy
     // path: the solve may never visit it (levels 8 and 9 of the L = 9 ladder are not), and if it does the error is raised there.
     for (size_t l = 0; l < errors.size(); ++l) {
         if (!errors[l]) continue;
         (void)hipGetLastError();
-        if (const char* dbg = getenv("MGBHIP_DEBUG"); dbg && atoi(dbg) >= 1) {
+        if (debug_level() >= 1) {
             try { std::rethrow_exception(errors[l]); }
             catch (const std::exception& ex) { fprintf(stderr, "[mgbhip] prepare: level %zu left to the lazy path (%s)\n", l, ex.what()); }
             catch (...) { fprintf(stderr, "[mgbhip] prepare: level %zu left to the lazy path\n", l); }
@@ -1124,20 +883,18 @@ void mgbhip_problem::ensure_direct(int level) {
     Level& L = levels[level];
     if (!(L.selection && L.direct) || dense || !L.solver.analyzed) return;
     hipStream_t st = stream();
-    const bool dbg2 = [] { const char* e = getenv("MGBHIP_DEBUG"); return e && atoi(e) >= 2; }();
+    const bool dbg2 = debug_level() >= 2;
     if (!L.solver.has_direct_map()) {
-        const auto t0 = std::chrono::steady_clock::now();
+        const Stopwatch sw;
         L.solver.set_direct_map(L.h_vmap.data(), L.nnz, hel_cap + L.nshared, st);
         std::vector<int32_t>().swap(L.h_vmap);        // 4 B per nonzero: not needed again
-        if (dbg2) fprintf(stderr, "[mgbhip] direct value map level %d: %.2f s\n", level,
-                          std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        if (dbg2) fprintf(stderr, "[mgbhip] direct value map level %d: %.2f s\n", level, sw.seconds());
     }
     if (!L.condense_tried) {          // from the next f2 on the element kernel writes the leaf fronts itself
-        const auto t0 = std::chrono::steady_clock::now();
+        const Stopwatch sw;
         L.condense_tried = true;
         L.condense = try_enable_condensed(level);
-        if (dbg2) fprintf(stderr, "[mgbhip] condensed-leaf set-up level %d: %.2f s\n", level,
-                          std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        if (dbg2) fprintf(stderr, "[mgbhip] condensed-leaf set-up level %d: %.2f s\n", level, sw.seconds());
     }
 }
 
@@ -1176,7 +933,7 @@ void mgbhip_problem::factor(int level, const double* rhs) {
 
 bool mgbhip_problem::lu_fallback(int level, const double* d_g, double* d_xout) {
     Level& L = levels[level];
-    static const bool off = [] { const char* e = getenv("MGBHIP_NO_LU_FALLBACK"); return e && e[0] == '1'; }();
+    static const bool off = env_on("MGBHIP_NO_LU_FALLBACK");
     if (off || sharded() || !L.have_H || L.H_in_slab || L.m < 1 || L.m > DENSE_LU_MAX_M || L.Hval.n < (size_t)L.nnz || !L.Hptr.p || !L.Hcol.p)
         return false;
     hipStream_t st = stream();

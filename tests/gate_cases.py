@@ -1,5 +1,6 @@
 """Hand-built fem1d hierarchies that put every shape-gated transfer, reduction and assembly kernel on both sides of its gate
-(csrc/problem.cpp: upload_level and the assembly-plan builder; DESIGN.md "Shape gates"), with exact references.
+(csrc/problem.cpp: upload_csr; csrc/assembly_plan.cpp: the assembly-plan gates; DESIGN.md "Shape gates"), with exact
+references.
 
 Every hierarchy is fem1d, k = 1, a uniform mesh of N elements (n = 2 N broken nodes), default D / f / g, the power cone with
 p = 1.5, written out as plain dataclasses like helpers.literal_fem1d_problem.  The last level is the true finest one (interior
@@ -341,7 +342,8 @@ def inputs(name, level):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the gate arithmetic of csrc/problem.cpp / csrc/kernels.hip, restated from R alone (p = 2 nodes per element, nu = 2 states)
+# the gate arithmetic of csrc/problem.cpp (upload_csr), csrc/assembly_plan.cpp, csrc/panel_layout.hpp and csrc/kernels.hip, restated
+# from R alone (p = 2 nodes per element, nu = 2 states)
 # ---------------------------------------------------------------------------------------------------------------------
 
 def element_columns(R, N):

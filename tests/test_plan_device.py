@@ -72,3 +72,24 @@ def test_plans_prepared_side_by_side_equal_the_lazily_built_ones_bitwise():
     assert len(keys) >= 4
     for k in keys:
         assert eager[k] == lazy[k], k
+
+
+@pytest.mark.gpu
+def test_host_plan_equals_device_plan_through_every_projection_kernel():
+    """The host builder (csrc/assembly_plan.cpp, MGBHIP_HOST_PLAN=1) against the device builder on the hand-built hierarchies of
+    tests/gate_cases.py whose levels are pinned to a projection kernel: proj_small (N = 64: accumulate, staged, accumulate,
+    selection) and proj_wide (N = 8: two matrix-core levels, selection).  Per level: pattern and f2 values bitwise equal, and
+    `level_plan` equal in every field but `direct` (the host builder never builds the direct map)."""
+    import gate_cases as G
+    dev = _run({"MGBHIP_HOST_PLAN": "0"}, "gates")
+    host = _run({"MGBHIP_HOST_PLAN": "1"}, "gates")
+    want = {f"{name}/{l}": lv.expect["projection"] if "projection" in lv.expect else "none"
+            for name in ("proj_small", "proj_wide") for l, lv in enumerate(G.CASE[name].all_levels())}
+    assert list(want.values()) == ["accumulate", "staged", "accumulate", "none", "mfma", "mfma", "none"]
+    assert dev.keys() == host.keys() == want.keys()
+    for k, projection in want.items():
+        (dev_digest, dev_plan), (host_digest, host_plan) = dev[k], host[k]
+        assert dev_plan["projection"] == projection and dev_plan["planned"], (k, dev_plan)
+        assert dev_digest == host_digest, k
+        assert not host_plan["direct"], (k, host_plan)
+        assert {f: v for f, v in dev_plan.items() if f != "direct"} == {f: v for f, v in host_plan.items() if f != "direct"}, k

@@ -1,6 +1,9 @@
 """Digest of the assembled Hessians (pattern + values) of every level of a few small problems.  Run once with
 the device plan builder and once with MGBHIP_HOST_PLAN=1: identical digests mean identical patterns AND
-identical contribution-list order (the sums are bitwise equal only then).  Used by tests/test_plan_device.py."""
+identical contribution-list order (the sums are bitwise equal only then).  Used by tests/test_plan_device.py.
+
+`plan_digest.py gates`: the same digest plus `level_plan` for every level of the hand-built hierarchies proj_small and proj_wide
+of tests/gate_cases.py, whose levels are pinned to the accumulate, staged and matrix-core projection kernels."""
 import hashlib
 import json
 import os
@@ -19,7 +22,26 @@ def digest(H):
     return h.hexdigest()
 
 
+def gates():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import gate_cases as G
+    from mgb_amd.device import DeviceProblem, HipContext
+    out = {}
+    ctx = HipContext(0)
+    for name in ("proj_small", "proj_wide"):
+        prob = G.problem(name)
+        P = DeviceProblem(ctx, prob.M[0], prob.Q)
+        for l in range(len(G.CASE[name].all_levels())):
+            H = P.f2(l, *G.inputs(name, l))
+            out[f"{name}/{l}"] = [digest(H), P.level_plan(l)]
+        P.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "gates":
+        return gates()
     import mgb_amd as m
     from mgb_amd.device import DeviceMGBProblem
     cases = {
