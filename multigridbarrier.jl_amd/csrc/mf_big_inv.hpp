@@ -1,6 +1,7 @@
 // mf_big_inv.hpp -- large fronts, inverse-based generation (fronts with lds_cap < m <= BIG_INV_MAX_M): the MFMA step
 // kernel mf_big_step, the block-0 kernel mf_big_diag0, the gathering assembly mf_big_gather (and mf_big_gather_lds), the triangle pack of the
-// interface front (mf_tri_pack) and the single-workgroup solves mf_fwd_inv / mf_bwd_inv.
+// interface front (mf_tri_pack) and the single-workgroup solves mf_fwd_inv / mf_bwd_inv (mf_bwd_inv_split: the boundary product
+// of a backward launch of few fronts shared among several workgroups per front).
 //
 // One launch per 32-column step.  The diagonal block of step j is factored AND inverted ahead of
 // time by the look-ahead workgroup of step j-1 (W_j = L_jj^{-1}, d_j); every trailing tile then
@@ -789,19 +790,27 @@ __global__ __launch_bounds__(BIGI_THREADS) void mf_fwd_inv(const FrontDev* __res
 
 // backward:  x_j = u_j - M_j G_j,  G[q] = sum over solved rows r of A[r, q] x[r]
 #ifdef MGB_PROBE_BWD       // root front of a sweep: phase timestamps (tools/gpu_probe_bwd.py; build with -DMGB_STEP_PROBE -DMGB_PROBE_BWD:
-                           // the slots are shared with the mf_big_step probes)
-#define BP(i) do { if (threadIdx.x == 0 && gridDim.x == 1 && fr[first].k > 400) g_probe[(i)] = wall_clock64(); } while (0)
+                           // the slots are shared with the mf_big_step probes).  -DMGB_PROBE_BWD=2: the first front of the
+                           // two-front level below the root instead (k about 255 with a boundary of about 512 rows at L = 9)
+#define BP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0 && gridDim.x == (MGB_PROBE_BWD) && fr[first].k > 400 / (MGB_PROBE_BWD)) g_probe[(i)] = wall_clock64(); } while (0)
 #else
 #define BP(i) do { } while (0)
 #endif
-__global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv(const FrontDev* __restrict__ fr, int32_t first,
-                                                           const int32_t* __restrict__ front_idx,
-                                                           const double* __restrict__ arena,
-                                                           const double* __restrict__ dvec,
-                                                           const double* __restrict__ y, double* __restrict__ x) {
+// One front of a backward launch.  SPLIT = false: the whole front in this workgroup (mf_bwd_inv, `fi` = blockIdx.x).
+// SPLIT = true (mf_bwd_inv_split, grid (S, count)): the boundary product of front `fi` is shared by columns among the S
+// workgroups of blockIdx.x -- 4-column group g goes to wave g % 16 of workgroup (g / 16) % S, the loop and the reductions
+// are those of the unsplit kernel -- and lands in gscr (gstride doubles per front of the launch).  Hand-off without
+// waiting: a workgroup publishes its columns (write-through stores, drained by every wave; one agent-scope release), then
+// takes a ticket on cnt[fi]; every ticket but the last returns, the last workgroup to arrive resets the counter, reads all
+// k products back past its L1 and runs the block recurrence.  No loop waits on another workgroup's memory.
+template <bool SPLIT>
+__device__ __forceinline__ void bwd_inv_front(const FrontDev* __restrict__ fr, int32_t first, uint32_t fi,
+                                              const int32_t* __restrict__ front_idx, const double* __restrict__ arena,
+                                              const double* __restrict__ dvec, const double* __restrict__ y,
+                                              double* __restrict__ x, double* gscr, int gstride, uint32_t* cnt) {
     extern __shared__ double sh[];
     BP(0);
-    const FrontDev F = fr[first + blockIdx.x];
+    const FrontDev F = fr[first + fi];
     const int m = F.m, k = F.k;
     const int tid = threadIdx.x, nt = BIGI_THREADS;
     const int lane = tid & 63, wave = tid >> 6;
@@ -824,6 +833,50 @@ __global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv(const FrontDev* __res
     // and butterflies overlap (a wave owns up to k / 16 columns, each a dependent load -> reduce chain)
     // A front with a handful of boundary rows (the root: the border row alone) takes one thread per column instead: the
     // butterflies of 511 columns for one row each kept the LDS pipeline of the workgroup busy for 17 us.
+    if (SPLIT) {
+        const bool thin = m - k <= 8;
+        const int S = (int)gridDim.x, part = (int)blockIdx.x;
+        double* gs = gscr + (int64_t)fi * gstride;                     // k <= gstride: the launch's max_k, rounded up
+        if (!thin)
+            for (int q0 = 4 * (wave + (nt / 64) * part); q0 < k; q0 += 4 * (nt / 64) * S) {
+                double s[4] = {0.0, 0.0, 0.0, 0.0};                    // the unsplit loop below, column for column
+                for (int r = k + lane; r < m; r += 64) {
+                    const double t = tl[r];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) s[u] += Fm[(int64_t)min(q0 + u, k - 1) * m + r] * t;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    s[u] += quad_perm_f64<0xB1>(s[u]);
+                    s[u] += quad_perm_f64<0x4E>(s[u]);
+                    s[u] += quad_perm_f64<0x124>(s[u]);
+                    s[u] += quad_perm_f64<0x128>(s[u]);
+                    s[u] += __shfl_xor(s[u], 16, 64);
+                    s[u] += __shfl_xor(s[u], 32, 64);
+                }
+                if (lane < 4 && q0 + lane < k)
+                    __hip_atomic_store(gs + q0 + lane, s[lane == 0 ? 0 : (lane == 1 ? 1 : (lane == 2 ? 2 : 3))], __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+            }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every storing wave drains its stores ...
+        __syncthreads();
+        uint32_t* ticket = reinterpret_cast<uint32_t*>(zq);            // (zq is first written inside the block loop)
+        if (tid == 0) {                                                // ... one lane releases and takes the ticket
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t t = __hip_atomic_fetch_add(cnt + fi, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == (uint32_t)(S - 1)) {                              // last to arrive: every other workgroup's columns are out
+                __hip_atomic_store(cnt + fi, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            ticket[0] = t;
+        }
+        __syncthreads();
+        if (ticket[0] != (uint32_t)(S - 1)) return;
+        if (!thin)
+            for (int q = tid; q < k; q += nt) gl[q] = __hip_atomic_load(gs + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (m - k <= 8) {
         for (int q = tid; q < k; q += nt) {
             const double* Aq = Fm + (int64_t)q * m;
@@ -831,7 +884,7 @@ __global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv(const FrontDev* __res
             for (int r = k; r < m; ++r) sq += Aq[r] * tl[r];
             gl[q] = sq;
         }
-    } else
+    } else if (!SPLIT)
     for (int q0 = 4 * wave; q0 < k; q0 += 4 * (nt / 64)) {
         double s[4] = {0.0, 0.0, 0.0, 0.0};
         for (int r = k + lane; r < m; r += 64) {
@@ -956,6 +1009,23 @@ __global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv(const FrontDev* __res
     BP(9);
 }
 
+__global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv(const FrontDev* __restrict__ fr, int32_t first,
+                                                           const int32_t* __restrict__ front_idx,
+                                                           const double* __restrict__ arena,
+                                                           const double* __restrict__ dvec,
+                                                           const double* __restrict__ y, double* __restrict__ x) {
+    bwd_inv_front<false>(fr, first, blockIdx.x, front_idx, arena, dvec, y, x, nullptr, 0, nullptr);
+}
+// grid (S, count), S = bwd_inv_split of the launch (mf_launch_plan.hpp)
+__global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv_split(const FrontDev* __restrict__ fr, int32_t first,
+                                                                 const int32_t* __restrict__ front_idx,
+                                                                 const double* __restrict__ arena,
+                                                                 const double* __restrict__ dvec,
+                                                                 const double* __restrict__ y, double* __restrict__ x,
+                                                                 double* gscr, int gstride, uint32_t* cnt) {
+    bwd_inv_front<true>(fr, first, blockIdx.y, front_idx, arena, dvec, y, x, gscr, gstride, cnt);
+}
+
 // ---- host launchers ------------------------------------------------------------------------------------------
 // Assembly of the fronts of a large-front launch: the gathering kernel when it applies (big_assembly_kind,
 // mf_launch_plan.hpp), the column-tiled one otherwise.  with_diag asks the gather launch for an extra workgroup per
@@ -1014,6 +1084,13 @@ inline void launch_fwd_inv(const SolveArgs& a, const MfLaunch& L) {
                        a.ug_ptr, a.ug_src, a.arena, a.dvec, a.b, a.y, a.uvec);
 }
 inline void launch_bwd_inv(const SolveArgs& a, const MfLaunch& L) {
+    // few fronts with a real boundary: S workgroups per front share the boundary product (bwd_inv_split, mf_launch_plan.hpp)
+    const int S = a.bwd_cnt ? bwd_inv_split(L.count, L.max_k, L.max_m) : 1;
+    if (S > 1) {
+        hipLaunchKernelGGL(mf_bwd_inv_split, dim3(S, L.count), dim3(BIGI_THREADS), bwd_inv_lds(L.max_m, L.max_k), a.st, a.fr, L.first,
+                           a.front_idx, a.arena, a.dvec, a.y, a.x, a.bwd_g, (int)bwd_split_stride(L.max_k), a.bwd_cnt);
+        return;
+    }
     hipLaunchKernelGGL(mf_bwd_inv, dim3(L.count), dim3(BIGI_THREADS), bwd_inv_lds(L.max_m, L.max_k), a.st, a.fr, L.first,
                        a.front_idx, a.arena, a.dvec, a.y, a.x);
 }

@@ -53,11 +53,13 @@ struct MfSwitches {
                             // before the static gather maps; the reference of tests/test_gpu_gather_maps.py)
     int gather_ct;          // MGBHIP_GATHER_CT=8/16/32: destination columns per workgroup of every mf_big_gather launch on the
                             // static maps (default 0: big_gather_ct chooses per launch)
+    bool bwd_split;         // off with MGBHIP_BWD_SPLIT=0: one workgroup per front in every backward launch of the inverse-based
+                            // path (bwd_inv_split; the reference of tests/test_gpu_backward_launches.py)
     static MfSwitches from_env() {
         auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
         return {env_on("MGBHIP_NO_GEO"), env_on("MGBHIP_OLD_BIG"), !env_on("MGBHIP_NO_MERGE_GROUPS"), !env_on("MGBHIP_NO_PACKED_LEAVES"),
                 !env_on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0),
-                env_on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0)};
+                env_on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0), num("MGBHIP_BWD_SPLIT", 1) != 0};
     }
 };
 
@@ -260,6 +262,35 @@ inline int big_gather_ct(const MfLaunch& L, int forced) {
     int ct = 8;
     while (ct < 32 && (int64_t)L.count * ((L.max_m + 2 * ct - 1) / (2 * ct)) >= GATHER_MIN_WGS) ct *= 2;
     return ct;
+}
+
+// Workgroups per front of a backward launch on the inverse-based path (mf_bwd_inv_split, mf_big_inv.hpp): the boundary
+// product G[q] = sum_r A[r, q] x[r] of a front needs nothing of its own launch, so on levels of few fronts -- where one
+// workgroup per front leaves most of the 256 compute units idle -- its pivot columns are dealt out to S workgroups; the
+// last one to finish goes on with the block recurrence.  A pure function of the launch: as many workgroups as the device
+// has compute units for (BWD_SPLIT_CUS / count), at least BWD_SPLIT_COLS columns each (one 4-column group per wave of a
+// 1024-thread workgroup), BWD_SPLIT_MAX at most.  1 = one workgroup per front (mf_bwd_inv): also for launches whose
+// fronts have a thin boundary (m - k <= BWD_THIN_BOUNDARY: one thread per column, the root front's border row).
+constexpr int BWD_SPLIT_MAX = 16;
+constexpr int BWD_SPLIT_CUS = 256;
+constexpr int BWD_SPLIT_COLS = 64;
+constexpr int BWD_THIN_BOUNDARY = 8;
+inline int bwd_inv_split(int32_t count, int32_t max_k, int32_t max_m) {
+    if (count < 1 || max_m - max_k <= BWD_THIN_BOUNDARY) return 1;
+    return std::max(1, std::min({BWD_SPLIT_MAX, BWD_SPLIT_CUS / count, (max_k + BWD_SPLIT_COLS - 1) / BWD_SPLIT_COLS}));
+}
+// doubles of boundary-product scratch per front of a split launch
+inline int32_t bwd_split_stride(int32_t max_k) { return (max_k + 1) & ~1; }
+// What the split launches of a sweep need: per-front arrival counters (out[0]) and doubles of scratch (out[1]).  Launches
+// of a sweep run one after the other, so all of them share one allocation, sized by the largest.
+inline void bwd_split_scratch(const LevelLaunches& solves, int64_t out[2]) {
+    out[0] = out[1] = 0;
+    for (auto& lev : solves)
+        for (auto& L : lev) {
+            if (L.count == 0 || L.cls || !L.inv || bwd_inv_split(L.count, L.max_k, L.max_m) == 1) continue;
+            out[0] = std::max<int64_t>(out[0], L.count);
+            out[1] = std::max<int64_t>(out[1], (int64_t)L.count * bwd_split_stride(L.max_k));
+        }
 }
 
 // ---- static gather maps of mf_big_gather ---------------------------------------------------------------------------

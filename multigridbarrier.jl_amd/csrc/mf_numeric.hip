@@ -42,6 +42,8 @@ int32_t query_lds_cap() {          // largest front class of mf_factor_small; th
 bool query_inv_optin() {           // the single-workgroup solves of the inverse-based path at BIG_INV_MAX_M (148 960 B of the 160 KB)
     if (hipFuncSetAttribute((const void*)mf_fwd_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_inv_lds(BIG_INV_MAX_M)) == hipSuccess &&
         hipFuncSetAttribute((const void*)mf_bwd_inv, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)bwd_inv_lds(BIG_INV_MAX_M, BIG_INV_MAX_M)) == hipSuccess &&
+        hipFuncSetAttribute((const void*)mf_bwd_inv_split, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)bwd_inv_lds(BIG_INV_MAX_M, BIG_INV_MAX_M)) == hipSuccess)
         return true;
     (void)hipGetLastError();
@@ -199,6 +201,16 @@ void MfSolver::analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, 
             if (!L.cls) max_big = std::max(max_big, L.count);
         }
     d_dscr.alloc((size_t)max_big * 2 * NB * NB);
+    {   // split backward launches (bwd_inv_split): per-front boundary products and arrival counters, shared by all launches
+        int64_t need[2] = {0, 0};
+        if (sw.bwd_split) bwd_split_scratch(level_solves, need);
+        if (need[0] == 0) { d_bwd_g.release(); d_bwd_cnt.release(); }
+        else {
+            d_bwd_g.alloc((size_t)need[1]);
+            d_bwd_cnt.alloc((size_t)need[0]);
+            d_bwd_cnt.zero(st);
+        }
+    }
 
     std::vector<int64_t> ug_ptr, ug_src;
     build_gather_lists(plan, on_big_path, fd, ug_ptr, ug_src);

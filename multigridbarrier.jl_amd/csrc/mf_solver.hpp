@@ -43,6 +43,8 @@ struct SolveArgs {
     const double* b;                    // forward sweep: right-hand side
     double *y, *x, *uvec, *tbig, *tsol; // x: backward sweep only
     hipStream_t st;
+    double* bwd_g;                      // split backward launches (bwd_inv_split): boundary products, per front of a launch
+    uint32_t* bwd_cnt;                  // ... and arrival counters, zero between launches; nullptr: MGBHIP_BWD_SPLIT=0
 };
 
 class MfSolver {
@@ -120,7 +122,7 @@ class MfSolver {
     void upload_plan(hipStream_t st);     // analyze(): plan arrays and work buffers
     SolveArgs solve_args(const double* d_b, double* d_x, hipStream_t st) const {
         return {d_fronts.p, d_front_idx.p, d_children.p, d_rel.p, d_ug_ptr.p, d_ug_src.p, d_arena.p, d_dvec.p, d_b, d_y.p, d_x,
-                d_uvec.p, d_tbig.p, d_tsol.p, st};
+                d_uvec.p, d_tbig.p, d_tsol.p, st, d_bwd_g.p, d_bwd_cnt.n ? d_bwd_cnt.p : nullptr};
     }
     void forward_pass(const double* d_b_np1, hipStream_t st, StageTimers* timers);
     void backward_pass(double* d_x_np1, hipStream_t st, StageTimers* timers);
@@ -133,6 +135,8 @@ class MfSolver {
     DevBuf<double> d_arena, d_uvec, d_y, d_tbig, d_tsol, d_dscr, d_dvec;
     DevBuf<double> d_ifpack;              // packed lower triangle of the interface front (domain decomposition)
     DevBuf<int32_t> d_status;
+    DevBuf<double> d_bwd_g;               // boundary products of the split backward launches (bwd_split_scratch)
+    DevBuf<uint32_t> d_bwd_cnt;           // their arrival counters: zeroed by analyze(), reset by the last workgroup to arrive
     // condensed leaves
     bool condensed_ok = false;
     bool leaf_packed = false;            // the m <= 16 leaf fronts are stored as packed triangles (FrontDev::packed)
