@@ -408,6 +408,43 @@ int mgbhip_closest_evaluate(mgbhip_closest* cp, int32_t ncomp, const double* z /
                             double* grad /* M x ncomp x e, or NULL: values only */);
 int mgbhip_closest_destroy(mgbhip_closest* cp); /* NULL is a no-op */
 
+/* ---- quadrature: integrals and norms of element-space functions over the mesh ------------------------------------
+ * N elements of p nodes and dimension d in e >= d coordinates [(d, e) = (1, 1..3), (2, 2..3) or (3, 3); x: (p N) x e,
+ * element-major] and a rule of Q points per element, given by its reference weights wref [Q] and by the element basis
+ * at its points: phi [Q x p], dphi [Q x p x d, the derivatives in reference coordinates].  Nothing else tells the
+ * library the element family.  At point q of an element with nodes x_i and values z_i
+ *     x_q = sum_i phi[q][i] x_i,   J = sum_i x_i dphi[q][i]^T [e x d],   measure_q = wref[q] sqrt(det J^T J),
+ *     u_q = sum_i phi[q][i] z_i,   grad u = J (J^T J)^-1 sum_i dphi[q][i] z_i   [tangential when e > d].
+ * x, wref, phi and dphi are copied.  A handle belongs to the context it was created from and must be destroyed before it.
+ *  - points [N x Q x e] and weights [N x Q, the measures: they sum to the measure of the mesh].
+ *  - integrate: z [(p N) x ncol]; per column the sum over all points of measure_q F_q with F = u [VALUE], |u - g|^pexp
+ *    [LP], |grad u - G|^pexp [W1P, Euclidean norm in R^e] or |grad u|^pexp / pexp - f u [ENERGY; source: f as p N nodal
+ *    values].  minus: g [N x Q x ncol] or G [N x Q x ncol x e] at the points, or NULL for zero; pexp finite and > 0
+ *    [ignored by VALUE].  totals [ncol]; per_element [N x ncol] or NULL.  An element's value is the sum of its Q terms
+ *    in an order fixed by Q alone, the totals are compensated sums over the elements in a fixed order: results are
+ *    reproducible bit for bit, do not depend on per_element, and a column's do not depend on the other columns.
+ *  - max: per column the largest |u_q - g_q| [LP] or |grad u - G| [W1P] over all points, into maxima [ncol].
+ *  - plan [no handle, no device]: out16 = { threads, lanes per element S = min(Q, threads), elements per workgroup G,
+ *    columns per pass, 1 if phi / dphi are staged in LDS [0: read through L2], threads of the reduction over the
+ *    elements, element groups, workgroups, dynamic LDS bytes, bytes of the tables, 0... } for that shape.
+ *  - times: device milliseconds of the last integrate or max call, taken with events on the context's stream:
+ *    ms2 = { the element kernel, the reduction over the elements }; invalid before the first call.                  */
+enum { MGBHIP_QUAD_VALUE = 0, MGBHIP_QUAD_LP = 1, MGBHIP_QUAD_W1P = 2, MGBHIP_QUAD_ENERGY = 3 };
+typedef struct mgbhip_quadrature mgbhip_quadrature;
+int mgbhip_quadrature_create(mgbhip_ctx* ctx, int32_t d, int32_t e, int32_t p, int64_t N, const double* x, int32_t Q,
+                             const double* wref, const double* phi, const double* dphi, mgbhip_quadrature** out);
+int mgbhip_quadrature_points(mgbhip_quadrature* quad, double* points /* N x Q x e */);
+int mgbhip_quadrature_weights(mgbhip_quadrature* quad, double* weights /* N x Q */);
+int mgbhip_quadrature_integrate(mgbhip_quadrature* quad, int32_t kind, double pexp, int32_t ncol,
+                                const double* z /* (p*N) x ncol */, const double* minus /* or NULL */,
+                                const double* source /* p*N: ENERGY; else NULL */,
+                                double* per_element /* N x ncol, or NULL */, double* totals /* ncol */);
+int mgbhip_quadrature_max(mgbhip_quadrature* quad, int32_t kind, int32_t ncol, const double* z /* (p*N) x ncol */,
+                          const double* minus /* or NULL */, double* maxima /* ncol */);
+int mgbhip_quadrature_plan(int32_t d, int32_t e, int32_t p, int32_t Q, int64_t N, int32_t* out16);
+int mgbhip_quadrature_times(const mgbhip_quadrature* quad, double* ms2);
+int mgbhip_quadrature_destroy(mgbhip_quadrature* quad); /* NULL is a no-op */
+
 /* ---- level sets: level curves (d = 2) and isosurfaces (d = 3) of an element-space function ------------------------
  * Every element is sampled on a uniform reference lattice of refine + 1 points per axis (Q_k; axis 0 fastest) or on
  * the barycentric lattice of the refine-fold uniform subdivision (P1 / P2) with its own basis; a lattice square is

@@ -15,6 +15,7 @@
 #include "interpolate.hpp"
 #include "polyline.hpp"
 #include "problem.hpp"
+#include "quadrature.hpp"
 #include "raycast.hpp"
 #include "stream.hpp"
 #include "surface.hpp"
@@ -62,6 +63,7 @@ struct Handle {
 };
 struct mgbhip_locator : Handle<Locator> {};            // a point locator (interpolate.hpp)
 struct mgbhip_closest : Handle<Closest> {};            // a closest-point locator (closest.hpp)
+struct mgbhip_quadrature : Handle<Quadrature> {};      // a quadrature rule on a mesh (quadrature.hpp)
 struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
 struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
 struct mgbhip_weld : Handle<Weld> {};                  // the index of a welded soup (weld.hpp)
@@ -978,6 +980,110 @@ int mgbhip_closest_evaluate(mgbhip_closest* cp, int32_t ncomp, const double* z, 
 }
 
 int mgbhip_closest_destroy(mgbhip_closest* cp) { return destroy_handle(cp); }
+
+static_assert(MGBHIP_QUAD_VALUE == QUAD_VALUE && MGBHIP_QUAD_LP == QUAD_LP && MGBHIP_QUAD_W1P == QUAD_W1P &&
+              MGBHIP_QUAD_ENERGY == QUAD_ENERGY, "mgbhip.h mirrors QuadKind");
+
+static bool quad_dims_ok(int32_t d, int32_t e) { return d >= 1 && d <= 3 && e >= d && e <= 3; }
+
+int mgbhip_quadrature_create(mgbhip_ctx* ctx, int32_t d, int32_t e, int32_t p, int64_t N, const double* x, int32_t Q,
+                             const double* wref, const double* phi, const double* dphi, mgbhip_quadrature** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(quad_dims_ok(d, e), "quadrature: (d, e) must be (1, 1..3), (2, 2..3) or (3, 3)");
+    MGB_REQUIRE(N > 0, "quadrature: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1 && Q >= 1, "quadrature: bad sizes");
+    MGB_REQUIRE(x != nullptr && wref != nullptr && phi != nullptr && dphi != nullptr, "null argument");
+    MGB_REQUIRE((int64_t)(1 + d) * Q * p < (int64_t)INT32_MAX && (int64_t)p * N * e < (int64_t)INT32_MAX &&
+                    N * Q * e < (int64_t)INT32_MAX,
+                "quadrature: sizes exceed 32-bit indexing");
+    MGB_REQUIRE(quad_decide(d, e, p, Q, N).G >= 1, "quadrature: an element's nodes do not fit in LDS");
+    for (int64_t i = 0; i < (int64_t)p * N * e; ++i) MGB_REQUIRE(std::isfinite(x[i]), "quadrature: the mesh has non-finite node coordinates");
+    for (int32_t q = 0; q < Q; ++q) MGB_REQUIRE(std::isfinite(wref[q]), "quadrature: the rule must be finite");
+    for (int64_t i = 0; i < (int64_t)Q * p; ++i) MGB_REQUIRE(std::isfinite(phi[i]), "quadrature: the basis tables must be finite");
+    for (int64_t i = 0; i < (int64_t)Q * p * d; ++i) MGB_REQUIRE(std::isfinite(dphi[i]), "quadrature: the basis tables must be finite");
+    create_handle(ctx, out, [&](Quadrature& Qd) { quadrature_build(Qd, d, e, p, N, x, Q, wref, phi, dphi, ctx->stream); });
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_quadrature_points(mgbhip_quadrature* h, double* points) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null quadrature");
+    MGB_REQUIRE(points != nullptr, "null argument");
+    quadrature_geometry(h->obj, points, nullptr, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_quadrature_weights(mgbhip_quadrature* h, double* weights) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null quadrature");
+    MGB_REQUIRE(weights != nullptr, "null argument");
+    quadrature_geometry(h->obj, nullptr, weights, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+// the size checks integrate and max share
+static void quad_check_call(const Quadrature& Qd, int32_t kind, int32_t ncol, const double* z, const double* minus) {
+    MGB_REQUIRE(kind >= QUAD_VALUE && kind <= QUAD_ENERGY, "quadrature: bad kind");
+    MGB_REQUIRE(ncol >= 1, "quadrature: bad sizes");
+    MGB_REQUIRE(z != nullptr, "null argument");
+    MGB_REQUIRE(minus == nullptr || kind == QUAD_LP || kind == QUAD_W1P, "quadrature: minus goes with the lp and w1p kinds only");
+    MGB_REQUIRE((int64_t)Qd.p * Qd.N * ncol < (int64_t)INT32_MAX && Qd.N * Qd.Q * ncol * (kind == QUAD_W1P ? Qd.e : 1) < (int64_t)INT32_MAX,
+                "quadrature: sizes exceed 32-bit indexing");
+}
+
+int mgbhip_quadrature_integrate(mgbhip_quadrature* h, int32_t kind, double pexp, int32_t ncol, const double* z, const double* minus,
+                                const double* source, double* per_element, double* totals) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null quadrature");
+    quad_check_call(h->obj, kind, ncol, z, minus);
+    MGB_REQUIRE(totals != nullptr, "null argument");
+    MGB_REQUIRE(kind == QUAD_VALUE || (std::isfinite(pexp) && pexp > 0.0), "quadrature: p must be finite and > 0");
+    MGB_REQUIRE((kind == QUAD_ENERGY) == (source != nullptr), "quadrature: source goes with the energy kind, and only with it");
+    quadrature_integrate(h->obj, kind, kind == QUAD_VALUE ? 1.0 : pexp, false, ncol, z, minus, source, per_element, totals,
+                         h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_quadrature_max(mgbhip_quadrature* h, int32_t kind, int32_t ncol, const double* z, const double* minus, double* maxima) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null quadrature");
+    quad_check_call(h->obj, kind, ncol, z, minus);
+    MGB_REQUIRE(kind == QUAD_LP || kind == QUAD_W1P, "quadrature: the maximum is defined for the lp and w1p kinds");
+    MGB_REQUIRE(maxima != nullptr, "null argument");
+    quadrature_integrate(h->obj, kind, 1.0, true, ncol, z, minus, nullptr, nullptr, maxima, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_quadrature_plan(int32_t d, int32_t e, int32_t p, int32_t Q, int64_t N, int32_t* out) {
+    MGB_API_BEGIN
+    MGB_REQUIRE(out != nullptr, "null argument");
+    MGB_REQUIRE(quad_dims_ok(d, e) && p >= 1 && Q >= 1 && N >= 1, "quadrature: bad sizes");
+    const QuadPlan plan = quad_decide(d, e, p, Q, N);
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = plan.threads; out[1] = plan.S; out[2] = plan.G; out[3] = plan.chunk; out[4] = plan.tables_lds;
+    out[5] = plan.reduce_threads; out[6] = (int32_t)plan.groups; out[7] = (int32_t)plan.grid; out[8] = (int32_t)plan.lds;
+    out[9] = (int32_t)std::min<size_t>(quad_lds_tables(d, p, Q), (size_t)INT32_MAX);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_quadrature_times(const mgbhip_quadrature* h, double* ms) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null quadrature");
+    MGB_REQUIRE(ms != nullptr, "null argument");
+    quadrature_times(h->obj, ms);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_quadrature_destroy(mgbhip_quadrature* h) { return destroy_handle(h); }
 
 int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
                                    const double* x, const double* table, int32_t nfield, const double* fields,

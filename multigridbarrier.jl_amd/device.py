@@ -118,6 +118,8 @@ EXPORTS = [
     "mgbhip_prolong_add", "mgbhip_level_plan", "mgbhip_elem_plan", "mgbhip_trial_values", "mgbhip_solver_launches", "mgbhip_interpolate", "mgbhip_interpolate_grad",
     "mgbhip_locator_create", "mgbhip_locator_elements", "mgbhip_locator_evaluate", "mgbhip_locator_destroy",
     "mgbhip_closest_create", "mgbhip_closest_fetch", "mgbhip_closest_evaluate", "mgbhip_closest_destroy",
+    "mgbhip_quadrature_create", "mgbhip_quadrature_points", "mgbhip_quadrature_weights", "mgbhip_quadrature_integrate",
+    "mgbhip_quadrature_max", "mgbhip_quadrature_plan", "mgbhip_quadrature_times", "mgbhip_quadrature_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
     "mgbhip_tessellate_create", "mgbhip_tessellate_fetch", "mgbhip_tessellate_destroy",
     "mgbhip_weld_create", "mgbhip_weld_fetch", "mgbhip_weld_rounds", "mgbhip_weld_destroy",
@@ -219,6 +221,15 @@ def load_library():
     lib.mgbhip_closest_fetch.argtypes = [vp, _ip, _dp, _dp, _dp, _ip]
     lib.mgbhip_closest_evaluate.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     lib.mgbhip_closest_destroy.argtypes = [vp]
+    lib.mgbhip_quadrature_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp,
+                                             C.POINTER(vp)]
+    lib.mgbhip_quadrature_points.argtypes = [vp, _dp]
+    lib.mgbhip_quadrature_weights.argtypes = [vp, _dp]
+    lib.mgbhip_quadrature_integrate.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp, _dp, _dp]
+    lib.mgbhip_quadrature_max.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp]
+    lib.mgbhip_quadrature_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _ip]
+    lib.mgbhip_quadrature_times.argtypes = [vp, _dp]
+    lib.mgbhip_quadrature_destroy.argtypes = [vp]
     lib.mgbhip_contour_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32,
                                           _dp, C.c_int32, _dp, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.mgbhip_contour_create_embedded.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp,
