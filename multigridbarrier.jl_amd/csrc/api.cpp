@@ -281,7 +281,7 @@ int mgbhip_elem_plan(mgbhip_problem* P, int32_t mode, int32_t* out) {
     MGB_API_BEGIN
     MGB_REQUIRE(P != nullptr && out != nullptr, "null argument");
     MGB_REQUIRE(mode >= MODE_F0 && mode <= MODE_F01, "elem_plan: bad mode");
-    const ElemParams E = P->base_params(-1, nullptr, nullptr, nullptr);      // level -1: nothing is launched or cached
+    const ElemParams E = P->elem_params(nullptr);      // no evaluation point: nothing is launched or cached
     const ElemPlan plan = elem_plan_of(E, mode, false);
     for (int i = 0; i < 16; ++i) out[i] = 0;
     out[0] = plan.kind; out[1] = plan.NY; out[2] = plan.P; out[3] = plan.threads; out[4] = plan.G; out[5] = plan.EPB;
@@ -374,9 +374,7 @@ int mgbhip_set_hessian(mgbhip_problem* P, int32_t level, const double* values) {
     MGB_REQUIRE(L.Hval.n >= (size_t)L.nnz, "this level keeps no CSR value array");
     L.Hval.upload(values, (size_t)L.nnz, P->stream());
     MGB_HIP_CHECK(hipStreamSynchronize(P->stream()));
-    L.have_H = true;
-    L.H_in_slab = false;
-    L.factored = false;
+    L.H.set_from_outside();
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -442,7 +440,7 @@ int mgbhip_newton_direction(mgbhip_problem* P, int32_t level, const double* s, c
     stage_inputs(P, level, s, c, z0);
     P->eval_f1(level, P->d_x.p, P->d_z0.p, P->d_c.p, P->d_g.p);
     P->eval_f2(level, P->d_x.p, P->d_z0.p, P->d_c.p, false, P->d_g.p);      // exactly the Newton loop's sequence
-    if (condensed) *condensed = P->levels[level].H_condensed ? 1 : 0;
+    if (condensed) *condensed = P->levels[level].H.condensed() ? 1 : 0;
     P->factor(level, P->d_g.p);
     P->trisolve_carried(level, P->d_nv.p);
     const int status = P->levels[level].solver.status(st);
@@ -682,7 +680,8 @@ static int node_map(mgbhip_problem* P, const double* z, double* F, double* Dz, i
     MGB_REQUIRE(P && z && F, "null argument");
     hipStream_t st = P->stream();
     P->d_z0.upload(z, (size_t)P->nu * P->n, st);
-    ElemParams E = P->base_params(-1, nullptr, P->d_z0.p, nullptr);
+    ElemParams E = P->elem_params(nullptr);
+    E.z0 = P->d_z0.p;
     if (Dz) {
         P->d_nodeDz.ensure((size_t)P->n * P->nD);
         E.out_Dz = P->d_nodeDz.p;

@@ -86,7 +86,9 @@ struct NewtonCtx {
 // F0, F1 and the gradient statistics are launched back to back and read with ONE
 // synchronisation (value, sum of squares, non-finite count, and the step kernel's "moved" flag):
 // evaluating F1 at a point F0 rejects only produces NaN/Inf that nobody reads.
-bool trial_values(NewtonCtx& C, double& ynext, double& gnorm_next, int32_t* moved = nullptr, const double* step = nullptr) {
+// restrict_fused_out (optional): whether restriction, |g|^2 partials and the step ran as one launch
+bool trial_values(NewtonCtx& C, double& ynext, double& gnorm_next, int32_t* moved = nullptr, const double* step = nullptr,
+                  bool* restrict_fused_out = nullptr) {
     mgbhip_problem* P = C.P;
     hipStream_t st = P->stream();
     // step != nullptr: the trial point x - (*step) n has not been formed yet.  On a selection level the element kernel forms it
@@ -97,27 +99,21 @@ bool trial_values(NewtonCtx& C, double& ynext, double& gnorm_next, int32_t* move
         ++P->step_stamp;
         if (!onfly) launch_step(P->d_x.p, P->d_nv.p, *step, P->d_xn.p, C.m, P->d_flag.p, P->step_stamp, st);
         P->touch();
-        if (onfly) { P->trial_x = P->d_x.p; P->trial_dir = P->d_nv.p; P->trial_alpha = *step; }
     }
     // the element kernel leaves its workgroup partials of f0; their sum, |g|^2, the non-finite count and the step kernel's
     // "moved" stamp are finished by ONE launch that also stores them in the pinned block (no reduce / copy launches)
     const bool fused = !P->dense;
     static const bool fuse_restrict = !env_on("MGBHIP_NO_FUSED_RESTRICT");
-    P->trial_fuse = mgbhip_problem::TrialFuse();
-    if (fused && fuse_restrict) {           // restriction + |g|^2 partials (+ the deferred step) in one launch where the level allows it
-        P->trial_fuse.want = true;
-        if (onfly) {
-            P->trial_fuse.x = P->d_x.p; P->trial_fuse.n = P->d_nv.p; P->trial_fuse.s = *step; P->trial_fuse.xn = P->d_xn.p;
-            P->trial_fuse.moved = P->d_flag.p; P->trial_fuse.stamp = P->step_stamp;
-        }
-    }
-    P->eval_f01_launch(C.level, P->d_xn.p, C.d_zJ, C.d_c, P->d_gn.p, P->sharded() ? P->d_gnpart.p : nullptr, fused);
-    const bool restrict_fused = P->trial_fuse.done;
-    P->trial_fuse.want = false;
+    TrialRestrict fuse;                     // restriction + |g|^2 partials (+ the deferred step) in one launch where the level allows it
+    TrialPoint point{};                     // the not yet written d_xn = x - (*step) n
     if (onfly) {
-        P->trial_x = nullptr; P->trial_dir = nullptr;
-        if (!restrict_fused) launch_step(P->d_x.p, P->d_nv.p, *step, P->d_xn.p, C.m, P->d_flag.p, P->step_stamp, st);
+        point = TrialPoint{P->d_x.p, P->d_nv.p, *step};
+        fuse = TrialRestrict{P->d_x.p, P->d_nv.p, *step, P->d_xn.p, P->d_flag.p, P->step_stamp};
     }
+    const bool restrict_fused = P->eval_f01_launch(C.level, P->d_xn.p, C.d_zJ, C.d_c, P->d_gn.p, P->sharded() ? P->d_gnpart.p : nullptr, fused,
+                                                   onfly ? &point : nullptr, (fused && fuse_restrict) ? &fuse : nullptr);
+    if (restrict_fused_out) *restrict_fused_out = restrict_fused;
+    if (onfly && !restrict_fused) launch_step(P->d_x.p, P->d_nv.p, *step, P->d_xn.p, C.m, P->d_flag.p, P->step_stamp, st);
     const double seq = P->next_seq();
     launch_trial_finish(P->d_gn.p, C.m, P->d_scratch.p, fused ? P->d_partials.p : nullptr, elem_grid(P->p, P->N), P->d_scal.p,
                         P->d_flag.p, P->pin.dev, st, P->own_mask(C.level), seq, restrict_fused);
@@ -265,7 +261,7 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
             DBG("newton[lev %d] k=%d: direction rejected (status %d, lambda^2=%.3e): refactoring with the substitution kernels\n",
                 C.level, k, fstatus, P->pin.d[4]);
             L.solver.robust = true;
-            L.factored = false;
+            L.H.drop_factors();
         }
         if (fstatus != MGBHIP_OK && P->lu_fallback(C.level, P->d_g.p, P->d_nv.p)) {
             // An exactly zero / non-finite pivot ended the un-pivoted LDL' (twice: inverse-based and substitution kernels).
@@ -371,7 +367,8 @@ double c_dot_Dz(mgbhip_problem* P, const double* d_c) {
     // sum_j dot(w .* c[:, j], (D_j z))  (src/mgb.jl:135-136, :165-166) with the UNSCALED cost grid
     // c (not t*c): the linear part of f0 at s = 0; invn = 0 switches the barrier term off
     hipStream_t st = P->stream();
-    ElemParams E = P->base_params(-1, nullptr, P->d_z.p, d_c);
+    ElemParams E = P->elem_params(d_c);
+    E.z0 = P->d_z.p;
     E.invn = 0.0;
     E.bw = nullptr;
     launch_elem(E, MODE_F0, st);
@@ -403,9 +400,10 @@ void trial_values_run(mgbhip_problem* P, int level, double step, double* y, int3
     NewtonCtx C{P, level, P->d_z0.p, P->d_c.p, P->levels[level].m};
     double yn = 0.0, gn = 0.0;
     const bool onfly = P->can_fuse_step(level);
-    *finite = trial_values(C, yn, gn, moved, &step) ? 1 : 0;
+    bool restrict_fused = false;
+    *finite = trial_values(C, yn, gn, moved, &step, &restrict_fused) ? 1 : 0;
     *y = yn;
-    *path = (onfly ? 1 : 0) | (P->trial_fuse.done ? 2 : 0);
+    *path = (onfly ? 1 : 0) | (restrict_fused ? 2 : 0);
 }
 
 int core_run(mgbhip_problem* P, double* z, const double* c, const mgbhip_options* optp, mgbhip_core_result* res) {
@@ -546,7 +544,7 @@ int matched_t_run(mgbhip_problem* P, const double* z, const double* c, double t_
         P->trisolve_carried(lev, P->d_tmp.p);
         int bad = P->levels[lev].solver.status(st) != MGBHIP_OK;
         MGB_HIP_CHECK(hipMemcpyAsync(P->d_nv.p, P->d_tmp.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, st));
-        P->levels[lev].factored = false;
+        P->levels[lev].H.drop_factors();
         P->factor(lev, P->d_gnpart.p);
         P->trisolve_carried(lev, P->d_tmp.p);
         bad |= P->levels[lev].solver.status(st) != MGBHIP_OK;

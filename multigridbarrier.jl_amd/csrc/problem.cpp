@@ -412,7 +412,7 @@ void mgbhip_problem::ensure_plan(int level) {
             if (L.direct) {          // room for the shared sums and the border column behind the slab
                 std::lock_guard<std::mutex> lock(shared_mutex);     // several selection levels may be planned at once (prepare_all)
                 d_hel.ensure((size_t)(hel_cap + L.nshared + m + 1));
-                hel_level = -1;
+                hel_owner.dropped();
             }
         }
     }
@@ -482,7 +482,7 @@ void mgbhip_problem::ensure_plan(int level) {
 // device-resident primitives
 // ---------------------------------------------------------------------------------------------
 
-ElemParams mgbhip_problem::base_params(int level, const double* d_s, const double* d_zz, const double* d_cc) const {
+ElemParams mgbhip_problem::elem_params(const double* d_cc) const {
     ElemParams E;
     std::memset(&E, 0, sizeof(E));
     E.p = p; E.nu = nu; E.nD = nD; E.nstage = nstage; E.N = N; E.n = n;
@@ -497,33 +497,6 @@ ElemParams mgbhip_problem::base_params(int level, const double* d_s, const doubl
     for (int k = 0; k < MGBHIP_MAX_ND; ++k) { E.D_state[k] = D_state[k]; E.D_op[k] = D_op[k]; E.D_stage[k] = D_stage[k]; }
     E.w = store->w.p;
     E.c = d_cc;
-    // z0 + R*s is formed once per evaluation point by a row-parallel kernel (cached on the
-    // (level, s, z) triple by the callers below); the element kernels read the result
-    E.z0 = d_zz;
-    if (level >= 0 && d_s != nullptr) {
-        const Level& L = levels[level];
-        if (zf_stamp == zstamp && zf_level == level && zf_s == d_s && zf_z == d_zz) {
-            // same evaluation point as the previous call: d_zfull is still valid
-        } else if (L.R_unit && !dense) {
-            // (the dense spectral path, launch_dense_eval, reads E.z0 only: it never takes this branch)
-            // selection level: the element kernel gathers s itself and leaves z0 + R s in d_zfull for the next evaluation
-            // at this point (the Hessian at an accepted line-search trial reads it back instead of chaining two gathers)
-            E.zsel = L.Rsel.p;
-            E.zs = d_s;
-            if (trial_x) { E.zs = trial_x; E.zx = trial_dir; E.zalpha = trial_alpha; }      // d_s (the trial vector) is written behind this launch
-            E.zout = d_zfull.p;
-            zf_stamp = zstamp; zf_level = level; zf_s = d_s; zf_z = d_zz;
-            goto prolonged;
-        } else if (L.R_long) {      // dense prolongation rows: wave per row
-            MGB_HIP_CHECK(hipMemcpyAsync(d_zfull.p, d_zz, sizeof(double) * (size_t)L.rows, hipMemcpyDeviceToDevice, stream()));
-            launch_csr_matvec(L.rows, L.Rptr.p, L.Rcol.p, L.Rval.p, d_s, d_zfull.p, true, true, stream());
-        } else {
-            launch_prolong(L.rows, L.Rptr.p, L.Rcol.p, L.Rval.p, d_s, d_zz, d_zfull.p, stream());
-        }
-        zf_stamp = zstamp; zf_level = level; zf_s = d_s; zf_z = d_zz;
-        E.z0 = d_zfull.p;
-    }
-prolonged:
     E.bw = has_bw ? bw.p : nullptr;
     E.invn = 1.0 / (double)n;
     E.cone = cone;
@@ -537,11 +510,54 @@ prolonged:
     return E;
 }
 
+// z0 + R*s is formed once per evaluation point (cached on the (level, s, z) triple and the touch() stamp); the element
+// kernels read the result
+bool mgbhip_problem::bind_point(ElemParams& E, int level, const double* d_s, const double* d_zz, const TrialPoint* trial) {
+    const Level& L = levels[level];
+    const PointKey here{zstamp, level, d_s, d_zz};
+    MGB_REQUIRE(!trial || (L.R_unit && !dense && !(zf == here)), "a trial point is given only after touch(), on a selection level");
+    E.z0 = d_zz;
+    if (d_s == nullptr) return false;
+    if (zf == here) {
+        // same evaluation point as the previous call: d_zfull is still valid
+    } else if (L.R_unit && !dense) {
+        // (the dense spectral path, launch_dense_eval, reads E.z0 only: it never takes this branch)
+        // selection level: the element kernel gathers s itself and leaves z0 + R s in d_zfull for the next evaluation
+        // at this point (the Hessian at an accepted line-search trial reads it back instead of chaining two gathers)
+        E.zsel = L.Rsel.p;
+        E.zs = d_s;
+        if (trial) { E.zs = trial->x; E.zx = trial->dir; E.zalpha = trial->alpha; }      // d_s (the trial vector) is written behind this launch
+        E.zout = d_zfull.p;
+        return true;
+    } else if (L.R_long) {      // dense prolongation rows: wave per row
+        MGB_HIP_CHECK(hipMemcpyAsync(d_zfull.p, d_zz, sizeof(double) * (size_t)L.rows, hipMemcpyDeviceToDevice, stream()));
+        launch_csr_matvec(L.rows, L.Rptr.p, L.Rcol.p, L.Rval.p, d_s, d_zfull.p, true, true, stream());
+    } else {
+        launch_prolong(L.rows, L.Rptr.p, L.Rcol.p, L.Rval.p, d_s, d_zz, d_zfull.p, stream());
+    }
+    zf = here;
+    E.z0 = d_zfull.p;
+    return false;
+}
+
+void mgbhip_problem::launch_elem_at(ElemParams& E, int mode, int level, const double* d_s, const double* d_zz, const TrialPoint* trial) {
+    const bool writes_zfull = bind_point(E, level, d_s, d_zz, trial);
+    launch_elem(E, mode, stream());
+    if (writes_zfull) zf = PointKey{zstamp, level, d_s, d_zz};
+}
+
+const char* mgbhip_problem::stage_name(Stage s, int level) const {
+    static const char* const names[][2] = {{"f0", "f0_coarse"}, {"f1", "f1_coarse"}, {"f01", "f01_coarse"}, {"f2", "f2_coarse"},
+                                           {"assemble", "assemble_coarse"}};
+    // fine-level launches are timed apart: they are the ones the HBM roofline is quoted on
+    return names[s][level + 1 == (int)levels.size() ? 0 : 1];
+}
+
 void mgbhip_problem::eval_f0_launch(int level, const double* d_s, const double* d_zz, const double* d_cc) {
     hipStream_t st = stream();
-    StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "f0" : "f0_coarse");
-    ElemParams E = base_params(level, d_s, d_zz, d_cc);
-    launch_elem(E, MODE_F0, st);
+    StageScope sc(ctx->timers, stage_name(STAGE_F0, level));
+    ElemParams E = elem_params(d_cc);
+    launch_elem_at(E, MODE_F0, level, d_s, d_zz);
     launch_reduce_partials(d_partials.p, elem_grid(p, N), d_scal.p, st);
     cnt.f0++;
 }
@@ -588,56 +604,54 @@ void mgbhip_problem::reduce_interface(int level, double* d_g, double* d_part) {
     launch_index_scatter(L.iface_buf.p, L.d_iface.p, ni, d_g, st);
 }
 
-void mgbhip_problem::eval_f1(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout, double* d_part) {
+bool mgbhip_problem::restrict_ret(int level, double* d_gout, const TrialRestrict* fuse) {
     hipStream_t st = stream();
     const Level& L = levels[level];
-    {
-        StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "f1" : "f1_coarse");
-        ElemParams E = base_params(level, d_s, d_zz, d_cc);
-        launch_elem(E, MODE_F1, st);
+    StageScope sc(ctx->timers, "restrict");
+    if (fuse && L.T_chunks == 0 && !L.T_long && !sharded()) {
+        // line-search trial: restriction, |g|^2 partial sums and the step kernel's work in one launch (kernels.hip)
+        launch_restrict_trial(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, d_scratch.p, fuse->x, fuse->n, fuse->s,
+                              fuse->xn, fuse->moved, fuse->stamp, st);
+        return true;
     }
+    if (L.T_chunks > 0)
+        launch_csr_matvec_chunked(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, d_tchunk.p, L.T_chunks, st);
+    else
+        launch_csr_matvec(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, false, L.T_long, st);
+    return false;
+}
+
+void mgbhip_problem::eval_f1(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout, double* d_part) {
     {
-        StageScope sc(ctx->timers, "restrict");
-        if (L.T_chunks > 0)
-            launch_csr_matvec_chunked(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, d_tchunk.p, L.T_chunks, st);
-        else
-            launch_csr_matvec(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, false, L.T_long, st);
+        StageScope sc(ctx->timers, stage_name(STAGE_F1, level));
+        ElemParams E = elem_params(d_cc);
+        launch_elem_at(E, MODE_F1, level, d_s, d_zz);
     }
-    if (L.sharded) reduce_interface(level, d_gout, d_part);
+    restrict_ret(level, d_gout);
+    if (levels[level].sharded) reduce_interface(level, d_gout, d_part);
     cnt.f1++;
 }
 
-void mgbhip_problem::eval_f01_launch(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout,
-                                     double* d_part, bool defer_f0_sum) {
+bool mgbhip_problem::eval_f01_launch(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout,
+                                     double* d_part, bool defer_f0_sum, const TrialPoint* trial, const TrialRestrict* fuse) {
+    MGB_REQUIRE(!trial || can_fuse_step(level), "a trial point is given only on a level whose element kernel forms it on the fly");
     if (dense) {                    // the dense (spectral) path keeps its separate GEMV pipelines
         eval_f0_launch(level, d_s, d_zz, d_cc);
         eval_f1(level, d_s, d_zz, d_cc, d_gout, d_part);
-        return;
+        return false;
     }
     hipStream_t st = stream();
-    const Level& L = levels[level];
     {
-        StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "f01" : "f01_coarse");
-        ElemParams E = base_params(level, d_s, d_zz, d_cc);
-        launch_elem(E, MODE_F01, st);
+        StageScope sc(ctx->timers, stage_name(STAGE_F01, level));
+        ElemParams E = elem_params(d_cc);
+        launch_elem_at(E, MODE_F01, level, d_s, d_zz, trial);
         if (!defer_f0_sum) launch_reduce_partials(d_partials.p, elem_grid(p, N), d_scal.p, st);
     }
-    {
-        StageScope sc(ctx->timers, "restrict");
-        trial_fuse.done = false;
-        if (trial_fuse.want && L.T_chunks == 0 && !L.T_long && !sharded()) {
-            // line-search trial: restriction, |g|^2 partial sums and the step kernel's work in one launch (kernels.hip)
-            launch_restrict_trial(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, d_scratch.p, trial_fuse.x, trial_fuse.n, trial_fuse.s,
-                                  trial_fuse.xn, trial_fuse.moved, trial_fuse.stamp, st);
-            trial_fuse.done = true;
-        } else if (L.T_chunks > 0)
-            launch_csr_matvec_chunked(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, d_tchunk.p, L.T_chunks, st);
-        else
-            launch_csr_matvec(L.m, L.Tptr.p, L.Tcol.p, L.Tval.p, d_ret.p, d_gout, false, L.T_long, st);
-    }
-    if (L.sharded) reduce_interface(level, d_gout, d_part);
+    const bool fused = restrict_ret(level, d_gout, fuse);
+    if (levels[level].sharded) reduce_interface(level, d_gout, d_part);
     cnt.f0++;
     cnt.f1++;
+    return fused;
 }
 
 bool mgbhip_problem::try_enable_condensed(int level) {
@@ -673,8 +687,9 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
         // Newton loop on a level with condensed leaves: one kernel evaluates the element blocks and eliminates the
         // element-local unknowns; nothing else is assembled (the other fronts receive every contribution through the
         // leaves' update blocks)
-        StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "f2" : "f2_coarse");
-        ElemParams E = base_params(level, d_s, d_zz, d_cc);
+        StageScope sc(ctx->timers, stage_name(STAGE_F2, level));
+        ElemParams E = elem_params(d_cc);
+        const bool writes_zfull = bind_point(E, level, d_s, d_zz);
         E.leaf_desc = L.solver.leaf_desc();
         E.leaf_arena = L.solver.arena();
         E.leaf_g = rhs;
@@ -684,30 +699,24 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
         if (!L.solver.leaf_flag_zero()) MGB_HIP_CHECK(hipMemsetAsync(E.leaf_status, 0, sizeof(int32_t), st));
         L.solver.leaf_flag_used();
         if (launch_elem_f2_condense(E, st)) {
-            L.have_H = true;
-            L.H_in_slab = true;
-            L.H_condensed = true;
-            L.condensed_rhs = rhs;
-            hel_level = level;
-            L.factored = false;
+            if (writes_zfull) zf = PointKey{zstamp, level, d_s, d_zz};
+            L.H.written_condensed(hel_owner, level, rhs);
             cnt.f2++;
             return;
         }
-        zf_stamp = -1;              // nothing ran: base_params may have promised d_zfull to a kernel that was not launched
+        // the condensing kernel does not apply to these parameters: nothing ran, the assembled path below evaluates
     }
-    L.H_condensed = false;
     L.proj_kernel = MGBHIP_PROJ_NONE;
     {
-        // fine-level launches are timed apart: they are the ones the HBM roofline is quoted on
-        StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "f2" : "f2_coarse");
-        ElemParams E = base_params(level, d_s, d_zz, d_cc);
+        StageScope sc(ctx->timers, stage_name(STAGE_F2, level));
+        ElemParams E = elem_params(d_cc);
         E_ymask = E.ymask;
         E.diag_mask = (L.selection && !dense) ? diag_mask_sel : 0;
         hel_layout(nu, N, p, E.diag_mask, E.blk_off);
-        launch_elem(E, MODE_F2, st);
+        launch_elem_at(E, MODE_F2, level, d_s, d_zz);
     }
     {
-        StageScope sc(ctx->timers, level + 1 == (int)levels.size() ? "assemble" : "assemble_coarse");
+        StageScope sc(ctx->timers, stage_name(STAGE_ASSEMBLE, level));
         if (dense) {
             // rows of y that enter the barrier form a contiguous range in every supported D
             // layout; rows outside it have zero weights and are skipped in the product
@@ -757,10 +766,8 @@ void mgbhip_problem::eval_f2(int level, const double* d_s, const double* d_zz, c
             }
         }
     }
-    L.have_H = true;
-    L.H_in_slab = L.selection && L.direct && !materialize && !dense;
-    hel_level = L.H_in_slab ? level : -1;         // any f2 overwrites the slab
-    L.factored = false;
+    if (L.selection && L.direct && !materialize && !dense) L.H.written_to_slab(hel_owner, level);
+    else L.H.written_to_csr(hel_owner);           // any f2 overwrites the slab
     cnt.f2++;
 }
 
@@ -900,41 +907,31 @@ void mgbhip_problem::ensure_direct(int level) {
 
 void mgbhip_problem::factor(int level, const double* rhs) {
     Level& L = levels[level];
-    MGB_REQUIRE(L.have_H, "solve requested before any Hessian was assembled at this level");
+    const FactorPlan plan = L.H.about_to_factor(hel_owner, level, rhs);      // throws when this H cannot be factored this way
     hipStream_t st = stream();
     ensure_analysis(level);
-    if (L.H_in_slab) {
+    if (plan.slab()) {
         // H was not materialised (eval_f2 with materialize = false): the values are the slab + shared sums in d_hel
-        MGB_REQUIRE(hel_level == level, "the element blocks of this level's Hessian were overwritten: evaluate f2 again");
-        MGB_REQUIRE(rhs != nullptr, "a Hessian kept in the slab is factored together with its right-hand side");
         ensure_direct(level);
-        MGB_REQUIRE(!L.H_condensed || rhs == L.condensed_rhs, "condensed leaves were formed for another right-hand side");
-        double* tail = d_hel.p + hel_cap + L.nshared;
-        launch_border_tail(rhs, tail, L.m, st);
-        L.solver.factor(d_hel.p, st, &ctx->timers, true, L.H_condensed);
-        L.border_state2 = 2;
-        L.factored = true;
-        cnt.factor++;
-        return;
+        launch_border_tail(rhs, d_hel.p + hel_cap + L.nshared, L.m, st);
+        L.solver.factor(d_hel.p, st, &ctx->timers, true, plan.condensed());
+    } else {
+        if (plan.write == HTail::Rhs) {          // border column -g, corner -1: the factorization carries the forward substitution of H x = g
+            launch_border_tail(rhs, L.Hval.p + L.nnz, L.m, st);
+        } else if (plan.write == HTail::Identity) {       // border column 0, corner 1: block diagonal, ordinary solves
+            MGB_HIP_CHECK(hipMemsetAsync(L.Hval.p + L.nnz, 0, sizeof(double) * (size_t)L.m, st));
+            launch_fill(1.0, L.Hval.p + L.nnz + L.m, 1, st);
+        }
+        L.solver.factor(L.Hval.p, st, &ctx->timers);
     }
-    L.border_state2 = 0;
-    if (rhs) {          // border column -g, corner -1: the factorization carries the forward substitution of H x = g
-        launch_border_tail(rhs, L.Hval.p + L.nnz, L.m, st);
-        L.border_state = 2;
-    } else if (L.border_state != 1) {       // border column 0, corner 1: block diagonal, ordinary solves
-        MGB_HIP_CHECK(hipMemsetAsync(L.Hval.p + L.nnz, 0, sizeof(double) * (size_t)L.m, st));
-        launch_fill(1.0, L.Hval.p + L.nnz + L.m, 1, st);
-        L.border_state = 1;
-    }
-    L.solver.factor(L.Hval.p, st, &ctx->timers);
-    L.factored = true;
+    L.H.factors_ready(plan);
     cnt.factor++;
 }
 
 bool mgbhip_problem::lu_fallback(int level, const double* d_g, double* d_xout) {
     Level& L = levels[level];
     static const bool off = env_on("MGBHIP_NO_LU_FALLBACK");
-    if (off || sharded() || !L.have_H || L.H_in_slab || L.m < 1 || L.m > DENSE_LU_MAX_M || L.Hval.n < (size_t)L.nnz || !L.Hptr.p || !L.Hcol.p)
+    if (off || sharded() || !L.H.in_csr() || L.m < 1 || L.m > DENSE_LU_MAX_M || L.Hval.n < (size_t)L.nnz || !L.Hptr.p || !L.Hcol.p)
         return false;
     hipStream_t st = stream();
     d_lu.ensure((size_t)L.m * (size_t)L.m);
@@ -950,13 +947,12 @@ bool mgbhip_problem::lu_fallback(int level, const double* d_g, double* d_xout) {
 
 void mgbhip_problem::trisolve(int level, const double* d_g, double* d_xout) {
     Level& L = levels[level];
-    MGB_REQUIRE(L.factored, "triangular solve before factorization");
-    MGB_REQUIRE(L.border_state == 1 && L.border_state2 == 0, "triangular solve on factors that carry a Newton right-hand side");
+    L.H.may_solve();
     L.solver.solve(d_g, d_xout, stream(), &ctx->timers);
 }
 
 void mgbhip_problem::trisolve_carried(int level, double* d_xout_np1) {
     Level& L = levels[level];
-    MGB_REQUIRE(L.factored && (L.border_state == 2 || L.border_state2 == 2), "carried solve without a factorization that carries the right-hand side");
+    L.H.may_solve_carried();
     L.solver.solve_border(d_xout_np1, stream(), &ctx->timers);
 }

@@ -7,6 +7,7 @@
 
 #include "../../include/mgbhip.h"
 #include "common.hpp"
+#include "hessian_state.hpp"
 #include "kernels.hpp"
 #include "mf_solver.hpp"
 
@@ -70,25 +71,28 @@ struct Level {
     // dense (spectral) levels: DR = [D_k R_{state(k)}]_k stacked ((nD*n) x m) and W = Ybar * DR
     DevBuf<double> denseDR, denseW;
     MfSolver solver;
-    bool have_H = false, factored = false;
+    HessianState H;                       // where the last eval_f2 / set_hessian left H, the border tail of Hval, the factors
     // direct values (fine / selection levels): the solver reads single-contribution entries of H straight from the
     // element-block slab d_hel and the shared ones from a compact array behind it: no CSR value array is formed
     bool direct = false;
     int64_t nshared = 0;
     DevBuf<int32_t> sh_q;                 // CSR positions of the shared entries
     std::vector<int32_t> h_vmap;          // CSR position -> index into [slab | shared | border]
-    bool H_in_slab = false;               // the last eval_f2 of this level left H in d_hel (not in Hval)
     // domain decomposition (mgbhip_problem_set_sharding): interface columns and the ownership mask of this rank
     bool sharded = false;
     std::vector<int32_t> h_iface;
     DevBuf<int32_t> d_iface;
     DevBuf<double> own, iface_buf;
     bool condense_tried = false, condense = false;   // leaf fronts written by the element kernel (kernels.hpp)
-    bool H_condensed = false;             // the last eval_f2 did so: d_hel holds no blocks, the arena holds the leaves
-    const double* condensed_rhs = nullptr;
-    int border_state2 = 0;                // 2: the current factors came from the slab path with a Newton right-hand side
-    int border_state = 0;                 // tail of Hval: 0 unset, 1 identity border (solve), 2 Newton right-hand side (solve_border)
 };
+
+// A line-search trial point x - alpha * dir that has not been written out yet: the element kernel of a selection level
+// forms it on the fly (driver.cpp: trial_values).  An argument of the evaluation, never a member of the problem.
+struct TrialPoint { const double* x; const double* dir; double alpha; };
+
+// Request to run restriction, |g|^2 partials and (x != nullptr) the line-search step x, n, s -> xn, moved stamp as ONE launch
+struct TrialRestrict { const double* x = nullptr; const double* n = nullptr; double s = 0.0;
+                       double* xn = nullptr; int32_t* moved = nullptr; int32_t stamp = 0; };
 
 struct Counters {
     int64_t f0 = 0, f1 = 0, f2 = 0, factor = 0, newton = 0;
@@ -125,10 +129,10 @@ struct mgbhip_problem {
     // z0 + R*s is cached in d_zfull across the f0/f1/f2 calls at one point: the key is the
     // (level, s, z) pointers plus a stamp every writer of those vectors bumps (touch()).
     int64_t zstamp = 0;
-    mutable int64_t zf_stamp = -1;
-    mutable int zf_level = -1;
-    mutable const double* zf_s = nullptr;
-    mutable const double* zf_z = nullptr;
+    struct PointKey {
+        int64_t stamp = -1; int level = -1; const double* s = nullptr; const double* z = nullptr;
+        bool operator==(const PointKey& o) const { return stamp == o.stamp && level == o.level && s == o.s && z == o.z; }
+    } zf;                                  // the point d_zfull holds
     void touch() { ++zstamp; }
     // one process per GPU (include/mgbhip.h: mgbhip_problem_set_collective)
     mgbhip_allreduce_fn coll_fn = nullptr;
@@ -143,7 +147,20 @@ struct mgbhip_problem {
     const double* own_mask(int level) const { return levels[level].sharded ? levels[level].own.p : nullptr; }
     mgbhip::DevBuf<double> d_gpart, d_gnpart;                        // partial gradients (right-hand sides of the local eliminations)
 
-    mgbhip::ElemParams base_params(int level, const double* d_s, const double* d_zz, const double* d_cc) const;
+    // everything of ElemParams that does not depend on the evaluation point (z0 stays null: the caller binds a point)
+    mgbhip::ElemParams elem_params(const double* d_cc) const;
+    // Resolves the point z0 + R*s of an evaluation: d_zfull when it already holds it; on a selection level the element kernel
+    // gathers s itself (trial: from x - alpha dir) and writes d_zfull; otherwise a prolongation kernel is launched into d_zfull.
+    // Returns true when the element kernel about to be launched writes d_zfull: the cache entry is recorded behind that
+    // launch (launch_elem_at), so a kernel that was not launched has promised nothing.
+    bool bind_point(mgbhip::ElemParams& E, int level, const double* d_s, const double* d_zz, const mgbhip::TrialPoint* trial = nullptr);
+    void launch_elem_at(mgbhip::ElemParams& E, int mode, int level, const double* d_s, const double* d_zz,
+                        const mgbhip::TrialPoint* trial = nullptr);
+    enum Stage { STAGE_F0, STAGE_F1, STAGE_F01, STAGE_F2, STAGE_ASSEMBLE };
+    const char* stage_name(Stage s, int level) const;      // "f2" on the finest level, "f2_coarse" below it
+    // d_gout = R' d_ret: chunked, long-row or plain gather.  fuse (a line-search trial): restriction, |g|^2 partials and the
+    // step in one launch where the level allows it; returns whether that launch ran
+    bool restrict_ret(int level, double* d_gout, const mgbhip::TrialRestrict* fuse = nullptr);
     hipStream_t stream() const { return ctx->stream; }
     void ensure_plan(int level);
     void ensure_analysis(int level);
@@ -154,16 +171,8 @@ struct mgbhip_problem {
     // complete: 1 650 waits per solve at L = 9) and falls back to hipStreamSynchronize after a millisecond or when polling is off.
     double next_seq() { return ++result_seq; }
     void wait_results(double seq);
-    // fused line-search step (driver.cpp: trial_values): while set, the next evaluation on a selection level reads its point as
-    // trial_x - trial_alpha * trial_dir instead of through the (not yet written) trial vector
-    const double* trial_x = nullptr;
-    const double* trial_dir = nullptr;
-    double trial_alpha = 0.0;
+    // fused line-search step (driver.cpp: trial_values): levels whose element kernel can form a trial point on the fly
     bool can_fuse_step(int level) const;
-    // trial_fuse.want: the caller (trial_values) asks eval_f01_launch to run restriction, |g|^2 partials and the line-search step
-    // (x, n, s -> xn, moved stamp) as ONE launch where the level allows it; .done reports that it happened
-    struct TrialFuse { bool want = false, done = false; const double* x = nullptr; const double* n = nullptr; double s = 0.0;
-                       double* xn = nullptr; int32_t* moved = nullptr; int32_t stamp = 0; } trial_fuse;
     // d_scal[lo .. lo + n) -> pin.d[lo .. lo + n), awaited (publish kernel + polled stamp)
     void read_scalars(int lo, int n);
     double result_seq = 0.0;
@@ -177,8 +186,10 @@ struct mgbhip_problem {
     void eval_f1(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout, double* d_part = nullptr);
     // one line-search trial: f0 (value in d_scal[0]) and f1 (gradient in d_gout) from one sweep over the elements
     // defer_f0_sum: leave the workgroup partials of f0 in d_partials for the caller's finishing launch (launch_trial_finish)
-    void eval_f01_launch(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout, double* d_part = nullptr,
-                         bool defer_f0_sum = false);
+    // trial: d_s has not been written yet, the point is trial->x - trial->alpha * trial->dir (only after touch(), only where
+    // can_fuse_step(level)).  fuse: see restrict_ret; returns whether the fused restriction ran
+    bool eval_f01_launch(int level, const double* d_s, const double* d_zz, const double* d_cc, double* d_gout, double* d_part = nullptr,
+                         bool defer_f0_sum = false, const mgbhip::TrialPoint* trial = nullptr, const mgbhip::TrialRestrict* fuse = nullptr);
     // materialize = false (Newton loop): on direct levels only the shared entries are summed, H is not formed as a CSR
     // value array and the next factor(level, rhs) reads the slab (valid until the next eval_f2 of any level)
     // rhs (with materialize = false): the gradient the following factor(level, rhs) will carry; on levels with
@@ -187,7 +198,7 @@ struct mgbhip_problem {
                  const double* rhs = nullptr);
     bool try_enable_condensed(int level);
     int64_t hel_cap = 0;                   // doubles of the element-block slab region of d_hel; extras live behind it
-    int hel_level = -1;                    // level whose blocks + shared sums d_hel currently holds (direct mode), or -1
+    mgbhip::SlabOwner hel_owner;           // level whose blocks + shared sums d_hel currently holds (direct mode)
     // returns MGBHIP_OK or MGBHIP_ERR_NOT_SPD; x = H^{-1} g on the device
     // rhs == nullptr: factor H for ordinary solves (trisolve).  rhs = g: factor the bordered matrix [H -g; -g' -1],
     // which performs the forward substitution of H x = g inside the factorization; trisolve_carried then needs the

@@ -180,3 +180,81 @@ def test_zero_pivot_falls_back_to_the_pivoted_lu_like_the_reference():
     assert "STATUS 3" in out.stdout, out.stdout + out.stderr
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ))
     assert "SOLVED" in out.stdout, out.stdout + out.stderr
+
+
+# ---- the Hessian's state record (csrc/hessian_state.hpp) and the evaluation point, through the public wrappers ----------
+
+@pytest.fixture(scope="module")
+def ladder():
+    """fem2d_P2 L = 3, p = 1.5 (the smallest ladder of this file) and, from ONE fresh problem, the references the tests below
+    compare with bit for bit: H^{-1} g at the finest level after f2, and f1 at an unrelated point."""
+    import mgb_amd as m
+    from helpers import stacked
+    from mgb_amd.device import DeviceMGBProblem
+    prob = m.assemble(m.amg(m.subdivide(m.fem2d_P2(), 3)), p=1.5)
+    D = DeviceMGBProblem(prob)
+    try:
+        P = D.main
+        J = len(P.level_sizes) - 1
+        rng = np.random.default_rng(11)
+        case = dict(prob=prob, J=J, z0=stacked(prob.g), c=0.1 * prob.f, s=1e-3 * rng.standard_normal(P.level_sizes[J]),
+                    s_coarse=1e-3 * rng.standard_normal(P.level_sizes[J - 1]), g=rng.standard_normal(P.level_sizes[J]),
+                    d=1e-3 * rng.standard_normal(P.level_sizes[J]), x2=1e-3 * rng.standard_normal(P.level_sizes[J]))
+        P.f2(J, case["s"], case["c"], case["z0"])
+        case["x_ref"] = P.solve(J, case["g"])
+        case["f1_ref"] = P.f1(J, case["x2"], case["c"], case["z0"])
+    finally:
+        D.close()
+    for v in case.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return case
+
+
+REJECTED = {
+    "fresh": ([], "solve requested before any Hessian was assembled at this level"),
+    "slab_without_rhs": (["newton_direction"], "a Hessian kept in the slab is factored together with its right-hand side"),
+    "slab_overwritten": (["newton_direction", "f2_coarse"],
+                         "the element blocks of this level's Hessian were overwritten: evaluate f2 again"),
+}
+
+
+@pytest.mark.parametrize("name", list(REJECTED))
+def test_solve_the_state_record_rejects_is_an_invalid_argument_and_the_problem_still_works(ladder, name):
+    """solve(J, g) where no Hessian exists, where the Newton sequence left H in the element-block slab (it is factored with
+    its right-hand side only), and where an f2 of another level has since overwritten that slab: MGBHIP_ERR_INVALID with the
+    message of the rule, raised on the host.  The same problem then evaluates f2 and solves, bit for bit like a fresh one."""
+    from mgb_amd import device as dev
+    from mgb_amd.device import DeviceMGBProblem
+    before, message = REJECTED[name]
+    J, s, c, z0, g = (ladder[k] for k in ("J", "s", "c", "z0", "g"))
+    D = DeviceMGBProblem(ladder["prob"])
+    try:
+        P = D.main
+        for step in before:
+            if step == "newton_direction":
+                P.newton_direction(J, s, c, z0)
+            else:
+                P.f2(J - 1, ladder["s_coarse"], c, z0)
+        with pytest.raises(dev.MGBHipError) as ei:
+            P.solve(J, g)
+        assert ei.value.status == dev.ERR_INVALID and message in str(ei.value), str(ei.value)
+        P.f2(J, s, c, z0)
+        assert np.array_equal(P.solve(J, g), ladder["x_ref"])
+    finally:
+        D.close()
+
+
+def test_no_trial_point_survives_trial_values(ladder):
+    """A line-search trial whose point the element kernel forms on the fly (path bit 0), then f1 at an unrelated point on the
+    same handle: bit for bit the f1 of a fresh handle.  The trial point is an argument of the evaluation, not a member."""
+    from mgb_amd.device import DeviceMGBProblem
+    J, s, c, z0 = (ladder[k] for k in ("J", "s", "c", "z0"))
+    D = DeviceMGBProblem(ladder["prob"])
+    try:
+        P = D.main
+        t = P.trial_values(J, s, ladder["d"], 0.5, c, z0)
+        assert t["on_the_fly"] and t["finite"] == 1 and t["moved"] == 1, t
+        assert np.array_equal(P.f1(J, ladder["x2"], c, z0), ladder["f1_ref"])
+    finally:
+        D.close()
