@@ -445,6 +445,62 @@ int mgbhip_quadrature_plan(int32_t d, int32_t e, int32_t p, int32_t Q, int64_t N
 int mgbhip_quadrature_times(const mgbhip_quadrature* quad, double* ms2);
 int mgbhip_quadrature_destroy(mgbhip_quadrature* quad); /* NULL is a no-op */
 
+/* ---- faces: the facets of a mesh, fluxes through its boundary and jumps across its interior faces ------------------
+ * N elements of p nodes in d = e = 2 or 3 coordinates [x: (p N) x d, element-major; t: N x p global node ids in
+ * [0, 2^31)], F local faces per element with 2^(d-1) corner nodes each [corners: F x 2^(d-1) local node indices] and a
+ * rule of Qf <= 100 points per face: weights wf [Qf] and, per local face, the element basis at the face's points
+ * [phi: F x Qf x p; dphi: F x Qf x p x d, the derivatives in reference coordinates], the reference tangents d xi / d s_j
+ * [tangents: F x (d-1) x d] and the reference outward normal [normals: F x d].  perm [ncode x Qf, ncode = 2 in 2-D and 8
+ * in 3-D]: point q of a face seen from its L side is point perm[code][q] seen from its R side.  Nothing else tells the
+ * library the element family.  Everything is copied.
+ *  - create builds the topology on the device: an (element, face) pair whose sorted corner ids [2-D: both; 3-D: the
+ *    three smallest] occur once is a boundary face, twice an interior face; more often is MGBHIP_ERR_INVALID, as is a
+ *    det J that is not positive and finite at a face point.  Boundary faces are numbered in ascending element * F +
+ *    face, interior faces in ascending lower incidence [the L side].  The code of an interior face: with i0, i1 the
+ *    places of L's first two face corners among R's face corners, i0 in 2-D and 2 i0 + [(i0 xor i1) == 2] in 3-D.
+ *  - topology [any pointer may be NULL]: boundary [B x 2: element, face], interior [I x 4: eL, fL, eR, fR], orientation
+ *    [I], element_faces [N x F: an interior face index, or -1 - b for boundary face b].
+ *  - geometry [which = 0: boundary faces, 1: interior faces from their L side; any pointer may be NULL]: points
+ *    [nf x Qf x d], unit outward normals [nf x Qf x d], measures ds [nf x Qf].  sizes [I]: |F|^(1/(d-1)), |F| the sum of
+ *    an interior face's measures in point order.
+ *  - At point q of local face f of an element with nodes x_i and values z_i:  J = sum_i x_i dphi[f][q][i]^T,
+ *    grad u = J^-T sum_i z_i dphi[f][q][i],  n = J^-T n_ref / |J^-T n_ref|,  ds = wf[q] |J t| [2-D] or
+ *    wf[q] |J t1 x J t2| [3-D],  a = |grad u|^(pexp-2) grad u  [pexp >= 1; the zero vector where grad u = 0].
+ *  - integrate: z [(p N) x ncol]; per column the sum over the boundary of ds weight F with F = u [VALUE] or a . n
+ *    [FLUX]; weight [B x Qf] or NULL for 1; per_face [B x ncol] or NULL; totals [ncol].
+ *  - jumps [I x ncol]: per interior face the sum of ds_L (u_L - u_R)^2 [VALUE] or ds_L (a_L . n_L + a_R . n_R)^2 [FLUX],
+ *    each side evaluated through its own element at the matched point.
+ *  - indicator: eta2 [N x ncol], per element the sum over its interior faces in local face order of (size / 2) times
+ *    the FLUX jump; totals [ncol].
+ *    A face's value is the sum of its Qf terms in an order fixed by Qf alone, totals are compensated sums in face or
+ *    element order: results are reproducible bit for bit, a column's do not depend on the other columns, a face's do
+ *    not depend on the weights of other faces, and totals do not depend on per_face.
+ *  - plan [no handle, no device]: out16 = { threads, lanes per face, faces per workgroup G [0: a face does not fit],
+ *    columns per pass, 1 if the tables are staged in LDS [0: read through L2], threads of the reduction, face groups,
+ *    workgroups, dynamic LDS bytes, bytes of the tables, 0... } for sides = 1 [boundary] or 2 [interior].
+ *  - times: device milliseconds taken with events on the context's stream: ms3 = { the face kernel and the reduction
+ *    of the last integrate / jumps / indicator call [0 before the first], the topology build of create }.            */
+enum { MGBHIP_FACE_VALUE = 0, MGBHIP_FACE_FLUX = 1 };
+typedef struct mgbhip_faces mgbhip_faces;
+int mgbhip_faces_create(mgbhip_ctx* ctx, int32_t d, int32_t p, int64_t N, const double* x, const int32_t* t, int32_t F,
+                        int32_t Qf, const double* wf, const double* phi, const double* dphi, const double* tangents,
+                        const double* normals, const int32_t* corners, int32_t ncode, const int32_t* perm,
+                        mgbhip_faces** out, int64_t* nboundary, int64_t* ninterior);
+int mgbhip_faces_topology(const mgbhip_faces* faces, int32_t* boundary, int32_t* interior, int32_t* orientation,
+                          int32_t* element_faces);
+int mgbhip_faces_geometry(mgbhip_faces* faces, int32_t which, double* points, double* normals, double* measures);
+int mgbhip_faces_sizes(const mgbhip_faces* faces, double* sizes /* I */);
+int mgbhip_faces_integrate(mgbhip_faces* faces, int32_t kind, double pexp, int32_t ncol, const double* z /* (p*N) x ncol */,
+                           const double* weight /* B x Qf, or NULL */, double* per_face /* B x ncol, or NULL */,
+                           double* totals /* ncol */);
+int mgbhip_faces_jumps(mgbhip_faces* faces, int32_t kind, double pexp, int32_t ncol, const double* z /* (p*N) x ncol */,
+                       double* jumps /* I x ncol */);
+int mgbhip_faces_indicator(mgbhip_faces* faces, double pexp, int32_t ncol, const double* z /* (p*N) x ncol */,
+                           double* eta2 /* N x ncol */, double* totals /* ncol */);
+int mgbhip_faces_plan(int32_t d, int32_t p, int32_t Qf, int32_t F, int32_t sides, int64_t nfaces, int32_t* out16);
+int mgbhip_faces_times(const mgbhip_faces* faces, double* ms3);
+int mgbhip_faces_destroy(mgbhip_faces* faces); /* NULL is a no-op */
+
 /* ---- level sets: level curves (d = 2) and isosurfaces (d = 3) of an element-space function ------------------------
  * Every element is sampled on a uniform reference lattice of refine + 1 points per axis (Q_k; axis 0 fastest) or on
  * the barycentric lattice of the refine-fold uniform subdivision (P1 / P2) with its own basis; a lattice square is

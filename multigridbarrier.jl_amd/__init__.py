@@ -28,6 +28,7 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .interpolate import interpolate, PointLocator
     from .closest import closest_point, ClosestPointLocator
     from .integrate import Quadrature, integrate, norm
+    from .faces import Faces, boundary_flux, jump_indicator
     from .contour import isocontour, Contour, tessellate, Tessellation
     from .raycast import RayCaster, camera_rays, render_volume
     from .surface import TriangleCaster, Hits, render_surfaces, render_figure

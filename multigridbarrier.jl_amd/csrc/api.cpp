@@ -11,6 +11,7 @@
 
 #include "closest.hpp"
 #include "contour.hpp"
+#include "faces.hpp"
 #include "figure.hpp"
 #include "interpolate.hpp"
 #include "polyline.hpp"
@@ -64,6 +65,7 @@ struct Handle {
 struct mgbhip_locator : Handle<Locator> {};            // a point locator (interpolate.hpp)
 struct mgbhip_closest : Handle<Closest> {};            // a closest-point locator (closest.hpp)
 struct mgbhip_quadrature : Handle<Quadrature> {};      // a quadrature rule on a mesh (quadrature.hpp)
+struct mgbhip_faces : Handle<Faces> {};                // the facets of a mesh (faces.hpp)
 struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
 struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
 struct mgbhip_weld : Handle<Weld> {};                  // the index of a welded soup (weld.hpp)
@@ -1083,6 +1085,138 @@ int mgbhip_quadrature_times(const mgbhip_quadrature* h, double* ms) {
 }
 
 int mgbhip_quadrature_destroy(mgbhip_quadrature* h) { return destroy_handle(h); }
+
+static_assert(MGBHIP_FACE_VALUE == FACE_VALUE && MGBHIP_FACE_FLUX == FACE_FLUX, "mgbhip.h mirrors FaceKind");
+
+int mgbhip_faces_create(mgbhip_ctx* ctx, int32_t d, int32_t p, int64_t N, const double* x, const int32_t* t, int32_t F, int32_t Qf,
+                        const double* wf, const double* phi, const double* dphi, const double* tangents, const double* normals,
+                        const int32_t* corners, int32_t ncode, const int32_t* perm, mgbhip_faces** out, int64_t* nboundary,
+                        int64_t* ninterior) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr && nboundary != nullptr && ninterior != nullptr, "null output pointer");
+    MGB_REQUIRE(d == 2 || d == 3, "faces: d must be 2 or 3");
+    MGB_REQUIRE(N > 0, "faces: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1 && F >= 1 && F <= 8 && Qf >= 1, "faces: bad sizes");
+    MGB_REQUIRE(ncode == (d == 2 ? 2 : 8), "faces: the permutation table has 2 codes in 2-D and 8 in 3-D");
+    MGB_REQUIRE(x != nullptr && t != nullptr && wf != nullptr && phi != nullptr && dphi != nullptr && tangents != nullptr &&
+                    normals != nullptr && corners != nullptr && perm != nullptr, "null argument");
+    MGB_REQUIRE(Qf <= FACE_MAX_QF, "faces: at most 100 points per face");
+    MGB_REQUIRE((int64_t)F * (1 + d) * Qf * p < (int64_t)INT32_MAX && (int64_t)p * N * d < (int64_t)INT32_MAX &&
+                    N * F * Qf * (2 * d + 1) < (int64_t)INT32_MAX,
+                "faces: sizes exceed 32-bit indexing");
+    MGB_REQUIRE(face_decide(d, p, Qf, F, 2, 1).G >= 1, "faces: the nodes of one face's elements do not fit in LDS");
+    const int NC = 1 << (d - 1);
+    for (int64_t i = 0; i < (int64_t)p * N * d; ++i) MGB_REQUIRE(std::isfinite(x[i]), "faces: the mesh has non-finite node coordinates");
+    for (int64_t i = 0; i < (int64_t)p * N; ++i) MGB_REQUIRE(t[i] >= 0, "faces: node ids must lie in [0, 2^31)");
+    for (int32_t q = 0; q < Qf; ++q) MGB_REQUIRE(std::isfinite(wf[q]), "faces: the rule must be finite");
+    for (int64_t i = 0; i < (int64_t)F * Qf * p; ++i) MGB_REQUIRE(std::isfinite(phi[i]), "faces: the basis tables must be finite");
+    for (int64_t i = 0; i < (int64_t)F * Qf * p * d; ++i) MGB_REQUIRE(std::isfinite(dphi[i]), "faces: the basis tables must be finite");
+    for (int i = 0; i < F * (d - 1) * d; ++i) MGB_REQUIRE(std::isfinite(tangents[i]), "faces: the tangents must be finite");
+    for (int i = 0; i < F * d; ++i) MGB_REQUIRE(std::isfinite(normals[i]), "faces: the normals must be finite");
+    for (int i = 0; i < F * NC; ++i) MGB_REQUIRE(corners[i] >= 0 && corners[i] < p, "faces: a face corner is not a node of the element");
+    for (int i = 0; i < ncode * Qf; ++i) MGB_REQUIRE(perm[i] >= 0 && perm[i] < Qf, "faces: a permutation entry is not a face point");
+    FacesIn in;
+    in.d = d; in.p = p; in.F = F; in.Qf = Qf; in.ncode = ncode; in.N = N; in.x = x; in.t = t; in.wf = wf; in.phi = phi; in.dphi = dphi;
+    in.tangents = tangents; in.normals = normals; in.corners = corners; in.perm = perm;
+    create_handle(ctx, out, [&](Faces& Fc) { faces_build(Fc, in, ctx->stream); });
+    *nboundary = (*out)->obj.B;
+    *ninterior = (*out)->obj.I;
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_topology(const mgbhip_faces* h, int32_t* boundary, int32_t* interior, int32_t* orientation, int32_t* element_faces) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    faces_topology(h->obj, boundary, interior, orientation, element_faces, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_geometry(mgbhip_faces* h, int32_t which, double* points, double* normals, double* measures) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    MGB_REQUIRE(which == 0 || which == 1, "faces: which must be 0 (boundary) or 1 (interior)");
+    faces_geometry(h->obj, which, points, normals, measures, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_sizes(const mgbhip_faces* h, double* sizes) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    MGB_REQUIRE(sizes != nullptr, "null argument");
+    faces_sizes(h->obj, sizes, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+// the checks integrate, jumps and indicator share
+static void faces_check_call(const Faces& Fc, int32_t kind, double pexp, int32_t ncol, const double* z) {
+    MGB_REQUIRE(kind == FACE_VALUE || kind == FACE_FLUX, "faces: bad kind");
+    MGB_REQUIRE(ncol >= 1, "faces: bad sizes");
+    MGB_REQUIRE(z != nullptr, "null argument");
+    MGB_REQUIRE(kind == FACE_VALUE || (std::isfinite(pexp) && pexp >= 1.0), "faces: p must be finite and >= 1");
+    MGB_REQUIRE((int64_t)Fc.p * Fc.N * ncol < (int64_t)INT32_MAX && Fc.N * Fc.F * ncol < (int64_t)INT32_MAX,
+                "faces: sizes exceed 32-bit indexing");
+}
+
+int mgbhip_faces_integrate(mgbhip_faces* h, int32_t kind, double pexp, int32_t ncol, const double* z, const double* weight,
+                           double* per_face, double* totals) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    faces_check_call(h->obj, kind, pexp, ncol, z);
+    MGB_REQUIRE(totals != nullptr, "null argument");
+    faces_integrate(h->obj, kind, kind == FACE_VALUE ? 2.0 : pexp, ncol, z, weight, per_face, totals, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_jumps(mgbhip_faces* h, int32_t kind, double pexp, int32_t ncol, const double* z, double* jumps) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    faces_check_call(h->obj, kind, pexp, ncol, z);
+    MGB_REQUIRE(jumps != nullptr || h->obj.I == 0, "null argument");
+    faces_jumps(h->obj, kind, kind == FACE_VALUE ? 2.0 : pexp, ncol, z, jumps, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_indicator(mgbhip_faces* h, double pexp, int32_t ncol, const double* z, double* eta2, double* totals) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    faces_check_call(h->obj, FACE_FLUX, pexp, ncol, z);
+    MGB_REQUIRE(eta2 != nullptr && totals != nullptr, "null argument");
+    faces_indicator(h->obj, pexp, ncol, z, eta2, totals, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_plan(int32_t d, int32_t p, int32_t Qf, int32_t F, int32_t sides, int64_t nfaces, int32_t* out) {
+    MGB_API_BEGIN
+    MGB_REQUIRE(out != nullptr, "null argument");
+    MGB_REQUIRE((d == 2 || d == 3) && p >= 1 && Qf >= 1 && F >= 1 && (sides == 1 || sides == 2) && nfaces >= 0, "faces: bad sizes");
+    const FacePlan plan = face_decide(d, p, Qf, F, sides, nfaces);
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = plan.threads; out[1] = plan.S; out[2] = plan.G; out[3] = plan.chunk; out[4] = plan.tables_lds;
+    out[5] = plan.reduce_threads; out[6] = (int32_t)plan.groups; out[7] = (int32_t)plan.grid;
+    out[8] = (int32_t)std::min<size_t>(plan.lds, (size_t)INT32_MAX);
+    out[9] = (int32_t)std::min<size_t>(face_lds_tables(d, p, Qf, F), (size_t)INT32_MAX);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_times(const mgbhip_faces* h, double* ms) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null faces");
+    MGB_REQUIRE(ms != nullptr, "null argument");
+    faces_times(h->obj, ms);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_faces_destroy(mgbhip_faces* h) { return destroy_handle(h); }
 
 int mgbhip_contour_create_embedded(mgbhip_ctx* ctx, int32_t family, int32_t d, int32_t e, int32_t k, int32_t p, int64_t N,
                                    const double* x, const double* table, int32_t nfield, const double* fields,

@@ -120,6 +120,8 @@ EXPORTS = [
     "mgbhip_closest_create", "mgbhip_closest_fetch", "mgbhip_closest_evaluate", "mgbhip_closest_destroy",
     "mgbhip_quadrature_create", "mgbhip_quadrature_points", "mgbhip_quadrature_weights", "mgbhip_quadrature_integrate",
     "mgbhip_quadrature_max", "mgbhip_quadrature_plan", "mgbhip_quadrature_times", "mgbhip_quadrature_destroy",
+    "mgbhip_faces_create", "mgbhip_faces_topology", "mgbhip_faces_geometry", "mgbhip_faces_sizes", "mgbhip_faces_integrate",
+    "mgbhip_faces_jumps", "mgbhip_faces_indicator", "mgbhip_faces_plan", "mgbhip_faces_times", "mgbhip_faces_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
     "mgbhip_tessellate_create", "mgbhip_tessellate_fetch", "mgbhip_tessellate_destroy",
     "mgbhip_weld_create", "mgbhip_weld_fetch", "mgbhip_weld_rounds", "mgbhip_weld_destroy",
@@ -230,6 +232,17 @@ def load_library():
     lib.mgbhip_quadrature_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _ip]
     lib.mgbhip_quadrature_times.argtypes = [vp, _dp]
     lib.mgbhip_quadrature_destroy.argtypes = [vp]
+    lib.mgbhip_faces_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, _dp, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
+                                        _dp, _ip, C.c_int32, _ip, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mgbhip_faces_topology.argtypes = [vp, _ip, _ip, _ip, _ip]
+    lib.mgbhip_faces_geometry.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    lib.mgbhip_faces_sizes.argtypes = [vp, _dp]
+    lib.mgbhip_faces_integrate.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp, _dp]
+    lib.mgbhip_faces_jumps.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, _dp, _dp]
+    lib.mgbhip_faces_indicator.argtypes = [vp, C.c_double, C.c_int32, _dp, _dp, _dp]
+    lib.mgbhip_faces_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _ip]
+    lib.mgbhip_faces_times.argtypes = [vp, _dp]
+    lib.mgbhip_faces_destroy.argtypes = [vp]
     lib.mgbhip_contour_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp, _dp, C.c_int32,
                                           _dp, C.c_int32, _dp, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.mgbhip_contour_create_embedded.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _dp,
