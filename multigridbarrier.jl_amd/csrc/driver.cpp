@@ -208,12 +208,30 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
     NewtonResult R;
     P->d_x.zero(st, (size_t)C.m);                        // s0 = zeros (src/mgb.jl:45)
     P->touch();                                          // new level / new fine snapshot: drop the cached z0 + R*s
-    double y = C.F0(P->d_x.p);
-    if (!std::isfinite(y)) throw InvalidArgument("newton: initial objective value is not finite");
+    // The start point's value, gradient and |g|^2 like a line-search trial's: one pass over the elements, eval_f1's own
+    // restriction, one finishing launch, one wait (instead of f0 + read-back, f1, vec_stats + read-back).  Where
+    // trial_values does not take its fused path, and under the Illinois search, the start keeps the separate passes;
+    // so do sharded problems.  MGBHIP_SPLIT_START=1 keeps them everywhere.
+    static const bool split_start = env_on("MGBHIP_SPLIT_START");
+    double y;
+    VecStats gs;
+    if (!split_start && !P->dense && !P->sharded() && opt.line_search != 1) {
+        P->eval_f01_launch(C.level, P->d_x.p, C.d_zJ, C.d_c, P->d_g.p, nullptr, true);
+        const double seq = P->next_seq();
+        launch_trial_finish(P->d_g.p, C.m, P->d_scratch.p, P->d_partials.p, elem_grid(P->p, P->N), P->d_scal.p, P->d_flag.p,
+                            P->pin.dev, st, P->own_mask(C.level), seq);
+        P->wait_results(seq);
+        y = P->pin.d[0];
+        if (!std::isfinite(y)) throw InvalidArgument("newton: initial objective value is not finite");
+        gs = VecStats{P->pin.d[2], P->pin.d[3]};
+    } else {
+        y = C.F0(P->d_x.p);
+        if (!std::isfinite(y)) throw InvalidArgument("newton: initial objective value is not finite");
+        if (P->sharded()) { P->d_gpart.ensure((size_t)C.m); P->d_gnpart.ensure((size_t)C.m); }
+        C.F1(P->d_x.p, P->d_g.p, P->d_gpart.p);
+        gs = vec_stats(P, C.level, P->d_g.p, C.m);
+    }
     double ymin = y;
-    if (P->sharded()) { P->d_gpart.ensure((size_t)C.m); P->d_gnpart.ensure((size_t)C.m); }
-    C.F1(P->d_x.p, P->d_g.p, P->d_gpart.p);
-    VecStats gs = vec_stats(P, C.level, P->d_g.p, C.m);
     if (gs.bad != 0.0 || !std::isfinite(gs.sumsq)) throw InvalidArgument("newton: initial gradient has non-finite entries");
     double gnorm = std::sqrt(gs.sumsq);
     double gmin = gnorm;
@@ -335,9 +353,12 @@ StepResult mgb_step(mgbhip_problem* P, const double* d_c, const mgbhip_options& 
     auto eta = [&](int j, int J, const Stop& stop, int maxit) -> bool {
         (void)j;
         const int lev = J - 1;
-        // snapshot zJ = z (the Newton closures capture it, src/mgb.jl:48)
-        MGB_HIP_CHECK(hipMemcpyAsync(P->d_z0.p, P->d_z.p, zn * sizeof(double), hipMemcpyDeviceToDevice, st));
-        NewtonCtx C{P, lev, P->d_z0.p, d_c, P->levels[lev].m};
+        // zJ = z (the Newton closures capture it, src/mgb.jl:48).  Nothing writes d_z until the solve has returned and its
+        // result is prolonged into it below, so the solve reads d_z itself; newton() calls touch() first, so the cached
+        // z0 + R*s of an earlier solve cannot match.  MGBHIP_Z_SNAPSHOT=1 copies z into d_z0 and reads that, as before.
+        static const bool snapshot = env_on("MGBHIP_Z_SNAPSHOT");
+        if (snapshot) MGB_HIP_CHECK(hipMemcpyAsync(P->d_z0.p, P->d_z.p, zn * sizeof(double), hipMemcpyDeviceToDevice, st));
+        NewtonCtx C{P, lev, snapshot ? P->d_z0.p : P->d_z.p, d_c, P->levels[lev].m};
         NewtonResult r = newton(C, opt, stop, maxit);
         out.its[lev] += r.k;
         if (r.converged) {

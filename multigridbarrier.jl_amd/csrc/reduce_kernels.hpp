@@ -150,7 +150,91 @@ struct FinishParams {
     int32_t host_lo, host_n;
     double seq;                  // != 0: written to host[15] after the results (system-scope fence in between): the host polls it
 };
+// The jobs of one finishing launch do not depend on each other, and almost none of the kernel's time is bandwidth: it is one
+// dependent memory latency per rolled `s += src[i]` and ten barriers per job.  So: the partials of ALL jobs are requested
+// before the first addition (U loads per job in flight, larger counts in chunks of 256 U), and the jobs' LDS trees run side
+// by side, one barrier per level.  Per job every thread still forms s = 0.0; s += src[tid]; s += src[tid + 256]; ... in
+// ascending order and the tree pairs as before (off = 128 .. 1, red[tid] += red[tid + off]): the sums are bit for bit
+// those of finish_serial_kernel (MGBHIP_FINISH_SERIAL=1 launches that one).
+constexpr int FINISH_LOADS_IN_FLIGHT = 8;       // 8 and 16 measure the same at L = 9 (6.8 / 6.9 us per launch): the smaller kernel
+template <int U>
 __global__ __launch_bounds__(256) void finish_kernel(const FinishParams P) {
+    __shared__ double red[4][256];
+    __shared__ double res[16];
+    const int tid = threadIdx.x;
+    if (tid < P.nints) {
+        res[P.ints_out + tid] = (double)P.ints[tid];
+        if (P.reset) P.ints[tid] = 0;
+    }
+    int64_t cnt[4], cmax = 0;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        cnt[o] = o < P.njobs ? P.job[o].count : 0;      // a job that is not there loads nothing and sums to 0.0
+        cmax = cnt[o] > cmax ? cnt[o] : cmax;
+    }
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t base = 0; base < cmax; base += 256 * U) {
+        double v[4][U];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const double* __restrict__ src = P.job[o].src;
+            // (one uniform test per job and chunk.  Past the end a lane re-reads the job's last partial and drops it below:
+            // no load sits behind a branch of its own -- a uniform test per row of 256 measured 1.1 us slower per launch)
+            if (base < cnt[o]) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t i = base + u * 256 + tid;
+                    v[o][u] = src[i < cnt[o] ? i : cnt[o] - 1];
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[o][u] = 0.0;
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = base + u * 256 + tid;
+                if (i < cnt[o]) s[o] += v[o][u];
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) red[o][tid] = s[o];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) {
+#pragma unroll
+            for (int o = 0; o < 4; ++o) red[o][tid] += red[o][tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+            if (o < P.njobs) res[P.job[o].out] = red[o][0];
+    }
+    __syncthreads();
+    // results -> device scalar block (every slot this launch produced) and -> host
+    if (tid < 16) {
+        bool mine = false;
+        for (int o = 0; o < P.njobs; ++o) mine = mine || (P.job[o].out == tid);
+        if (tid >= P.ints_out && tid < P.ints_out + P.nints) mine = true;
+        if (mine) P.out[tid] = res[tid];
+        if (P.host && tid >= P.host_lo && tid < P.host_lo + P.host_n) P.host[tid] = mine ? res[tid] : P.out[tid];
+    }
+    if (P.host && P.seq != 0.0) {
+        __threadfence_system();                      // this thread's result stores are visible to the host ...
+        __syncthreads();                             // ... for every writing thread, before the stamp
+        if (tid == 0) {
+            __hip_atomic_store(P.host + 15, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// The jobs one after another (MGBHIP_FINISH_SERIAL=1): the kernel finish_kernel<U> is held to, bit for bit.
+__global__ __launch_bounds__(256) void finish_serial_kernel(const FinishParams P) {
     __shared__ double red[256];
     __shared__ double res[16];
     const int tid = threadIdx.x;
@@ -202,7 +286,9 @@ static int reduce_blocks(int64_t n);      // workgroups of a vector reduction: k
 int64_t reduce_scratch_doubles(int64_t n) { return 3 * (int64_t)reduce_blocks(n); }
 
 static void launch_finish(const FinishParams& F, hipStream_t st) {
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, F);
+    static const bool serial = env_on("MGBHIP_FINISH_SERIAL");
+    if (serial) hipLaunchKernelGGL(finish_serial_kernel, dim3(1), dim3(256), 0, st, F);
+    else hipLaunchKernelGGL(finish_kernel<FINISH_LOADS_IN_FLIGHT>, dim3(1), dim3(256), 0, st, F);
     MGB_HIP_CHECK(hipGetLastError());
 }
 
