@@ -388,7 +388,7 @@ int mgbhip_solve_newton(mgbhip_problem* P, int32_t level, const double* g, doubl
     hipStream_t st = P->stream();
     const size_t m = (size_t)P->levels[level].m;
     P->d_g.upload(g, m, st);
-    P->factor(level, P->d_g.p);                    // [H -g; -g' -1]: the forward substitution rides along
+    P->factor(level, P->d_g.p, P->d_nv.p);         // [H -g; -g' -1]: the forward substitution rides along
     P->trisolve_carried(level, P->d_nv.p);         // one backward sweep from x_n = 1
     int status = P->levels[level].solver.status(st);
     if (status != MGBHIP_OK && P->lu_fallback(level, P->d_g.p, P->d_nv.p)) status = MGBHIP_OK;   // LDL' failed: pivoted LU (src/utils.jl:145)
@@ -443,7 +443,7 @@ int mgbhip_newton_direction(mgbhip_problem* P, int32_t level, const double* s, c
     P->eval_f1(level, P->d_x.p, P->d_z0.p, P->d_c.p, P->d_g.p);
     P->eval_f2(level, P->d_x.p, P->d_z0.p, P->d_c.p, false, P->d_g.p);      // exactly the Newton loop's sequence
     if (condensed) *condensed = P->levels[level].H.condensed() ? 1 : 0;
-    P->factor(level, P->d_g.p);
+    P->factor(level, P->d_g.p, P->d_nv.p);
     P->trisolve_carried(level, P->d_nv.p);
     const int status = P->levels[level].solver.status(st);
     P->d_nv.download(x, m, st);

@@ -250,7 +250,7 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
         int fstatus = MGBHIP_OK;
         int leaf_flag = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
-            P->factor(C.level, C.rhs_of_g());               // the gradient rides along: no forward sweep afterwards
+            P->factor(C.level, C.rhs_of_g(), P->d_nv.p);    // the gradient rides along: no forward sweep afterwards
             P->trisolve_carried(C.level, P->d_nv.p);
             // pivot flags, direction statistics and lambda^2 = <g, n> in one round trip: the finishing launch stores them in
             // the pinned block and clears the solver's flags for the next factorization (no copy / memset launches)

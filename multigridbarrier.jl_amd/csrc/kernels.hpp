@@ -139,7 +139,7 @@ void launch_prolong(int64_t rows, const int32_t* ptr, const int32_t* col, const 
 void launch_step(const double* x, const double* n, double s, double* xn, int64_t len, int32_t* moved, int32_t stamp,
                  hipStream_t st);
 void launch_scale_copy(const double* src, double alpha, double* dst, int64_t len, hipStream_t st);
-void launch_border_tail(const double* g, double* tail, int64_t m, hipStream_t st);   // tail = [-g; -1]
+void launch_border_tail(const double* g, double* tail, int64_t m, hipStream_t st, double* x_one = nullptr);   // tail = [-g; -1]; *x_one = 1
 void launch_axpy(double alpha, const double* x, double* y, int64_t len, hipStream_t st);
 void launch_fill(double value, double* y, int64_t len, hipStream_t st);       // y[:] = value
 

@@ -55,11 +55,16 @@ struct MfSwitches {
                             // static maps (default 0: big_gather_ct chooses per launch)
     bool bwd_split;         // off with MGBHIP_BWD_SPLIT=0: one workgroup per front in every backward launch of the inverse-based
                             // path (bwd_inv_split; the reference of tests/test_gpu_backward_launches.py)
+    int small_threads;      // MGBHIP_SMALL_THREADS=256/512/1024: that many threads per front in every mf_factor_small launch of a
+                            // class > 32 (default 0: factor_small_threads chooses per launch; tests/test_gpu_small_threads.py)
+    bool border_launches;   // MGBHIP_BORDER_LAUNCHES=1: a carried factorization and its sweep launch the 1 x 1 border front too
+                            // (MfSolver::skips_border; the reference of tests/test_gpu_border_skip.py)
     static MfSwitches from_env() {
         auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
         return {env_on("MGBHIP_NO_GEO"), env_on("MGBHIP_OLD_BIG"), !env_on("MGBHIP_NO_MERGE_GROUPS"), !env_on("MGBHIP_NO_PACKED_LEAVES"),
                 !env_on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0),
-                env_on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0), num("MGBHIP_BWD_SPLIT", 1) != 0};
+                env_on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0), num("MGBHIP_BWD_SPLIT", 1) != 0,
+                (int)num("MGBHIP_SMALL_THREADS", 0), env_on("MGBHIP_BORDER_LAUNCHES")};
     }
 };
 
@@ -250,6 +255,40 @@ inline MfBlock0 big_block0_kind(const MfLaunch& L, bool inv) {
 // Backward sweep of an LDS launch: the register-resident variants for max_k <= 8 / <= 16, 0 = the general one
 // (a 32-column variant holds 143 registers and loses more to occupancy on the 8192-front level than it gains)
 inline int backward_small_kmax(const MfLaunch& L) { return L.max_k <= 8 ? 8 : (L.max_k <= 16 ? 16 : 0); }
+
+// ---- threads per front of mf_factor_small ---------------------------------------------------------------------------
+// Dynamic LDS of one workgroup: the front (a packed triangle for the classes >= 88) + the 8-column scaled panel.  The
+// kernel's static arrays (child descriptors, one child's relative indices, pivot reciprocals) add SMALL_STATIC_LDS.
+inline size_t factor_small_lds(int cls) {
+    return (size_t)((cls >= 88 ? cls * (cls + 1) / 2 : cls * cls) + 8 * cls) * sizeof(double);
+}
+constexpr int SMALL_STATIC_LDS = 2112;
+constexpr int CU_LDS_BYTES = 160 * 1024;    // LDS of a gfx950 compute unit
+constexpr int SMALL_FILL_WAVES = 24;        // waves of one launch on a compute unit up to which wider workgroups won (below)
+// One workgroup per front, and nothing in the kernel's arithmetic depends on its size: the fill, the extend-add, the update
+// tiles and the write-back are dealt out to however many threads there are, in the same per-entry order.  256 threads are
+// right for a launch that fills the device.  One that does not leaves the compute units' wave slots empty, and the same
+// fronts finish sooner with more threads each.  A compute unit has per_cu workgroups of the launch at a time: ceil(count /
+// compute units), and at most what the class's LDS lets it hold (class 128: two; a larger launch runs in rounds of that
+// many).  The rule takes the widest of 256 / 512 / 1024 threads that keeps per_cu * threads / 64 <= SMALL_FILL_WAVES:
+//   per_cu 1 (count <= 256 on the MI355X): 1024    2 and 3: 512    4 and more: 256
+// which is, launch by launch, what three alternating passes over every LDS launch of the fem2d_P2 L = 9 ladder chose
+// (profiles/small_threads_ab.txt: 1024 threads lose from per_cu = 2 on, 512 from per_cu = 4 on, by up to a factor of two;
+// class 128 gains from 512 threads at 512 fronts, one round, and at 620, two).  `forced`: MGBHIP_SMALL_THREADS.  Classes
+// <= 32 keep 64 / 128 threads.  The panel solve takes one row per thread, so a launch needs threads >= m - 1: 64 / 128 /
+// 256 cover the classes 16 / 32 / 128 (static_assert below, MGB_REQUIRE in launch_factor_small).
+inline int factor_small_threads(const MfLaunch& L, int compute_units, int forced = 0) {
+    if (L.cls <= 16) return 64;
+    if (L.cls <= 32) return 128;
+    if (forced == 256 || forced == 512 || forced == 1024) return forced;
+    const int64_t cu = std::max(compute_units, 1);
+    const int64_t fit = std::max<int64_t>(1, CU_LDS_BYTES / (int64_t)(factor_small_lds(L.cls) + SMALL_STATIC_LDS));
+    const int64_t per_cu = std::min(fit, ((int64_t)L.count + cu - 1) / cu);
+    int threads = 256;
+    while (threads < 1024 && per_cu * (2 * threads / 64) <= SMALL_FILL_WAVES) threads *= 2;
+    return threads;
+}
+static_assert(16 - 1 <= 64 && 32 - 1 <= 128 && 128 - 1 <= 256, "mf_factor_small solves one panel row per thread");
 
 // Destination columns per workgroup of mf_big_gather on the static maps: 8 (two per wave), doubled up to 32 while the launch
 // keeps at least GATHER_MIN_WGS column workgroups.  A workgroup's fixed cost -- descriptor, map rows into LDS, two

@@ -222,6 +222,24 @@ void MfSolver::analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, 
     std::vector<int32_t> gmap;
     if (!sw.gather_lds_maps) build_gather_maps(plan, level_launches, grec, gmap);
     gather_ct = sw.gather_ct;
+    small_threads = sw.small_threads;
+    {   // compute units of the device in use: factor_small_threads sets a launch's workgroups against them
+        int dev = 0, cus = 0;
+        MGB_HIP_CHECK(hipGetDevice(&dev));
+        MGB_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        compute_units = std::max(cus, 1);
+    }
+    border_launches = sw.border_launches;
+    {   // the border unknown's own root front (mf_analyze: above every other root, so alone on the last level)
+        const int32_t nlev = (int32_t)plan.level_ptr.size() - 1;
+        border_alone = false;
+        if (plan.border && nlev >= 2 && plan.level_ptr[nlev] - plan.level_ptr[nlev - 1] == 1) {
+            const Front& f = plan.fronts[plan.level_ptr[nlev - 1]];
+            border_alone = f.m == 1 && f.k == 1 && plan.front_idx[f.idx_off] == (int32_t)plan.n;
+        }
+    }
+    border_skipped = false;
+    carried_x = nullptr;
     if (grec.empty()) { d_grec.release(); d_gmap.release(); }
     else { d_grec.upload(grec, st); d_gmap.upload(gmap, st); }
     d_fronts.upload(fd, st);
@@ -245,7 +263,11 @@ void MfSolver::set_direct_map(const int32_t* value_map, int64_t nnz, int64_t tai
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
-void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timers, bool direct, bool condensed) {
+bool MfSolver::skips_border() const {
+    return analyzed && border_alone && !border_launches && !robust && plan.iface_front < 0;
+}
+
+void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timers, bool direct, bool condensed, double* carried_x_np1) {
     MGB_REQUIRE(!direct || d_a_src_direct.n > 0, "MfSolver::factor: no direct value map");
     MGB_REQUIRE(!condensed || (direct && condensed_ok), "MfSolver::factor: condensed leaves are not enabled");
     MGB_REQUIRE(analyzed, "MfSolver::factor before analyze");
@@ -255,14 +277,20 @@ void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timer
     const FactorArgs a{condensed ? d_fronts_c.p : d_fronts.p, d_children.p, d_rel.p,
                        condensed ? d_a_src_c.p : (direct ? d_a_src_direct.p : d_a_src.p), condensed ? d_a_dst_c.p : d_a_dst.p,
                        condensed ? d_a_colptr_c.p : d_a_colptr.p, d_values, d_arena.p, d_dscr.p, d_dvec.p, d_status.p, st,
-                       d_grec.n ? d_grec.p : nullptr, d_gmap.p, gather_ct};
+                       d_grec.n ? d_grec.p : nullptr, d_gmap.p, gather_ct, small_threads, compute_units};
     if (timers) timers->begin("factor");
     factored_inv = !robust;
+    // The border front's pivot -1 - lambda^2 is read by nobody on the carried path (the Newton loop forms lambda^2 = <g, n>
+    // itself, and a non-finite pivot there means a non-finite lambda^2, which it reports): no launch for it.
+    border_skipped = carried_x_np1 != nullptr && skips_border();
+    carried_x = border_skipped ? carried_x_np1 : nullptr;
+    const int border_level = (int)level_launches.size() - 1;
     if (!status_zero) MGB_HIP_CHECK(hipMemsetAsync(d_status.p, 0, sizeof(int32_t), st));      // [1], the leaf flag of a condensing f2, stays
     status_zero = false;
     factored_condensed = condensed;
     int lvno = -1;
     for (auto& lev : level_launches) {
+        if (border_skipped && lvno + 1 == border_level) break;
         LevelScope lvscope(timers, "fac", ++lvno);
         for (auto& L : lev) {
             if (L.count == 0) continue;
@@ -303,6 +331,7 @@ void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timer
 
 void MfSolver::solve(const double* d_b, double* d_x, hipStream_t st, StageTimers* timers) {
     MGB_REQUIRE(analyzed, "MfSolver::solve before analyze");
+    MGB_REQUIRE(!border_skipped, "MfSolver::solve on factors that carry a Newton right-hand side");      // no border pivot
     if (timers) timers->begin("trisolve");
     // the factored system is [H c; c' gamma] with c = 0 (set_border_identity): solve it for [b; 0]
     const size_t n = (size_t)plan.n;
@@ -329,7 +358,12 @@ void MfSolver::solve_border(double* d_x_np1, hipStream_t st, StageTimers* timers
         MGB_HIP_CHECK(hipMemcpyAsync(d_y.p + n, d_one.p, sizeof(double), hipMemcpyDeviceToDevice, st));
         y_border_one = true;
     }
-    backward_pass(d_x_np1, st, timers);
+    // Without the border front's launch (factor() with carried_x) x[n] = 1 is the caller's: the kernel that wrote this
+    // system's border column stored it, after every earlier writer of the output on the stream and with nothing between
+    // it and this sweep.  Any other output gets its own copy.
+    if (border_skipped && d_x_np1 != carried_x)
+        MGB_HIP_CHECK(hipMemcpyAsync(d_x_np1 + n, d_one.p, sizeof(double), hipMemcpyDeviceToDevice, st));
+    backward_pass(d_x_np1, st, timers, border_skipped);
     MGB_HIP_CHECK(hipGetLastError());
     if (timers) timers->end();
 }
@@ -352,9 +386,10 @@ void MfSolver::forward_pass(const double* d_b, hipStream_t st, StageTimers* time
     }
 }
 
-void MfSolver::backward_pass(double* d_x, hipStream_t st, StageTimers* timers) {
+void MfSolver::backward_pass(double* d_x, hipStream_t st, StageTimers* timers, bool without_border) {
     const SolveArgs a = solve_args(nullptr, d_x, st);
-    for (int32_t l = (int32_t)level_solves.size() - 1; l >= 0; --l) {
+    // without_border: the last level, the border front, only stores x[n] = y[n] = 1, which d_x already holds
+    for (int32_t l = (int32_t)level_solves.size() - (without_border ? 2 : 1); l >= 0; --l) {
         LevelScope lvscope(timers, "bwd", l);
         for (auto it = level_solves[l].rbegin(); it != level_solves[l].rend(); ++it) {
             const MfLaunch& L = *it;

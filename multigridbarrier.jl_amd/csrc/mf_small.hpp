@@ -83,11 +83,13 @@ __global__ void mf_factor_small(const FrontDev* __restrict__ fr, int32_t first,
         }
         __syncthreads();
         for (int c0 = 0; c0 < nc; c0 += 4) {
-            if (nt == 256 && (c0 & 15) == 0) {
+            if (nt >= 256 && (c0 & 15) == 0) {
                 // Sixteen small children (update block <= 8 x 8) at once: wave w takes children 4w .. 4w+3, one entry
                 // per lane, so ALL their loads are in flight together (one memory latency for the group instead
                 // of four).  The additions keep child order: a wave applies its four children in program order
                 // (LDS operations of one wave stay ordered) and the waves take turns, four barriers in all.
+                // Written for four waves: in a wider workgroup (factor_small_threads) waves 4 and up own no child
+                // (4 w >= 16 >= ng) and only join the barriers.
                 const int ng = min(16, nc - c0);
                 bool small16 = true;
                 for (int u = 0; u < ng; ++u) small16 = small16 && cB[c0 + u] * cB[c0 + u] <= 64;
@@ -686,13 +688,11 @@ __global__ __launch_bounds__(256) void mf_backward_tiny(const FrontDev* __restri
 }
 
 // ---- host launchers ------------------------------------------------------------------------------------------
-// mf_factor_small: the front (a packed triangle for the classes >= 88) + the 8-column scaled panel
-inline size_t factor_small_lds(int cls) {
-    return (size_t)((cls >= 88 ? cls * (cls + 1) / 2 : cls * cls) + 8 * cls) * sizeof(double);
-}
+// mf_factor_small: LDS by factor_small_lds, threads per front by factor_small_threads (mf_launch_plan.hpp)
 inline void launch_factor_small(const FactorArgs& a, const MfLaunch& L) {
     // 8-column LDS panels (16- and 32-column ones were measured slower in round 3 and removed in round 4)
-    const int threads = L.cls <= 16 ? 64 : (L.cls <= 32 ? 128 : 256);
+    const int threads = factor_small_threads(L, a.compute_units, a.small_threads);
+    MGB_REQUIRE(threads >= L.max_m - 1, "mf_factor_small: fewer threads than panel rows");      // one row per thread in the panel solve
     if (L.cls >= 88)
         hipLaunchKernelGGL((mf_factor_small<8, true>), dim3(L.count), dim3(threads), factor_small_lds(L.cls), a.st, a.fr, L.first,
                            a.children, a.rel, a.a_src, a.a_dst, a.values, a.arena, a.status);

@@ -34,6 +34,8 @@ struct FactorArgs {
     const GatherRec* grec;      // static gather maps of mf_big_gather (build_gather_maps); nullptr: the kernel builds them in LDS
     const int32_t* gmap;
     int gather_ct;              // MGBHIP_GATHER_CT (0: big_gather_ct chooses)
+    int small_threads;          // MGBHIP_SMALL_THREADS (0: factor_small_threads chooses)
+    int compute_units;          // of the device, for factor_small_threads
 };
 struct SolveArgs {
     const FrontDev* fr;
@@ -62,7 +64,15 @@ class MfSolver {
     // direct = true: d_values is the value space of set_direct_map (slab | shared | border) instead of the CSR array
     // condensed = true (needs direct and enable_condensed): the leaf fronts are already in the arena, written by the
     // element kernel of the same Newton iteration; the leaf level is skipped and no matrix entry is read
-    void factor(const double* d_values, hipStream_t st, StageTimers* timers, bool direct = false, bool condensed = false);
+    // carried_x (optional, needs a c = -g border): the n + 1 doubles the one solve_border() of these factors will write,
+    // with carried_x[n] = 1 already on the stream.  The launches of the 1 x 1 border front are then left out where
+    // skips_border() allows it: nobody reads its pivot -1 - lambda^2, and its backward launch only stores that 1.
+    void factor(const double* d_values, hipStream_t st, StageTimers* timers, bool direct = false, bool condensed = false,
+                double* carried_x = nullptr);
+    // Whether a factor() with carried_x leaves out the border front's launches: not under MGBHIP_BORDER_LAUNCHES=1, not for
+    // the robust refactorization, not with an interface front (domain decomposition), and only when the tree's last level
+    // is that front alone.
+    bool skips_border() const;
     // Condensed leaves (kernels.hpp, launch_elem_f2_condense).  N elements of P nodes, ucol[e * P + i] = unknown of the
     // u component at node i of element e or -1, node P - 1 interior to the element, slack unknown of broken node q =
     // slack0 + q.  Checks that the plan's leaf level is exactly one front per element with the element's slacks and
@@ -92,6 +102,8 @@ class MfSolver {
     // x = H^{-1} b (device vectors of length n; x may alias b); factors must come from a c = 0 border
     void solve(const double* d_b, double* d_x, hipStream_t st, StageTimers* timers);
     // x[0:n] = H^{-1} g for factors of the c = -g border; d_x_np1 has room for n + 1 doubles (x[n] = 1 on return)
+    // After a factor() that left the border front out, its backward launch is left out too; x[n] is the caller's 1
+    // (d_x_np1 == carried_x), or is copied there first for any other output.
     void solve_border(double* d_x_np1, hipStream_t st, StageTimers* timers);
     // Shape of one factorization + backward sweep as the device runs it (mgbhip_solver_chain): out[0] sequential
     // 32-column pivot blocks on the critical path of the large fronts (sum over their tree levels of ceil(max_k / 32)),
@@ -125,7 +137,7 @@ class MfSolver {
                 d_uvec.p, d_tbig.p, d_tsol.p, st, d_bwd_g.p, d_bwd_cnt.n ? d_bwd_cnt.p : nullptr};
     }
     void forward_pass(const double* d_b_np1, hipStream_t st, StageTimers* timers);
-    void backward_pass(double* d_x_np1, hipStream_t st, StageTimers* timers);
+    void backward_pass(double* d_x_np1, hipStream_t st, StageTimers* timers, bool without_border = false);
     DevBuf<double> d_bx, d_xx, d_one;     // bordered right-hand side / solution of solve(), the constant 1
     DevBuf<FrontDev> d_fronts;
     DevBuf<int32_t> d_front_idx, d_children, d_rel, d_a_src, d_a_src_direct, d_a_dst, d_a_colptr;
@@ -148,6 +160,12 @@ class MfSolver {
     std::vector<std::vector<MfLaunch>> level_launches;   // per level, leaves first (factorization: one per LDS class)
     std::vector<std::vector<MfLaunch>> level_solves;     // triangular solves: all LDS-class fronts of a level in one launch
     int gather_ct = 0;              // MfSwitches::gather_ct of the last analyze()
+    int small_threads = 0;          // MfSwitches::small_threads of the last analyze()
+    int compute_units = 1;          // of the current device, queried by analyze()
+    bool border_launches = false;   // MfSwitches::border_launches of the last analyze()
+    bool border_alone = false;      // the plan's last level is the 1 x 1 border front and nothing else
+    bool border_skipped = false;    // the current factors were formed without the border front's launch ...
+    const double* carried_x = nullptr;   // ... and this output holds the 1 its backward launch would store
     int32_t lds_cap = 88;           // largest m factored out of LDS
     bool uses_inv = false;
     bool y_border_one = false;      // d_y[n] holds the 1 the border sweep starts from

@@ -905,24 +905,28 @@ void mgbhip_problem::ensure_direct(int level) {
     }
 }
 
-void mgbhip_problem::factor(int level, const double* rhs) {
+void mgbhip_problem::factor(int level, const double* rhs, double* carried_out) {
     Level& L = levels[level];
     const FactorPlan plan = L.H.about_to_factor(hel_owner, level, rhs);      // throws when this H cannot be factored this way
     hipStream_t st = stream();
     ensure_analysis(level);
+    // Carried (plan.write == HTail::Rhs: the factors allow trisolve_carried only) and the caller has named the sweep's output:
+    // no launches for the border front.  The solver decides (not for its robust refactorization, not under the switch).
+    double* const carried_x = (plan.write == HTail::Rhs && carried_out && !sharded() && L.solver.skips_border()) ? carried_out : nullptr;
+    double* const x_one = carried_x ? carried_x + L.m : nullptr;
     if (plan.slab()) {
         // H was not materialised (eval_f2 with materialize = false): the values are the slab + shared sums in d_hel
         ensure_direct(level);
-        launch_border_tail(rhs, d_hel.p + hel_cap + L.nshared, L.m, st);
-        L.solver.factor(d_hel.p, st, &ctx->timers, true, plan.condensed());
+        launch_border_tail(rhs, d_hel.p + hel_cap + L.nshared, L.m, st, x_one);
+        L.solver.factor(d_hel.p, st, &ctx->timers, true, plan.condensed(), carried_x);
     } else {
         if (plan.write == HTail::Rhs) {          // border column -g, corner -1: the factorization carries the forward substitution of H x = g
-            launch_border_tail(rhs, L.Hval.p + L.nnz, L.m, st);
+            launch_border_tail(rhs, L.Hval.p + L.nnz, L.m, st, x_one);
         } else if (plan.write == HTail::Identity) {       // border column 0, corner 1: block diagonal, ordinary solves
             MGB_HIP_CHECK(hipMemsetAsync(L.Hval.p + L.nnz, 0, sizeof(double) * (size_t)L.m, st));
             launch_fill(1.0, L.Hval.p + L.nnz + L.m, 1, st);
         }
-        L.solver.factor(L.Hval.p, st, &ctx->timers);
+        L.solver.factor(L.Hval.p, st, &ctx->timers, false, false, carried_x);
     }
     L.H.factors_ready(plan);
     cnt.factor++;

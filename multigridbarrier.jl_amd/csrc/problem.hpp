@@ -203,7 +203,10 @@ struct mgbhip_problem {
     // rhs == nullptr: factor H for ordinary solves (trisolve).  rhs = g: factor the bordered matrix [H -g; -g' -1],
     // which performs the forward substitution of H x = g inside the factorization; trisolve_carried then needs the
     // backward sweep only (the Newton loop's one solve per factorization).
-    void factor(int level, const double* rhs = nullptr);
+    // carried_out (with rhs): the m + 1 doubles the trisolve_carried that follows will write.  The kernel that writes the
+    // border column then also stores carried_out[m] = 1, the value the sweep starts from, and the solver leaves out the two
+    // launches of the 1 x 1 border front (MfSolver::skips_border); without it, or on a sharded problem, they stay.
+    void factor(int level, const double* rhs = nullptr, double* carried_out = nullptr);
     void trisolve(int level, const double* d_g, double* d_xout);
     void trisolve_carried(int level, double* d_xout_np1);      // output has room for m + 1 doubles
     // The reference's last resort when the symmetric factorizations fail (Julia's `Symmetric(H) \ g`: Cholesky -> LDL' -> LU,

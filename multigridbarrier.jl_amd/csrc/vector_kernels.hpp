@@ -124,11 +124,16 @@ __global__ __launch_bounds__(256) void scale_copy_kernel(const double* __restric
     if (i < len) dst[i] = alpha * src[i];
 }
 
-// border column of the bordered Newton system: tail[0 .. m) = -g, tail[m] = -1 (one launch)
-__global__ __launch_bounds__(256) void border_tail_kernel(const double* __restrict__ g, double* __restrict__ tail, int64_t m) {
+// border column of the bordered Newton system: tail[0 .. m) = -g, tail[m] = -1 (one launch).  x_one (optional): the entry
+// x[m] = 1 the backward sweep of this system starts from, when the border front has no launch of its own
+__global__ __launch_bounds__(256) void border_tail_kernel(const double* __restrict__ g, double* __restrict__ tail, int64_t m,
+                                                          double* __restrict__ x_one) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < m) tail[i] = -1.0 * g[i];
-    else if (i == m) tail[i] = -1.0;
+    else if (i == m) {
+        tail[i] = -1.0;
+        if (x_one) *x_one = 1.0;
+    }
 }
 
 __global__ __launch_bounds__(256) void axpy_kernel(double alpha, const double* __restrict__ x,
@@ -213,8 +218,8 @@ void launch_scale_copy(const double* src, double alpha, double* dst, int64_t len
     MGB_HIP_CHECK(hipGetLastError());
 }
 
-void launch_border_tail(const double* g, double* tail, int64_t m, hipStream_t st) {
-    hipLaunchKernelGGL(border_tail_kernel, dim3((unsigned)((m + 1 + 255) / 256)), dim3(256), 0, st, g, tail, m);
+void launch_border_tail(const double* g, double* tail, int64_t m, hipStream_t st, double* x_one) {
+    hipLaunchKernelGGL(border_tail_kernel, dim3((unsigned)((m + 1 + 255) / 256)), dim3(256), 0, st, g, tail, m, x_one);
     MGB_HIP_CHECK(hipGetLastError());
 }
 
