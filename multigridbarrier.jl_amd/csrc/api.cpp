@@ -987,6 +987,16 @@ static_assert(MGBHIP_QUAD_VALUE == QUAD_VALUE && MGBHIP_QUAD_LP == QUAD_LP && MG
 
 static bool quad_dims_ok(int32_t d, int32_t e) { return d >= 1 && d <= 3 && e >= d && e <= 3; }
 
+// the ten slots of mgbhip_quadrature_plan and mgbhip_faces_plan (16 are zeroed).  lds: slot 8 as each entry point has always
+// reported plan.lds (the faces plan stops at INT32_MAX, the quadrature plan converts); the table bytes stop at INT32_MAX
+static void quad_plan_out(const QuadPlan& plan, int32_t lds, size_t table_bytes, int32_t* out) {
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = plan.threads; out[1] = plan.S; out[2] = plan.G; out[3] = plan.chunk; out[4] = plan.tables_lds;
+    out[5] = plan.reduce_threads; out[6] = (int32_t)plan.groups; out[7] = (int32_t)plan.grid;
+    out[8] = lds;
+    out[9] = (int32_t)std::min<size_t>(table_bytes, (size_t)INT32_MAX);
+}
+
 int mgbhip_quadrature_create(mgbhip_ctx* ctx, int32_t d, int32_t e, int32_t p, int64_t N, const double* x, int32_t Q,
                              const double* wref, const double* phi, const double* dphi, mgbhip_quadrature** out) {
     MGB_API_BEGIN_ON(ctx)
@@ -1067,10 +1077,7 @@ int mgbhip_quadrature_plan(int32_t d, int32_t e, int32_t p, int32_t Q, int64_t N
     MGB_REQUIRE(out != nullptr, "null argument");
     MGB_REQUIRE(quad_dims_ok(d, e) && p >= 1 && Q >= 1 && N >= 1, "quadrature: bad sizes");
     const QuadPlan plan = quad_decide(d, e, p, Q, N);
-    for (int i = 0; i < 16; ++i) out[i] = 0;
-    out[0] = plan.threads; out[1] = plan.S; out[2] = plan.G; out[3] = plan.chunk; out[4] = plan.tables_lds;
-    out[5] = plan.reduce_threads; out[6] = (int32_t)plan.groups; out[7] = (int32_t)plan.grid; out[8] = (int32_t)plan.lds;
-    out[9] = (int32_t)std::min<size_t>(quad_lds_tables(d, p, Q), (size_t)INT32_MAX);
+    quad_plan_out(plan, (int32_t)plan.lds, quad_lds_tables(d, p, Q), out);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1197,12 +1204,8 @@ int mgbhip_faces_plan(int32_t d, int32_t p, int32_t Qf, int32_t F, int32_t sides
     MGB_API_BEGIN
     MGB_REQUIRE(out != nullptr, "null argument");
     MGB_REQUIRE((d == 2 || d == 3) && p >= 1 && Qf >= 1 && F >= 1 && (sides == 1 || sides == 2) && nfaces >= 0, "faces: bad sizes");
-    const FacePlan plan = face_decide(d, p, Qf, F, sides, nfaces);
-    for (int i = 0; i < 16; ++i) out[i] = 0;
-    out[0] = plan.threads; out[1] = plan.S; out[2] = plan.G; out[3] = plan.chunk; out[4] = plan.tables_lds;
-    out[5] = plan.reduce_threads; out[6] = (int32_t)plan.groups; out[7] = (int32_t)plan.grid;
-    out[8] = (int32_t)std::min<size_t>(plan.lds, (size_t)INT32_MAX);
-    out[9] = (int32_t)std::min<size_t>(face_lds_tables(d, p, Qf, F), (size_t)INT32_MAX);
+    const QuadPlan plan = face_decide(d, p, Qf, F, sides, nfaces);
+    quad_plan_out(plan, (int32_t)std::min<size_t>(plan.lds, (size_t)INT32_MAX), face_lds_tables(d, p, Qf, F), out);
     return MGBHIP_OK;
     MGB_API_END
 }

@@ -148,6 +148,35 @@ struct StageTimers {
     }
 };
 
+// The events around the intervals of an object's last call (Quadrature, Faces): begin() records ev[0] and mark(i) ev[i];
+// ms(i) is the device time from ev[i] to ev[i + 1], 0 if either was never recorded.  timed: the last call ran to its end.
+// Here and not in quad_device.hpp because api.cpp sees the objects that hold one, and that header carries a kernel.
+template <int N>
+struct CallEvents {
+    hipEvent_t ev[N] = {};
+    bool timed = false;
+    CallEvents() = default;
+    CallEvents(const CallEvents&) = delete;
+    CallEvents& operator=(const CallEvents&) = delete;
+    ~CallEvents() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(int i, hipStream_t st) {
+        if (!ev[i]) MGB_HIP_CHECK(hipEventCreate(&ev[i]));
+        MGB_HIP_CHECK(hipEventRecord(ev[i], st));
+    }
+    void begin(hipStream_t st) {
+        timed = false;
+        mark(0, st);
+    }
+    double ms(int i) const {
+        float t = 0.0f;
+        if (ev[i] && ev[i + 1]) MGB_HIP_CHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+        return t;
+    }
+};
+
 struct StageScope {
     StageTimers& t;
     StageScope(StageTimers& tt, const char* name) : t(tt) { t.begin(name); }

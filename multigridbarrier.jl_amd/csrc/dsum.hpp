@@ -1,6 +1,7 @@
 // dsum.hpp -- the compensated sum every translation unit that adds long columns shares (reduce_kernels.hpp and its
-// users in kernels.hip, quadrature.hip).  Internal linkage, like device_prims.hpp: the library is built without
-// relocatable device code, so each translation unit carries its own copy of what it inlines.
+// users in kernels.hip; quad_device.hpp and its users quadrature.hip and faces.hip).  Internal linkage, like
+// device_prims.hpp: the library is built without relocatable device code, so each translation unit carries its own copy
+// of what it inlines.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -19,9 +19,10 @@
 // with the compiler's default contraction (fast: a product feeding a sum may be fused, which only removes roundings).
 // An interior face evaluates each side through its own element map, the R side at point perm[orientation][q].
 //
-// Summation order.  No atomics.  The Qf terms of a face are added by a halving tree over its Qf lanes, which depends on
-// Qf alone; totals are the compensated sums of dsum.hpp over the faces (or the elements) in a fixed shape, as in
-// quadrature.hip.  The indicator gathers an element's interior faces through element_faces in local face order.
+// Summation order.  No atomics.  The Qf terms of a face are added by a halving tree over its Qf lanes (the lines of
+// quadrature.hip's), which depends on Qf alone; totals are the column reduction of quad_device.hpp over the faces (or the
+// elements): the very kernel quadrature.hip runs.  The indicator gathers an element's interior faces through
+// element_faces in local face order.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,8 +31,8 @@
 #include <vector>
 
 #include "device_prims.hpp"
-#include "dsum.hpp"
 #include "faces.hpp"
+#include "quad_device.hpp"
 
 namespace mgbhip {
 
@@ -225,7 +226,7 @@ __device__ __forceinline__ void face_geo(const double* xe, const double* tabf, c
     geo.rnn = 1.0 / sqrt(n2);
 }
 
-// u (FACE_VALUE) or a(grad u) . n (FACE_FLUX) at the point, for the column whose nodal values are zc[i * FACE_CHUNK]
+// u (FACE_VALUE) or a(grad u) . n (FACE_FLUX) at the point, for the column whose nodal values are zc[i * QUAD_CHUNK]
 template <int D, int KIND>
 __device__ __forceinline__ double face_eval(const FaceGeo<D>& geo, const double* zc, const double* tabf, int p, int Qf, int q,
                                             int pmode, double pexp) {
@@ -237,7 +238,7 @@ __device__ __forceinline__ double face_eval(const FaceGeo<D>& geo, const double*
     const double z0 = zc[0];
     for (int i = 0; i < p; ++i) {
         const double* t = tabf + (size_t)i * (1 + D) * Qf + q;
-        const double zi = zc[i * FACE_CHUNK];
+        const double zi = zc[i * QUAD_CHUNK];
         if constexpr (KIND == FACE_VALUE) u = __builtin_fma(t[0], zi, u);
         else {
             const double dz = zi - z0;
@@ -281,7 +282,7 @@ struct FaceParams {
 };
 
 template <int D, int SIDES, int KIND, bool TAB_LDS>
-__global__ __launch_bounds__(FACE_THREADS) void face_kernel(const FaceParams P) {
+__global__ __launch_bounds__(QUAD_THREADS) void face_kernel(const FaceParams P) {
     extern __shared__ __attribute__((aligned(16))) double face_lds[];
     const int tid = threadIdx.x, p = P.p, Qf = P.Qf, G = P.G, ncol = P.ncol;
     constexpr int SW = 2 * SIDES, FG = (D - 1) * D + D;
@@ -290,9 +291,9 @@ __global__ __launch_bounds__(FACE_THREADS) void face_kernel(const FaceParams P) 
     double* red = zs + face_lds_zs(G, SIDES, p);
     const double* tab = P.tab;
     if constexpr (TAB_LDS) {
-        double* tl = red + face_lds_red();
+        double* tl = red + quad_lds_red();
         const int n = P.F * (1 + D) * Qf * p;
-        for (int i = tid; i < n; i += FACE_THREADS) tl[i] = P.tab[i];
+        for (int i = tid; i < n; i += QUAD_THREADS) tl[i] = P.tab[i];
         tab = tl;                                   // first read after the barrier behind the z chunk
     }
     const int g = tid / Qf, q = tid - g * Qf;
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(FACE_THREADS) void face_kernel(const FaceParams P) 
         const int nfl = (int)((P.nf - f0) < (int64_t)G ? (P.nf - f0) : (int64_t)G);
         const int sides = nfl * SIDES;
         __syncthreads();
-        for (int i = tid; i < sides * per; i += FACE_THREADS) {
+        for (int i = tid; i < sides * per; i += QUAD_THREADS) {
             const int gs = i / per, r = i - gs * per;
             const int64_t e = P.faces[(f0 + gs / SIDES) * SW + 2 * (gs % SIDES)];
             xs[i] = P.x[e * per + r];
@@ -322,13 +323,13 @@ __global__ __launch_bounds__(FACE_THREADS) void face_kernel(const FaceParams P) 
             }
         }
         FaceGeo<D> geoL, geoR;
-        for (int c0 = 0; c0 < ncol; c0 += FACE_CHUNK) {
-            const int nc = (ncol - c0) < FACE_CHUNK ? (ncol - c0) : FACE_CHUNK;
-            for (int i = tid; i < sides * p * nc; i += FACE_THREADS) {
+        for (int c0 = 0; c0 < ncol; c0 += QUAD_CHUNK) {
+            const int nc = (ncol - c0) < QUAD_CHUNK ? (ncol - c0) : QUAD_CHUNK;
+            for (int i = tid; i < sides * p * nc; i += QUAD_THREADS) {
                 const int row = i / nc, c = i - row * nc;
                 const int gs = row / p, node = row - gs * p;
                 const int64_t e = P.faces[(f0 + gs / SIDES) * SW + 2 * (gs % SIDES)];
-                zs[row * FACE_CHUNK + c] = P.z[(e * p + node) * ncol + c0 + c];
+                zs[row * QUAD_CHUNK + c] = P.z[(e * p + node) * ncol + c0 + c];
             }
             __syncthreads();
             if (active) {
@@ -343,32 +344,29 @@ __global__ __launch_bounds__(FACE_THREADS) void face_kernel(const FaceParams P) 
                 if constexpr (SIDES == 1)
                     if (P.weight) w *= P.weight[(f0 + g) * Qf + q];
                 for (int c = 0; c < nc; ++c) {
-                    const double vL = face_eval<D, KIND>(geoL, zs + (g * SIDES) * p * FACE_CHUNK + c, tabL, p, Qf, q, P.pmode, P.pexp);
+                    const double vL = face_eval<D, KIND>(geoL, zs + (g * SIDES) * p * QUAD_CHUNK + c, tabL, p, Qf, q, P.pmode, P.pexp);
                     double term;
                     if constexpr (SIDES == 1) {
                         term = w * vL;
                     } else {
-                        const double vR = face_eval<D, KIND>(geoR, zs + (g * SIDES + 1) * p * FACE_CHUNK + c, tabR, p, Qf, qR, P.pmode, P.pexp);
+                        const double vR = face_eval<D, KIND>(geoR, zs + (g * SIDES + 1) * p * QUAD_CHUNK + c, tabR, p, Qf, qR, P.pmode, P.pexp);
                         const double j = KIND == FACE_VALUE ? vL - vR : vL + vR;
                         term = w * (j * j);
                     }
-                    red[c * FACE_THREADS + tid] = term;
+                    red[c * QUAD_THREADS + tid] = term;
                 }
             }
-            for (int off = tree >> 1; off > 0; off >>= 1) {
+            for (int off = tree >> 1; off > 0; off >>= 1) {         // the halving tree: quad_kernel has these lines with a max branch
                 __syncthreads();
                 if (active && q < off && q + off < Qf) {
                     for (int c = 0; c < nc; ++c) {
-                        double* r = red + c * FACE_THREADS + tid;
+                        double* r = red + c * QUAD_THREADS + tid;
                         *r = r[0] + r[off];
                     }
                 }
             }
             __syncthreads();
-            if (tid < nfl * nc) {
-                const int gg = tid / nc, c = tid - gg * nc;
-                P.out[(f0 + gg) * ncol + c0 + c] = red[c * FACE_THREADS + gg * Qf];
-            }
+            quad_write_items(P.out, red, tid, f0, nfl, Qf, ncol, c0, nc);
         }
     }
 }
@@ -376,12 +374,12 @@ __global__ __launch_bounds__(FACE_THREADS) void face_kernel(const FaceParams P) 
 // points (nf x Qf x d), normals (nf x Qf x d) and measures (nf x Qf) of the faces whose [element, face] pairs start every
 // row of `faces` (stride sw); any may be null
 template <int D>
-__global__ __launch_bounds__(FACE_THREADS) void face_geometry_kernel(const double* __restrict__ x, const double* __restrict__ wf,
+__global__ __launch_bounds__(QUAD_THREADS) void face_geometry_kernel(const double* __restrict__ x, const double* __restrict__ wf,
                                                                      const double* __restrict__ tab, const double* __restrict__ fgeo,
                                                                      const int32_t* __restrict__ faces, int sw, int64_t nf, int p, int Qf,
                                                                      double* __restrict__ points, double* __restrict__ normals,
                                                                      double* __restrict__ measures) {
-    const int64_t idx = (int64_t)blockIdx.x * FACE_THREADS + threadIdx.x;
+    const int64_t idx = (int64_t)blockIdx.x * QUAD_THREADS + threadIdx.x;
     if (idx >= nf * Qf) return;
     const int64_t fc = idx / Qf;
     const int q = (int)(idx - fc * Qf);
@@ -449,45 +447,16 @@ __global__ __launch_bounds__(BLOCK) void face_indicator_kernel(const int32_t* __
     eta2[i] = s;
 }
 
-// totals[col] = the compensated sum of column col of rows (n x ncol): one workgroup per column, as quadrature.hip
-__global__ __launch_bounds__(FACE_REDUCE_THREADS) void face_reduce_kernel(const double* __restrict__ rows, int64_t n, int ncol,
-                                                                          double* __restrict__ totals) {
-    __shared__ double ws[FACE_REDUCE_THREADS / 64], wc[FACE_REDUCE_THREADS / 64];
-    const int tid = threadIdx.x, col = blockIdx.x;
-    constexpr int W = FACE_REDUCE_THREADS / 64;
-    DSum a;
-#pragma unroll 4
-    for (int64_t i = tid; i < n; i += FACE_REDUCE_THREADS) a.add(rows[i * ncol + col]);
-    dsum_wave_reduce(a);
-    if ((tid & 63) == 0) { ws[tid >> 6] = a.s; wc[tid >> 6] = a.c; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < W; ++w) a.merge(ws[w], wc[w]);
-        totals[col] = a.value();
-    }
-}
-
 // ---- launchers ------------------------------------------------------------------------------------------------------
 
-template <int D, int SIDES, int KIND, bool TAB_LDS>
-void launch_face(const FaceParams& P, const FacePlan& plan, hipStream_t st) {
-    static const bool big_lds = [] {          // opt-in to more than 64 KB of dynamic LDS, once per instantiation
-        return hipFuncSetAttribute((const void*)face_kernel<D, SIDES, KIND, TAB_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)FACE_LDS_MAX) == hipSuccess;
-    }();
-    if (plan.lds > 64 * 1024 && !big_lds) throw HipError("faces: the device refused the dynamic LDS opt-in");
-    hipLaunchKernelGGL((face_kernel<D, SIDES, KIND, TAB_LDS>), dim3((unsigned)plan.grid), dim3(FACE_THREADS), plan.lds, st, P);
-    MGB_HIP_CHECK(hipGetLastError());
-}
-
 template <int D, int SIDES>
-void launch_face_kind(int kind, const FaceParams& P, const FacePlan& plan, hipStream_t st) {
+void launch_face_kind(int kind, const FaceParams& P, const QuadPlan& plan, hipStream_t st) {
     if (kind == FACE_VALUE) {
-        if (plan.tables_lds) launch_face<D, SIDES, FACE_VALUE, true>(P, plan, st);
-        else launch_face<D, SIDES, FACE_VALUE, false>(P, plan, st);
+        if (plan.tables_lds) quad_launch<face_kernel<D, SIDES, FACE_VALUE, true>>("faces", P, plan, st);
+        else quad_launch<face_kernel<D, SIDES, FACE_VALUE, false>>("faces", P, plan, st);
     } else {
-        if (plan.tables_lds) launch_face<D, SIDES, FACE_FLUX, true>(P, plan, st);
-        else launch_face<D, SIDES, FACE_FLUX, false>(P, plan, st);
+        if (plan.tables_lds) quad_launch<face_kernel<D, SIDES, FACE_FLUX, true>>("faces", P, plan, st);
+        else quad_launch<face_kernel<D, SIDES, FACE_FLUX, false>>("faces", P, plan, st);
     }
 }
 
@@ -495,7 +464,7 @@ void launch_face_kind(int kind, const FaceParams& P, const FacePlan& plan, hipSt
 void run_faces(Faces& Fc, int sides, int32_t kind, double pexp, int32_t ncol, const double* weight, hipStream_t st) {
     const int64_t nf = sides == 1 ? Fc.B : Fc.I;
     if (nf == 0) return;
-    const FacePlan plan = face_decide(Fc.d, Fc.p, Fc.Qf, Fc.F, sides, nf);
+    const QuadPlan plan = face_decide(Fc.d, Fc.p, Fc.Qf, Fc.F, sides, nf);
     Fc.face.ensure((size_t)nf * ncol);
     FaceParams P{};
     P.x = Fc.x.p; P.wf = Fc.wf.p; P.tab = Fc.tab.p; P.fgeo = Fc.fgeo.p; P.perm = Fc.perm.p;
@@ -503,7 +472,7 @@ void run_faces(Faces& Fc, int sides, int32_t kind, double pexp, int32_t ncol, co
     P.orient = Fc.orientation.p;
     P.z = Fc.z.p; P.weight = weight; P.out = Fc.face.p;
     P.nf = nf; P.p = Fc.p; P.Qf = Fc.Qf; P.F = Fc.F; P.ncol = ncol; P.G = plan.G;
-    P.pmode = pexp == 1.0 ? 1 : pexp == 2.0 ? 2 : 0;
+    P.pmode = quad_pmode(pexp);
     P.pexp = pexp;
     if (Fc.d == 2) {
         if (sides == 1) launch_face_kind<2, 1>(kind, P, plan, st);
@@ -514,27 +483,15 @@ void run_faces(Faces& Fc, int sides, int32_t kind, double pexp, int32_t ncol, co
     }
 }
 
-void reduce_columns(const double* rows, int64_t n, int32_t ncol, double* totals, hipStream_t st) {
-    hipLaunchKernelGGL(face_reduce_kernel, dim3((unsigned)ncol), dim3(FACE_REDUCE_THREADS), 0, st, rows, n, (int)ncol, totals);
-    MGB_HIP_CHECK(hipGetLastError());
-}
-
-void begin_call(Faces& Fc, hipStream_t st) {
-    for (hipEvent_t& e : Fc.ev)
-        if (!e) MGB_HIP_CHECK(hipEventCreate(&e));
-    Fc.timed = false;
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[0], st));
-}
-
 void launch_geometry(const Faces& Fc, const int32_t* faces, int sw, int64_t nf, double* points, double* normals, double* measures,
                      hipStream_t st) {
     if (nf == 0) return;
-    const unsigned grid = (unsigned)((nf * Fc.Qf + FACE_THREADS - 1) / FACE_THREADS);
+    const unsigned grid = (unsigned)((nf * Fc.Qf + QUAD_THREADS - 1) / QUAD_THREADS);
     if (Fc.d == 2)
-        hipLaunchKernelGGL((face_geometry_kernel<2>), dim3(grid), dim3(FACE_THREADS), 0, st, Fc.x.p, Fc.wf.p, Fc.tab.p, Fc.fgeo.p, faces, sw,
+        hipLaunchKernelGGL((face_geometry_kernel<2>), dim3(grid), dim3(QUAD_THREADS), 0, st, Fc.x.p, Fc.wf.p, Fc.tab.p, Fc.fgeo.p, faces, sw,
                            nf, Fc.p, Fc.Qf, points, normals, measures);
     else
-        hipLaunchKernelGGL((face_geometry_kernel<3>), dim3(grid), dim3(FACE_THREADS), 0, st, Fc.x.p, Fc.wf.p, Fc.tab.p, Fc.fgeo.p, faces, sw,
+        hipLaunchKernelGGL((face_geometry_kernel<3>), dim3(grid), dim3(QUAD_THREADS), 0, st, Fc.x.p, Fc.wf.p, Fc.tab.p, Fc.fgeo.p, faces, sw,
                            nf, Fc.p, Fc.Qf, points, normals, measures);
     MGB_HIP_CHECK(hipGetLastError());
 }
@@ -603,13 +560,8 @@ void faces_build(Faces& Fc, const FacesIn& in, hipStream_t st) {
     const int NC = 1 << (d - 1), FG = (d - 1) * d + d;
     std::vector<double> tab((size_t)F * p * (1 + d) * Qf), fgeo((size_t)F * FG);
     for (int f = 0; f < F; ++f) {
-        double* tf = tab.data() + (size_t)f * p * (1 + d) * Qf;
-        for (int q = 0; q < Qf; ++q)
-            for (int i = 0; i < p; ++i) {
-                const size_t src = ((size_t)f * Qf + q) * p + i;
-                tf[((size_t)i * (1 + d)) * Qf + q] = in.phi[src];
-                for (int b = 0; b < d; ++b) tf[((size_t)i * (1 + d) + 1 + b) * Qf + q] = in.dphi[src * d + b];
-            }
+        const size_t at = (size_t)f * Qf * p;
+        quad_repack_tables(d, p, Qf, in.phi + at, in.dphi + at * d, tab.data() + at * (1 + d));
         for (int j = 0; j < (d - 1) * d; ++j) fgeo[(size_t)f * FG + j] = in.tangents[(size_t)f * (d - 1) * d + j];
         for (int a = 0; a < d; ++a) fgeo[(size_t)f * FG + (d - 1) * d + a] = in.normals[(size_t)f * d + a];
     }
@@ -622,12 +574,10 @@ void faces_build(Faces& Fc, const FacesIn& in, hipStream_t st) {
     Fc.fgeo.upload(fgeo, st);
     Fc.corners.upload(in.corners, (size_t)F * NC, st);
     Fc.perm.upload(in.perm, (size_t)in.ncode * Qf, st);
-    for (hipEvent_t& e : Fc.ev)
-        if (!e) MGB_HIP_CHECK(hipEventCreate(&e));
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[3], st));
+    Fc.ev.mark(3, st);
     if (d == 2) build_topology<2>(Fc, key_bits((uint64_t)top), st);
     else build_topology<4>(Fc, key_bits((uint64_t)top), st);
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[4], st));
+    Fc.ev.mark(4, st);
     // det J at every face point of every element
     const int64_t M = in.N * F;
     DevBuf<int32_t> bad;
@@ -687,26 +637,26 @@ void faces_integrate(Faces& Fc, int32_t kind, double pexp, int32_t ncol, const d
     Fc.z.upload(z, (size_t)Fc.p * Fc.N * ncol, st);
     if (weight) Fc.weight.upload(weight, (size_t)Fc.B * Fc.Qf, st);
     Fc.totals.ensure((size_t)ncol);
-    begin_call(Fc, st);
+    Fc.ev.begin(st);
     run_faces(Fc, 1, kind, pexp, ncol, weight ? Fc.weight.p : nullptr, st);
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[1], st));
-    reduce_columns(Fc.face.p, Fc.B, ncol, Fc.totals.p, st);
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[2], st));
+    Fc.ev.mark(1, st);
+    quad_reduce_columns(Fc.face.p, Fc.B, ncol, false, Fc.totals.p, st);
+    Fc.ev.mark(2, st);
     Fc.totals.download(totals, (size_t)ncol, st);
     if (per_face) Fc.face.download(per_face, (size_t)Fc.B * ncol, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
-    Fc.timed = true;
+    Fc.ev.timed = true;
 }
 
 void faces_jumps(Faces& Fc, int32_t kind, double pexp, int32_t ncol, const double* z, double* out, hipStream_t st) {
     Fc.z.upload(z, (size_t)Fc.p * Fc.N * ncol, st);
-    begin_call(Fc, st);
+    Fc.ev.begin(st);
     run_faces(Fc, 2, kind, pexp, ncol, nullptr, st);
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[1], st));
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[2], st));
+    Fc.ev.mark(1, st);
+    Fc.ev.mark(2, st);
     Fc.face.download(out, (size_t)Fc.I * ncol, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
-    Fc.timed = true;
+    Fc.ev.timed = true;
 }
 
 void faces_indicator(Faces& Fc, double pexp, int32_t ncol, const double* z, double* eta2, double* totals, hipStream_t st) {
@@ -714,32 +664,23 @@ void faces_indicator(Faces& Fc, double pexp, int32_t ncol, const double* z, doub
     Fc.elem.ensure((size_t)Fc.N * ncol);
     Fc.totals.ensure((size_t)ncol);
     Fc.face.ensure(1);
-    begin_call(Fc, st);
+    Fc.ev.begin(st);
     run_faces(Fc, 2, FACE_FLUX, pexp, ncol, nullptr, st);
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[1], st));
+    Fc.ev.mark(1, st);
     hipLaunchKernelGGL(face_indicator_kernel, dim3(grid_1d(Fc.N * ncol)), dim3(BLOCK), 0, st, Fc.element_faces.p, Fc.hF.p, Fc.face.p,
                        Fc.N, Fc.F, (int)ncol, Fc.elem.p);
     MGB_HIP_CHECK(hipGetLastError());
-    reduce_columns(Fc.elem.p, Fc.N, ncol, Fc.totals.p, st);
-    MGB_HIP_CHECK(hipEventRecord(Fc.ev[2], st));
+    quad_reduce_columns(Fc.elem.p, Fc.N, ncol, false, Fc.totals.p, st);
+    Fc.ev.mark(2, st);
     Fc.elem.download(eta2, (size_t)Fc.N * ncol, st);
     Fc.totals.download(totals, (size_t)ncol, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
-    Fc.timed = true;
+    Fc.ev.timed = true;
 }
 
 void faces_times(const Faces& Fc, double* ms) {
-    ms[0] = ms[1] = ms[2] = 0.0;
-    float t = 0.0f;
-    if (Fc.timed)
-        for (int i = 0; i < 2; ++i) {
-            MGB_HIP_CHECK(hipEventElapsedTime(&t, Fc.ev[i], Fc.ev[i + 1]));
-            ms[i] = t;
-        }
-    if (Fc.ev[3] && Fc.ev[4]) {
-        MGB_HIP_CHECK(hipEventElapsedTime(&t, Fc.ev[3], Fc.ev[4]));
-        ms[2] = t;
-    }
+    for (int i = 0; i < 2; ++i) ms[i] = Fc.ev.timed ? Fc.ev.ms(i) : 0.0;
+    ms[2] = Fc.ev.ms(3);
 }
 
 }  // namespace mgbhip

@@ -33,12 +33,7 @@ struct Faces {
     DevBuf<int32_t> boundary, interior, orientation, element_faces;     // B x 2, I x 4, I, N x F
     DevBuf<double> hF;                            // I: |F|^(1/(d-1)) from the L side
     DevBuf<double> z, weight, face, elem, totals, geo;    // per call: grown to the largest size seen and kept
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // 0..2 around the last call's face kernel and reduction, 3..4 around the topology build
-    bool timed = false;
-    ~Faces() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    CallEvents<5> ev;                             // 0..2 around the last call's face kernel and reduction, 3..4 around the topology build
 };
 
 // Builds the topology and checks det J at every face point; complete on return.  InvalidArgument for a face shared by

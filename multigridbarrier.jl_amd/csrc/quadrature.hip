@@ -10,15 +10,15 @@
 // Summation order.  No atomics.  Lane s of an element adds the terms of its points s, s + S, ... in that order
 // (S = min(Q, 256)); the S lane sums are added by a halving tree over s.  Both depend on Q alone, so an element's value
 // does not depend on N, on the number of columns or on its place in the workgroup.  The element values go to an N x ncol
-// array, and a second launch adds each column over the elements with the compensated sums of dsum.hpp: one workgroup of
-// 1024 lanes per column, lane t takes the elements t, t + 1024, ..., then the fixed shuffle tree and the 16 wave sums in
-// order.  The shape is fixed, so totals are reproducible bit for bit and a column's total does not depend on the others.
+// array, and the column reduction of quad_device.hpp adds each column over the elements with the compensated sums of
+// dsum.hpp in a fixed shape, so totals are reproducible bit for bit and a column's total does not depend on the others.
+// faces.hip takes the plan, the write-out and the reduction from the same headers and has the same lines for the tree.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 #include <vector>
 
-#include "dsum.hpp"
+#include "quad_device.hpp"
 #include "quadrature.hpp"
 
 namespace mgbhip {
@@ -102,9 +102,6 @@ __device__ __forceinline__ void quad_geo(const double* xs, const double* tab, in
     }
     geo.sdet = sqrt(det);
 }
-
-// a NaN on either side stays
-__device__ __forceinline__ double quad_max(double a, double b) { return (b > a || b != b) ? b : a; }
 
 __device__ __forceinline__ double quad_power(double s2, int pmode, double pexp) {      // |v|^p from s2 = |v|^2
     return pmode == 2 ? s2 : pmode == 1 ? sqrt(s2) : pow(s2, 0.5 * pexp);
@@ -206,7 +203,7 @@ __global__ __launch_bounds__(QUAD_THREADS) void quad_kernel(const QuadParams P) 
                     first = false;
                 }
             }
-            for (int off = tree >> 1; off > 0; off >>= 1) {
+            for (int off = tree >> 1; off > 0; off >>= 1) {         // the halving tree: face_kernel has these lines without the max
                 __syncthreads();
                 if (active && s < off && s + off < S) {
                     for (int c = 0; c < nc; ++c) {
@@ -216,10 +213,7 @@ __global__ __launch_bounds__(QUAD_THREADS) void quad_kernel(const QuadParams P) 
                 }
             }
             __syncthreads();
-            if (tid < nel * nc) {
-                const int gg = tid / nc, c = tid - gg * nc;
-                P.elem[(el0 + gg) * ncol + c0 + c] = red[c * QUAD_THREADS + gg * S];
-            }
+            quad_write_items(P.elem, red, tid, el0, nel, S, ncol, c0, nc);
         }
     }
 }
@@ -243,51 +237,10 @@ __global__ __launch_bounds__(QUAD_THREADS) void quad_geometry_kernel(const doubl
     if (weights) weights[idx] = wref[q] * geo.sdet;
 }
 
-// totals[col] = the compensated sum (or the maximum) of column col of elem (N x ncol): one workgroup per column
-__global__ __launch_bounds__(QUAD_REDUCE_THREADS) void quad_reduce_kernel(const double* __restrict__ elem, int64_t N, int ncol,
-                                                                          int is_max, double* __restrict__ totals) {
-    __shared__ double ws[QUAD_REDUCE_THREADS / 64], wc[QUAD_REDUCE_THREADS / 64];
-    const int tid = threadIdx.x, col = blockIdx.x;
-    constexpr int W = QUAD_REDUCE_THREADS / 64;
-    if (is_max) {
-        double m = 0.0;
-        for (int64_t i = tid; i < N; i += QUAD_REDUCE_THREADS) m = quad_max(m, elem[i * ncol + col]);
-        for (int off = 32; off > 0; off >>= 1) m = quad_max(m, __shfl_down(m, off, 64));
-        if ((tid & 63) == 0) ws[tid >> 6] = m;
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < W; ++w) m = quad_max(m, ws[w]);
-            totals[col] = m;
-        }
-        return;
-    }
-    DSum a;
-#pragma unroll 4                // the loads do not depend on the sum: four in flight per lane, added in order
-    for (int64_t i = tid; i < N; i += QUAD_REDUCE_THREADS) a.add(elem[i * ncol + col]);
-    dsum_wave_reduce(a);
-    if ((tid & 63) == 0) { ws[tid >> 6] = a.s; wc[tid >> 6] = a.c; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < W; ++w) a.merge(ws[w], wc[w]);
-        totals[col] = a.value();
-    }
-}
-
-template <int D, int E, int KIND, bool TAB_LDS>
-void launch_quad(const QuadParams& P, const QuadPlan& plan, hipStream_t st) {
-    static const bool big_lds = [] {          // opt-in to more than 64 KB of dynamic LDS, once per instantiation
-        return hipFuncSetAttribute((const void*)quad_kernel<D, E, KIND, TAB_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)QUAD_LDS_MAX) == hipSuccess;
-    }();
-    if (plan.lds > 64 * 1024 && !big_lds) throw HipError("quadrature: the device refused the dynamic LDS opt-in");
-    hipLaunchKernelGGL((quad_kernel<D, E, KIND, TAB_LDS>), dim3((unsigned)plan.grid), dim3(QUAD_THREADS), plan.lds, st, P);
-    MGB_HIP_CHECK(hipGetLastError());
-}
-
 template <int D, int E, int KIND>
 void launch_quad_tab(const QuadParams& P, const QuadPlan& plan, hipStream_t st) {
-    if (plan.tables_lds) launch_quad<D, E, KIND, true>(P, plan, st);
-    else launch_quad<D, E, KIND, false>(P, plan, st);
+    if (plan.tables_lds) quad_launch<quad_kernel<D, E, KIND, true>>("quadrature", P, plan, st);
+    else quad_launch<quad_kernel<D, E, KIND, false>>("quadrature", P, plan, st);
 }
 
 template <int D, int E>
@@ -318,11 +271,7 @@ void quadrature_build(Quadrature& Qd, int32_t d, int32_t e, int32_t p, int64_t N
                       const double* wref, const double* phi, const double* dphi, hipStream_t st) {
     Qd.d = d; Qd.e = e; Qd.p = p; Qd.Q = Q; Qd.N = N;
     std::vector<double> tab((size_t)(1 + d) * Q * p);
-    for (int q = 0; q < Q; ++q)
-        for (int i = 0; i < p; ++i) {
-            tab[((size_t)i * (1 + d)) * Q + q] = phi[(size_t)q * p + i];
-            for (int b = 0; b < d; ++b) tab[((size_t)i * (1 + d) + 1 + b) * Q + q] = dphi[((size_t)q * p + i) * d + b];
-        }
+    quad_repack_tables(d, p, Q, phi, dphi, tab.data());
     Qd.x.upload(x, (size_t)p * N * e, st);
     Qd.wref.upload(wref, (size_t)Q, st);
     Qd.tab.upload(tab, st);
@@ -360,31 +309,22 @@ void quadrature_integrate(Quadrature& Qd, int32_t kind, double pexp, bool is_max
     P.elem = Qd.elem.p;
     P.N = Qd.N; P.p = Qd.p; P.Q = Qd.Q; P.ncol = ncol; P.S = plan.S; P.G = plan.G;
     P.is_max = is_max ? 1 : 0;
-    P.pmode = pexp == 1.0 ? 1 : pexp == 2.0 ? 2 : 0;
+    P.pmode = quad_pmode(pexp);
     P.pexp = pexp;
-    for (hipEvent_t& e : Qd.ev)
-        if (!e) MGB_HIP_CHECK(hipEventCreate(&e));
-    Qd.timed = false;
-    MGB_HIP_CHECK(hipEventRecord(Qd.ev[0], st));
+    Qd.ev.begin(st);
     dispatch_dims(Qd.d, Qd.e, [&](auto D, auto E) { launch_quad_kind<decltype(D)::value, decltype(E)::value>(kind, P, plan, st); });
-    MGB_HIP_CHECK(hipEventRecord(Qd.ev[1], st));
-    hipLaunchKernelGGL(quad_reduce_kernel, dim3((unsigned)ncol), dim3(QUAD_REDUCE_THREADS), 0, st, Qd.elem.p, Qd.N, (int)ncol,
-                       P.is_max, Qd.totals.p);
-    MGB_HIP_CHECK(hipGetLastError());
-    MGB_HIP_CHECK(hipEventRecord(Qd.ev[2], st));
+    Qd.ev.mark(1, st);
+    quad_reduce_columns(Qd.elem.p, Qd.N, ncol, is_max, Qd.totals.p, st);
+    Qd.ev.mark(2, st);
     Qd.totals.download(totals, (size_t)ncol, st);
     if (per_element) Qd.elem.download(per_element, (size_t)Qd.N * ncol, st);
     MGB_HIP_CHECK(hipStreamSynchronize(st));
-    Qd.timed = true;
+    Qd.ev.timed = true;
 }
 
 void quadrature_times(const Quadrature& Qd, double* ms) {
-    if (!Qd.timed) throw InvalidArgument("quadrature: no integrate call has completed yet");
-    for (int i = 0; i < 2; ++i) {
-        float t = 0.0f;
-        MGB_HIP_CHECK(hipEventElapsedTime(&t, Qd.ev[i], Qd.ev[i + 1]));
-        ms[i] = t;
-    }
+    if (!Qd.ev.timed) throw InvalidArgument("quadrature: no integrate call has completed yet");
+    for (int i = 0; i < 2; ++i) ms[i] = Qd.ev.ms(i);
 }
 
 }  // namespace mgbhip

@@ -16,12 +16,7 @@ struct Quadrature {
     int64_t N = 0;
     DevBuf<double> x, wref, tab;
     DevBuf<double> z, minus, source, elem, totals, geo;   // per call: grown to the largest size seen and kept
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};       // around the element kernel and the reduction of the last call
-    bool timed = false;
-    ~Quadrature() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    CallEvents<3> ev;                                     // around the element kernel and the reduction of the last call
 };
 
 // x host (p*N) x e, wref host Q, phi host Q x p, dphi host Q x p x d; complete on return

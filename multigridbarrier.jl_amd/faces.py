@@ -37,7 +37,7 @@ from . import fem2d_p1, fem2d_p2
 from ._handle import DeviceObject
 from .fem2d_p1 import FEM2D_P1
 from .fem2d_p2 import FEM2D_P2
-from .integrate import MAX_ORDER, gauss_rule_cube, qk_tables, triangle_tables
+from .integrate import MAX_ORDER, PLAN_KEYS, gauss_rule_cube, qk_tables, triangle_tables
 from .interpolate import MAX_DEGREE, _c_f64
 from .multigrid import Geometry
 from .spectral import SPECTRAL1D, SPECTRAL2D
@@ -156,14 +156,14 @@ def face_tables(geom: Geometry, order=None) -> dict:
 
 
 def plan(d: int, p: int, Qf: int, F: int, sides: int, nfaces: int) -> dict:
-    """What `mgbhip_faces_plan` reports for a shape (csrc/faces_layout.hpp `face_decide`): `sides = 1` the boundary
+    """What `mgbhip_faces_plan` reports for a shape (csrc/faces_layout.hpp `face_decide`, the lane plan of
+    csrc/quad_layout.hpp for faces): `sides = 1` the boundary
     kernel, `2` the interior one; needs the library, no device."""
     from .device import _check, load_library
     lib = load_library()
     out = (C.c_int32 * 16)()
     _check(lib, lib.mgbhip_faces_plan(d, p, Qf, F, sides, nfaces, out))
-    keys = ("threads", "S", "G", "chunk", "tables_lds", "reduce_threads", "groups", "grid", "lds", "table_bytes")
-    return dict(zip(keys, (int(v) for v in out)))
+    return dict(zip(PLAN_KEYS, (int(v) for v in out)))
 
 
 def _iptr(a):

@@ -198,14 +198,17 @@ def _exponent(p, allow_inf: bool = False) -> float:
     return p
 
 
+# the slots of mgbhip_quadrature_plan and mgbhip_faces_plan, in order (csrc/quad_layout.hpp `QuadPlan`, then the table bytes)
+PLAN_KEYS = ("threads", "S", "G", "chunk", "tables_lds", "reduce_threads", "groups", "grid", "lds", "table_bytes")
+
+
 def plan(d: int, e: int, p: int, Q: int, N: int) -> dict:
     """What `mgbhip_quadrature_plan` reports for a shape (csrc/quad_layout.hpp `quad_decide`); needs the library, no device."""
     from .device import _check, load_library
     lib = load_library()
     out = (C.c_int32 * 16)()
     _check(lib, lib.mgbhip_quadrature_plan(d, e, p, Q, N, out))
-    keys = ("threads", "S", "G", "chunk", "tables_lds", "reduce_threads", "groups", "grid", "lds", "table_bytes")
-    return dict(zip(keys, (int(v) for v in out)))
+    return dict(zip(PLAN_KEYS, (int(v) for v in out)))
 
 
 class _Spec:
