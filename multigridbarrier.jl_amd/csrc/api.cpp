@@ -576,7 +576,7 @@ int mgbhip_vec_dot(const mgbhip_vec* a, const mgbhip_vec* b, double* out) {
     if (a->len == 0) return MGBHIP_OK;
     mgbhip_ctx* c = a->ctx;
     double* sc = vec_scratch(c, a->len);
-    launch_dot(a->buf.p, b->buf.p, a->len, sc, c->vscal.p, c->stream);
+    launch_dot(a->buf.p, b->buf.p, a->len, sc, c->vscal.p, 0, c->stream);
     c->vscal.download(out, 1, c->stream);
     MGB_HIP_CHECK(hipStreamSynchronize(c->stream));
     return MGBHIP_OK;
@@ -588,7 +588,7 @@ static int vec_stats_host(const mgbhip_vec* a, double* two) {
     two[0] = two[1] = 0.0;
     if (a->len == 0) return MGBHIP_OK;
     double* sc = vec_scratch(c, a->len);
-    launch_vec_stats(a->buf.p, a->len, sc, c->vscal.p, c->stream);
+    launch_vec_stats(a->buf.p, a->len, sc, c->vscal.p, 0, c->stream);
     c->vscal.download(two, 2, c->stream);
     MGB_HIP_CHECK(hipStreamSynchronize(c->stream));
     return MGBHIP_OK;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "host_util.hpp"     // InvalidArgument, MGB_REQUIRE, env_on, debug_level, Stopwatch
+#include "readback.hpp"      // the slots of the scalar read-back block, FinishParams
 
 namespace mgbhip {
 
@@ -73,15 +74,13 @@ struct DevBuf {
 // Small pinned host block for scalar read-backs (a pageable destination sends every 8-byte
 // copy through the runtime's staging path).
 struct PinnedBuf {
-    double* d = nullptr;        // 16 doubles
-    int32_t* i = nullptr;       // 16 ints
-    double* dev = nullptr;      // the same 16 doubles as the device sees them (finishing kernels store their results here)
+    double* d = nullptr;        // RB_SLOTS doubles (readback.hpp)
+    double* dev = nullptr;      // the same doubles as the device sees them (finishing kernels store their results here)
     PinnedBuf() {
         void* p = nullptr;
-        if (hipHostMalloc(&p, 16 * sizeof(double) + 16 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc(&p, RB_SLOTS * sizeof(double), hipHostMallocDefault) != hipSuccess)
             throw HipError("hipHostMalloc failed for the scalar read-back block");
         d = static_cast<double*>(p);
-        i = reinterpret_cast<int32_t*>(d + 16);
         void* dp = nullptr;
         if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess || dp == nullptr)
             throw HipError("hipHostGetDevicePointer failed for the scalar read-back block");

@@ -51,19 +51,14 @@ struct VecStats { double sumsq, bad; };
 // One process per GPU (include/mgbhip.h, mgbhip_problem_set_collective): vectors live on this rank's unknowns with the
 // interface replicated, so every reduction runs over the entries the rank owns (mask) and is then summed over ranks.
 VecStats vec_stats(mgbhip_problem* P, int level, const double* d_v, int64_t len) {
-    hipStream_t st = P->stream();
-    launch_vec_stats(d_v, len, P->d_scratch.p, P->d_scal.p + 2, st, P->own_mask(level));
-    P->read_scalars(2, 2);
-    if (P->sharded()) P->allreduce_host(P->pin.d + 2, 2, 0);
-    return VecStats{P->pin.d[2], P->pin.d[3]};
+    launch_vec_stats(d_v, len, P->d_scratch.p, P->d_scal.p, RB_SUMSQ, P->stream(), P->own_mask(level));
+    const double* r = P->read_scalars(RB_SUMSQ, 2);
+    return VecStats{r[0], r[1]};
 }
 
 double dev_dot(mgbhip_problem* P, int level, const double* a, const double* b, int64_t len) {
-    hipStream_t st = P->stream();
-    launch_dot(a, b, len, P->d_scratch.p, P->d_scal.p + 4, st, P->own_mask(level));
-    P->read_scalars(4, 1);
-    if (P->sharded()) P->allreduce_host(P->pin.d + 4, 1, 0);
-    return P->pin.d[4];
+    launch_dot(a, b, len, P->d_scratch.p, P->d_scal.p, RB_GDOTV, P->stream(), P->own_mask(level));
+    return *P->read_scalars(RB_GDOTV, 1);
 }
 
 struct NewtonCtx {
@@ -114,21 +109,12 @@ bool trial_values(NewtonCtx& C, double& ynext, double& gnorm_next, int32_t* move
                                                    onfly ? &point : nullptr, (fused && fuse_restrict) ? &fuse : nullptr);
     if (restrict_fused_out) *restrict_fused_out = restrict_fused;
     if (onfly && !restrict_fused) launch_step(P->d_x.p, P->d_nv.p, *step, P->d_xn.p, C.m, P->d_flag.p, P->step_stamp, st);
-    const double seq = P->next_seq();
-    launch_trial_finish(P->d_gn.p, C.m, P->d_scratch.p, fused ? P->d_partials.p : nullptr, elem_grid(P->p, P->N), P->d_scal.p,
-                        P->d_flag.p, P->pin.dev, st, P->own_mask(C.level), seq, restrict_fused);
-    P->wait_results(seq);
-    P->pin.i[0] = P->pin.d[4] == (double)P->step_stamp ? 1 : 0;      // the stamp of the step kernel that formed this trial point
-    if (P->sharded()) {              // value, |g|^2, non-finite count and the "moved" flag in one sum over ranks
-        P->pin.d[1] = (double)P->pin.i[0];
-        P->allreduce_host(P->pin.d, 4, 0);
-        P->pin.i[0] = P->pin.d[1] != 0.0 ? 1 : 0;
-    }
-    if (moved) *moved = P->pin.i[0];
-    ynext = P->pin.d[0];
+    const TrialReadback r = P->finish_trial(C.level, P->d_gn.p, fused, restrict_fused);
+    if (moved) *moved = r.moved ? 1 : 0;
+    ynext = r.value;
     if (!std::isfinite(ynext)) return false;
-    if (P->pin.d[3] != 0.0 || !std::isfinite(P->pin.d[2])) return false;
-    gnorm_next = std::sqrt(P->pin.d[2]);
+    if (r.bad != 0.0 || !std::isfinite(r.sumsq)) return false;
+    gnorm_next = std::sqrt(r.sumsq);
     return true;
 }
 
@@ -137,8 +123,6 @@ bool trial_values(NewtonCtx& C, double& ynext, double& gnorm_next, int32_t* move
 // trial was ever evaluated successfully (then x, y, g stay as they were).
 bool linesearch_backtracking(NewtonCtx& C, const mgbhip_options& opt, double y, double inc, double& ynext,
                              double& gnorm_next) {
-    mgbhip_problem* P = C.P;
-    hipStream_t st = P->stream();
     double s = 1.0;
     bool have = false;
     while (s > 0.0) {
@@ -172,7 +156,6 @@ bool linesearch_illinois(NewtonCtx& C, const mgbhip_options& opt, double inc, do
         return v;
     };
     double s = 1.0;
-    bool have = false;
     while (s > 0.0) {
         try {
             // illinois(phi, 0, s; fa = inc)
@@ -199,7 +182,7 @@ bool linesearch_illinois(NewtonCtx& C, const mgbhip_options& opt, double inc, do
         }
         s *= opt.ls_beta;
     }
-    return have;
+    return false;
 }
 
 NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, int maxit) {
@@ -217,13 +200,10 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
     VecStats gs;
     if (!split_start && !P->dense && !P->sharded() && opt.line_search != 1) {
         P->eval_f01_launch(C.level, P->d_x.p, C.d_zJ, C.d_c, P->d_g.p, nullptr, true);
-        const double seq = P->next_seq();
-        launch_trial_finish(P->d_g.p, C.m, P->d_scratch.p, P->d_partials.p, elem_grid(P->p, P->N), P->d_scal.p, P->d_flag.p,
-                            P->pin.dev, st, P->own_mask(C.level), seq);
-        P->wait_results(seq);
-        y = P->pin.d[0];
+        const TrialReadback r = P->finish_trial(C.level, P->d_g.p, true, false);
+        y = r.value;
         if (!std::isfinite(y)) throw InvalidArgument("newton: initial objective value is not finite");
-        gs = VecStats{P->pin.d[2], P->pin.d[3]};
+        gs = VecStats{r.sumsq, r.bad};
     } else {
         y = C.F0(P->d_x.p);
         if (!std::isfinite(y)) throw InvalidArgument("newton: initial objective value is not finite");
@@ -248,36 +228,26 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
         C.F2(P->d_x.p);
         auto t0 = std::chrono::steady_clock::now();
         int fstatus = MGBHIP_OK;
-        int leaf_flag = 0;
+        bool leaf_flag = false;
+        DirReadback dir{};
         for (int attempt = 0; attempt < 2; ++attempt) {
             P->factor(C.level, C.rhs_of_g(), P->d_nv.p);    // the gradient rides along: no forward sweep afterwards
             P->trisolve_carried(C.level, P->d_nv.p);
             // pivot flags, direction statistics and lambda^2 = <g, n> in one round trip: the finishing launch stores them in
-            // the pinned block and clears the solver's flags for the next factorization (no copy / memset launches)
-            const double seq = P->next_seq();
-            launch_dir_finish(P->d_nv.p, P->d_g.p, C.m, P->d_scratch.p, P->d_scal.p, L.solver.status_flags_rw(), P->pin.dev, st,
-                              P->own_mask(C.level), seq);
-            L.solver.flags_cleared();
-            P->wait_results(seq);
-            P->pin.i[1] = P->pin.d[5] != 0.0 ? 1 : 0;
-            leaf_flag |= P->pin.d[6] != 0.0 ? 1 : 0;        // the condensed leaves are not re-formed by a refactorization: their flag sticks
-            P->pin.i[2] = leaf_flag;
-            fstatus = MfSolver::status_from(P->pin.i + 1, L.solver.factored_condensed);
-            if (P->sharded()) {          // every rank must take the same branch: the pivot flag travels with the sums
-                P->pin.d[5] = fstatus != MGBHIP_OK ? 1.0 : 0.0;
-                P->allreduce_host(P->pin.d + 2, 4, 0);
-                fstatus = P->pin.d[5] != 0.0 ? MGBHIP_ERR_NOT_SPD : MGBHIP_OK;
-            }
+            // the pinned block and clears the solver's flags for the next factorization (no copy / memset launches).
+            // The condensed leaves are not re-formed by a refactorization: their flag sticks, and the status counts it
+            dir = P->finish_direction(C.level, leaf_flag, &fstatus);
+            leaf_flag = leaf_flag || dir.leaf;
             // The fast large-front kernels apply inverted 32 x 32 diagonal blocks; near the edge of singularity
             // that loses digits a substitution keeps.  A failed pivot, a non-finite direction or lambda^2 <= 0
             // is re-done once with the substitution kernels before the reference's own tests see it.
             // (lambda^2 <= 0 within EPS * max(|y|, 1) is the reference's legitimate round-off-floor exit, src/newton.jl:257-271)
-            const bool at_floor = std::fabs(P->pin.d[4]) <= EPS * std::fmax(std::fabs(y), 1.0);
-            const bool suspicious = fstatus != MGBHIP_OK || P->pin.d[3] != 0.0 || !std::isfinite(P->pin.d[2]) ||
-                                    (!(P->pin.d[4] > 0) && !at_floor);
+            const bool at_floor = std::fabs(dir.gdotv) <= EPS * std::fmax(std::fabs(y), 1.0);
+            const bool suspicious = fstatus != MGBHIP_OK || dir.bad != 0.0 || !std::isfinite(dir.sumsq) ||
+                                    (!(dir.gdotv > 0) && !at_floor);
             if (!suspicious || attempt == 1 || !L.solver.has_inverse_path() || L.solver.robust) break;
             DBG("newton[lev %d] k=%d: direction rejected (status %d, lambda^2=%.3e): refactoring with the substitution kernels\n",
-                C.level, k, fstatus, P->pin.d[4]);
+                C.level, k, fstatus, dir.gdotv);
             L.solver.robust = true;
             L.H.drop_factors();
         }
@@ -287,11 +257,8 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
             // dense partially pivoted LU on the device, for systems small enough to be held densely.  The reference's own
             // tests (non-finite direction, lambda^2 <= 0) then see that direction.
             DBG("newton[lev %d] k=%d: LDL' met a zero pivot; direction from the pivoted LU fallback\n", C.level, k);
-            launch_dir_finish(P->d_nv.p, P->d_g.p, C.m, P->d_scratch.p, P->d_scal.p, L.solver.status_flags_rw(), P->pin.dev, st,
-                              P->own_mask(C.level));
-            L.solver.flags_cleared();
-            MGB_HIP_CHECK(hipStreamSynchronize(st));
-            fstatus = MGBHIP_OK;
+            dir = P->finish_direction(C.level, false, &fstatus);
+            fstatus = MGBHIP_OK;              // the flags it read are those the LDL' left behind
         }
         P->cnt.solve_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (fstatus != MGBHIP_OK) {
@@ -301,8 +268,8 @@ NewtonResult newton(NewtonCtx& C, const mgbhip_options& opt, const Stop& stop, i
             converged = false;
             break;
         }
-        if (P->pin.d[3] != 0.0 || !std::isfinite(P->pin.d[2])) throw InvalidArgument("newton: Newton direction has non-finite entries");
-        const double inc = P->pin.d[4];
+        if (dir.bad != 0.0 || !std::isfinite(dir.sumsq)) throw InvalidArgument("newton: Newton direction has non-finite entries");
+        const double inc = dir.gdotv;
         DBG("newton[lev %d] k=%d y=%.17g |g|=%.6e lambda^2=%.6e\n", C.level, k, y, gnorm, inc);
         if (inc <= 0) {
             converged = std::fabs(inc) <= EPS * std::fmax(std::fabs(y), 1.0);   // src/newton.jl:257-271

@@ -98,19 +98,15 @@ void launch_elem(const ElemParams& P, int mode, hipStream_t st);
 
 // deterministic two-stage reductions into a device scalar block
 void launch_reduce_partials(const double* partials, int64_t count, double* out, hipStream_t st);
-// stats[0] = sum v^2, stats[1] = number of non-finite entries (as double)
+// block[slot] = sum v^2, block[slot + 1] = number of non-finite entries (as double); launch_dot: block[slot] = a.b
 // mask (optional, domain decomposition): weights of the sums, 1 on the entries this rank owns and 0 elsewhere
-// ints (optional): nints device flags copied behind the sums as doubles (stats[2 ..] / stats3[3 ..]): one read-back for all
-void launch_vec_stats(const double* v, int64_t n, double* scratch, double* stats, hipStream_t st, const double* mask = nullptr,
-                      const int32_t* ints = nullptr, int nints = 0);
-// stats3 = [sum v*v, count of non-finite v, g.v] in one pass (values identical to launch_vec_stats + launch_dot)
-void launch_dir_stats(const double* v, const double* g, int64_t n, double* scratch, double* stats3, hipStream_t st,
-                      const double* mask = nullptr, const int32_t* ints = nullptr, int nints = 0);
-void launch_dot(const double* a, const double* b, int64_t n, double* scratch, double* out, hipStream_t st, const double* mask = nullptr);
+void launch_vec_stats(const double* v, int64_t n, double* scratch, double* block, int32_t slot, hipStream_t st,
+                      const double* mask = nullptr);
+void launch_dot(const double* a, const double* b, int64_t n, double* scratch, double* block, int32_t slot, hipStream_t st,
+                const double* mask = nullptr);
 // The two read-backs of a Newton iteration, each ONE finishing launch that also writes the pinned host block `host`
-// (device-visible pointer of a hipHostMalloc block; same slot indices as `scal`) -- no copy launch, no memset launch:
-//   direction: scal[2] = sum v^2, [3] = non-finite count of v, [4] = g.v, [5], [6] = status2[0..1] (read, then cleared)
-//   trial:     scal[0] = sum of f0_partials (nullptr: scal[0] is already final), [2] = sum g^2, [3] = non-finite count, [4] = *moved
+// (device-visible pointer of a hipHostMalloc block; same slot indices as `scal`) -- no copy launch, no memset launch.
+// The slots of both layouts: readback.hpp.
 // restriction + |g|^2 partials (+ the line-search step when xn != nullptr) in one launch; scratch gets the partial sums in the layout
 // launch_trial_finish(partials_ready = true) reads
 void launch_restrict_trial(int64_t rows, const int32_t* ptr, const int32_t* col, const double* val, const double* ret, double* g,

@@ -563,11 +563,8 @@ void mgbhip_problem::eval_f0_launch(int level, const double* d_s, const double* 
 }
 
 double mgbhip_problem::eval_f0(int level, const double* d_s, const double* d_zz, const double* d_cc) {
-    hipStream_t st = stream();
     eval_f0_launch(level, d_s, d_zz, d_cc);
-    read_scalars(0, 1);
-    if (sharded()) allreduce_host(pin.d, 1, 0);
-    return pin.d[0];
+    return *read_scalars(RB_VALUE, 1);
 }
 
 void mgbhip_problem::allreduce_host(double* h, int64_t count, int op) {
@@ -775,7 +772,7 @@ void mgbhip_problem::wait_results(double seq) {
     static const bool poll = !env_on("MGBHIP_NO_POLL");
     hipStream_t st = stream();
     if (poll && seq != 0.0) {
-        volatile const double* stamp = pin.d + 15;
+        volatile const double* stamp = pin.d + RB_STAMP;
         const Stopwatch sw;
         for (int spins = 0;; ++spins) {
             if (__atomic_load_n(reinterpret_cast<const volatile uint64_t*>(stamp), __ATOMIC_ACQUIRE) ==
@@ -788,10 +785,46 @@ void mgbhip_problem::wait_results(double seq) {
     MGB_HIP_CHECK(hipStreamSynchronize(st));
 }
 
-void mgbhip_problem::read_scalars(int lo, int n) {
+const double* mgbhip_problem::read_scalars(int lo, int n) {
     const double seq = next_seq();
     launch_publish(d_scal.p + lo, n, pin.dev, lo, seq, stream());
     wait_results(seq);
+    if (sharded()) allreduce_host(pin.d + lo, n, 0);
+    return pin.d + lo;
+}
+
+TrialReadback mgbhip_problem::finish_trial(int level, const double* d_grad, bool f0_partials, bool partials_ready) {
+    const double seq = next_seq();
+    launch_trial_finish(d_grad, levels[level].m, d_scratch.p, f0_partials ? d_partials.p : nullptr, elem_grid(p, N), d_scal.p,
+                        d_flag.p, pin.dev, stream(), own_mask(level), seq, partials_ready);
+    wait_results(seq);
+    TrialReadback r = decode_trial(pin.d, step_stamp);      // the stamp of the step kernel that formed this trial point
+    if (sharded()) {              // value, |g|^2, non-finite count and the "moved" flag in one sum over ranks
+        double s[RB_SHARD];
+        pack_trial(r, s);
+        allreduce_host(s, RB_SHARD, 0);
+        r = unpack_trial(s);
+    }
+    return r;
+}
+
+DirReadback mgbhip_problem::finish_direction(int level, bool leaf_before, int* status) {
+    MfSolver& solver = levels[level].solver;
+    const double seq = next_seq();
+    launch_dir_finish(d_nv.p, d_g.p, levels[level].m, d_scratch.p, d_scal.p, solver.status_flags_rw(), pin.dev, stream(),
+                      own_mask(level), seq);
+    solver.flags_cleared();
+    wait_results(seq);
+    DirReadback r = decode_direction(pin.d);
+    const int32_t flags2[2] = {r.pivot ? 1 : 0, (leaf_before || r.leaf) ? 1 : 0};
+    *status = MfSolver::status_from(flags2, solver.factored_condensed);
+    if (sharded()) {              // every rank must take the same branch: the status travels with the sums
+        double s[RB_SHARD];
+        pack_direction(r, *status != MGBHIP_OK, s);
+        allreduce_host(s, RB_SHARD, 0);
+        *status = unpack_direction(s, r) ? MGBHIP_ERR_NOT_SPD : MGBHIP_OK;
+    }
+    return r;
 }
 
 bool mgbhip_problem::can_fuse_step(int level) const {

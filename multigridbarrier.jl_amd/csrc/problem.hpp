@@ -173,8 +173,17 @@ struct mgbhip_problem {
     void wait_results(double seq);
     // fused line-search step (driver.cpp: trial_values): levels whose element kernel can form a trial point on the fly
     bool can_fuse_step(int level) const;
-    // d_scal[lo .. lo + n) -> pin.d[lo .. lo + n), awaited (publish kernel + polled stamp)
-    void read_scalars(int lo, int n);
+    // d_scal[lo .. lo + n) -> the pinned block, awaited (publish kernel + polled stamp) and summed over the ranks of a sharded
+    // problem; returns the host's slot lo (valid until the next read-back)
+    const double* read_scalars(int lo, int n);
+    // The two read-backs of a Newton iteration (slots and records: readback.hpp), each one finishing launch, one wait and, on
+    // a sharded problem, one allreduce of 4 doubles.
+    // Trial: d_grad = the trial point's gradient on `level`; f0_partials: the element kernel left its workgroup partials of
+    // f0 in d_partials (else d_scal[RB_VALUE] is final); partials_ready: a fused restriction left those of |g|^2 in d_scratch
+    mgbhip::TrialReadback finish_trial(int level, const double* d_grad, bool f0_partials, bool partials_ready);
+    // Direction d_nv against the gradient d_g.  *status = the factorization's (MfSolver::status_from on the pivot flag and
+    // leaf_before || the leaf flag), on a sharded problem a failure on any rank; the solver's device flags are left cleared
+    mgbhip::DirReadback finish_direction(int level, bool leaf_before, int* status);
     double result_seq = 0.0;
     std::mutex shared_mutex;               // prepare_all: state of the problem (not of one level) touched while levels are planned side by side
     bool prepared = false;

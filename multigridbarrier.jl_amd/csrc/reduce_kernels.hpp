@@ -133,24 +133,7 @@ __global__ __launch_bounds__(256) void dir_stats_kernel(const double* __restrict
     }
 }
 
-// Second stage of every two-stage reduction, ONE launch for everything the host wants from one synchronisation:
-// up to four strided sums (each: 256 threads stride over the partials + the same LDS tree as before, so the values
-// are bit for bit those of the separate reduce_partials / reduce2 launches this replaces), device flags that ride
-// behind the sums as doubles (a pivot status, the step kernel's "moved" stamp; `reset` clears them for their next
-// producer: no hipMemsetAsync per Newton iteration), and a copy of out[host_lo .. host_lo + host_n) straight into
-// the pinned host block (host-coherent memory: visible after the stream synchronises; no copy launch).
-struct FinishJob { const double* src; int64_t count; int32_t out; };
-struct FinishParams {
-    FinishJob job[4];
-    int32_t njobs;
-    double* out;
-    int32_t* ints;
-    int32_t nints, ints_out, reset;
-    double* host;
-    int32_t host_lo, host_n;
-    double seq;                  // != 0: written to host[15] after the results (system-scope fence in between): the host polls it
-};
-// The jobs of one finishing launch do not depend on each other, and almost none of the kernel's time is bandwidth: it is one
+// The finishing launch (FinishParams: readback.hpp).  Its jobs do not depend on each other, and almost none of the kernel's time is bandwidth: it is one
 // dependent memory latency per rolled `s += src[i]` and ten barriers per job.  So: the partials of ALL jobs are requested
 // before the first addition (U loads per job in flight, larger counts in chunks of 256 U), and the jobs' LDS trees run side
 // by side, one barrier per level.  Per job every thread still forms s = 0.0; s += src[tid]; s += src[tid + 256]; ... in
@@ -160,7 +143,7 @@ constexpr int FINISH_LOADS_IN_FLIGHT = 8;       // 8 and 16 measure the same at 
 template <int U>
 __global__ __launch_bounds__(256) void finish_kernel(const FinishParams P) {
     __shared__ double red[4][256];
-    __shared__ double res[16];
+    __shared__ double res[RB_SLOTS];
     const int tid = threadIdx.x;
     if (tid < P.nints) {
         res[P.ints_out + tid] = (double)P.ints[tid];
@@ -217,7 +200,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const FinishParams P) {
     }
     __syncthreads();
     // results -> device scalar block (every slot this launch produced) and -> host
-    if (tid < 16) {
+    if (tid < RB_SLOTS) {
         bool mine = false;
         for (int o = 0; o < P.njobs; ++o) mine = mine || (P.job[o].out == tid);
         if (tid >= P.ints_out && tid < P.ints_out + P.nints) mine = true;
@@ -228,7 +211,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const FinishParams P) {
         __threadfence_system();                      // this thread's result stores are visible to the host ...
         __syncthreads();                             // ... for every writing thread, before the stamp
         if (tid == 0) {
-            __hip_atomic_store(P.host + 15, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(P.host + RB_STAMP, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
@@ -236,7 +219,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const FinishParams P) {
 // The jobs one after another (MGBHIP_FINISH_SERIAL=1): the kernel finish_kernel<U> is held to, bit for bit.
 __global__ __launch_bounds__(256) void finish_serial_kernel(const FinishParams P) {
     __shared__ double red[256];
-    __shared__ double res[16];
+    __shared__ double res[RB_SLOTS];
     const int tid = threadIdx.x;
     if (tid < P.nints) {
         res[P.ints_out + tid] = (double)P.ints[tid];
@@ -258,7 +241,7 @@ __global__ __launch_bounds__(256) void finish_serial_kernel(const FinishParams P
     }
     __syncthreads();
     // results -> device scalar block (every slot this launch produced) and -> host
-    if (tid < 16) {
+    if (tid < RB_SLOTS) {
         bool mine = false;
         for (int o = 0; o < P.njobs; ++o) mine = mine || (P.job[o].out == tid);
         if (tid >= P.ints_out && tid < P.ints_out + P.nints) mine = true;
@@ -269,7 +252,7 @@ __global__ __launch_bounds__(256) void finish_serial_kernel(const FinishParams P
         __threadfence_system();                      // this thread's result stores are visible to the host ...
         __syncthreads();                             // ... for every writing thread, before the stamp
         if (tid == 0) {
-            __hip_atomic_store(P.host + 15, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(P.host + RB_STAMP, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
@@ -292,37 +275,21 @@ static void launch_finish(const FinishParams& F, hipStream_t st) {
     MGB_HIP_CHECK(hipGetLastError());
 }
 
-void launch_vec_stats(const double* v, int64_t n, double* scratch, double* stats, hipStream_t st, const double* mask,
-                      const int32_t* ints, int nints) {
+// stats: block[slot] = sum v^2, block[slot + 1] = count of non-finite v
+void launch_vec_stats(const double* v, int64_t n, double* scratch, double* block, int32_t slot, hipStream_t st, const double* mask) {
     const int nb = reduce_blocks(n);
     hipLaunchKernelGGL(block_reduce_kernel<1>, dim3(nb), dim3(256), 0, st, v, (const double*)nullptr, n, scratch, mask);
-    FinishParams F{};
-    F.job[0] = FinishJob{scratch, nb, 0};
-    F.job[1] = FinishJob{scratch + nb, nb, 1};
-    F.njobs = 2;
-    F.out = stats;
-    F.ints = const_cast<int32_t*>(ints); F.nints = nints; F.ints_out = 2; F.reset = 0;
-    launch_finish(F, st);
+    launch_finish(finish_plain(scratch, nb, 2, block, slot), st);
 }
 
-void launch_dir_stats(const double* v, const double* g, int64_t n, double* scratch, double* stats3, hipStream_t st,
-                      const double* mask, const int32_t* ints, int nints) {
+void launch_dot(const double* a, const double* b, int64_t n, double* scratch, double* block, int32_t slot, hipStream_t st,
+                const double* mask) {
     const int nb = reduce_blocks(n);
-    hipLaunchKernelGGL(dir_stats_kernel, dim3(nb), dim3(256), 0, st, v, g, n, scratch, mask);
-    FinishParams F{};
-    F.job[0] = FinishJob{scratch, nb, 0};
-    F.job[1] = FinishJob{scratch + nb, nb, 1};
-    F.job[2] = FinishJob{scratch + 2 * nb, nb, 2};
-    F.njobs = 3;
-    F.out = stats3;
-    F.ints = const_cast<int32_t*>(ints); F.nints = nints; F.ints_out = 3; F.reset = 0;
-    launch_finish(F, st);
+    hipLaunchKernelGGL(block_reduce_kernel<0>, dim3(nb), dim3(256), 0, st, a, b, n, scratch, mask);
+    launch_finish(finish_plain(scratch, nb, 1, block, slot), st);
 }
 
-// The Newton direction's read-back in one finishing launch: scal[2] = sum v^2, scal[3] = non-finite count, scal[4] = g.v,
-// scal[5], scal[6] = the solver's status flags (read AND cleared: the next factorization / condensing f2 finds them zero
-// without a memset launch); scal[2..7) also lands in the pinned host block `host` (same indices).
-// n <= 16 scalars of the device block to the pinned host block (through its device pointer) with the sequence stamp behind
+// n <= RB_SLOTS scalars of the device block to the pinned host block (through its device pointer) with the sequence stamp behind
 // them: what a hipMemcpyAsync + hipStreamSynchronize pair did with a runtime copy kernel (11 us) and the runtime's wait.
 __global__ void publish_kernel(const double* __restrict__ src, int n, double* __restrict__ host, double* __restrict__ stamp, double seq) {
     const int tid = threadIdx.x;
@@ -333,54 +300,24 @@ __global__ void publish_kernel(const double* __restrict__ src, int n, double* __
 }
 
 void launch_publish(const double* src, int n, double* host_block, int host_lo, double seq, hipStream_t st) {
-    // host_block: device pointer of the 16-double pinned block; the stamp always goes to its slot 15
-    hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, st, src, n, host_block + host_lo, host_block + 15, seq);
+    // host_block: device pointer of the pinned block
+    hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, st, src, n, host_block + host_lo, host_block + RB_STAMP, seq);
     MGB_HIP_CHECK(hipGetLastError());
 }
 
+// The two read-backs of a Newton iteration (slots: readback.hpp, finish_direction_params / finish_trial_params)
 void launch_dir_finish(const double* v, const double* g, int64_t n, double* scratch, double* scal, int32_t* status2, double* host,
                        hipStream_t st, const double* mask, double seq) {
     const int nb = reduce_blocks(n);
     hipLaunchKernelGGL(dir_stats_kernel, dim3(nb), dim3(256), 0, st, v, g, n, scratch, mask);
-    FinishParams F{};
-    F.job[0] = FinishJob{scratch, nb, 2};
-    F.job[1] = FinishJob{scratch + nb, nb, 3};
-    F.job[2] = FinishJob{scratch + 2 * nb, nb, 4};
-    F.njobs = 3;
-    F.out = scal;
-    F.ints = status2; F.nints = 2; F.ints_out = 5; F.reset = 1;
-    F.host = host; F.host_lo = 2; F.host_n = 5;
-    F.seq = seq;
-    launch_finish(F, st);
+    launch_finish(finish_direction_params(scratch, nb, scal, status2, host, seq), st);
 }
 
-// One line-search trial's read-back: scal[0] = f0 (sum of the element kernel's workgroup partials), scal[2] = |g|^2,
-// scal[3] = non-finite count of g, scal[4] = the step kernel's "moved" stamp; scal[0..5) -> host.
 void launch_trial_finish(const double* g, int64_t n, double* scratch, const double* f0_partials, int64_t f0_count, double* scal,
                          int32_t* moved, double* host, hipStream_t st, const double* mask, double seq, bool partials_ready) {
     const int nb = reduce_blocks(n);
     if (!partials_ready) hipLaunchKernelGGL(block_reduce_kernel<1>, dim3(nb), dim3(256), 0, st, g, (const double*)nullptr, n, scratch, mask);
-    FinishParams F{};
-    int nj = 0;
-    if (f0_partials) F.job[nj++] = FinishJob{f0_partials, f0_count, 0};
-    F.job[nj++] = FinishJob{scratch, nb, 2};
-    F.job[nj++] = FinishJob{scratch + nb, nb, 3};
-    F.njobs = nj;
-    F.out = scal;
-    F.ints = moved; F.nints = 1; F.ints_out = 4; F.reset = 0;
-    F.host = host; F.host_lo = 0; F.host_n = 5;
-    F.seq = seq;
-    launch_finish(F, st);
-}
-
-void launch_dot(const double* a, const double* b, int64_t n, double* scratch, double* out, hipStream_t st, const double* mask) {
-    const int nb = reduce_blocks(n);
-    hipLaunchKernelGGL(block_reduce_kernel<0>, dim3(nb), dim3(256), 0, st, a, b, n, scratch, mask);
-    FinishParams F{};
-    F.job[0] = FinishJob{scratch, nb, 0};
-    F.njobs = 1;
-    F.out = out;
-    launch_finish(F, st);
+    launch_finish(finish_trial_params(f0_partials, f0_count, scratch, nb, scal, moved, host, seq), st);
 }
 
 void launch_restrict_trial(int64_t rows, const int32_t* ptr, const int32_t* col, const double* val, const double* ret, double* g,
