@@ -1,7 +1,8 @@
 // mf_big_inv.hpp -- large fronts, inverse-based generation (fronts with lds_cap < m <= BIG_INV_MAX_M): the MFMA step
-// kernel mf_big_step, the block-0 kernel mf_big_diag0, the gathering assembly mf_big_gather (and mf_big_gather_lds), the triangle pack of the
-// interface front (mf_tri_pack) and the single-workgroup solves mf_fwd_inv / mf_bwd_inv (mf_bwd_inv_split: the boundary product
-// of a backward launch of few fronts shared among several workgroups per front).
+// kernel mf_big_step, the block-0 kernel mf_big_diag0 with the block-0 tail and the slot format it shares with the gathering
+// assembly (mf_big_assemble.hpp), the triangle pack of the interface front (mf_tri_pack) and the single-workgroup solves
+// mf_fwd_inv / mf_bwd_inv (mf_bwd_inv_split: the boundary product of a backward launch of few fronts shared among several
+// workgroups per front).
 //
 // One launch per 32-column step.  The diagonal block of step j is factored AND inverted ahead of
 // time by the look-ahead workgroup of step j-1 (W_j = L_jj^{-1}, d_j); every trailing tile then
@@ -16,7 +17,6 @@
 // the lower triangle keeps the unfactored block (sibling workgroups of step 0 still read it).
 #pragma once
 #include "mf_device.hpp"
-#include "mf_big_subst.hpp"     // launch_big_assemble falls back on the column-tiled assembly
 
 namespace mgbhip {
 namespace {
@@ -33,6 +33,21 @@ __device__ __forceinline__ void block_ldlt32(double (*Dn)[NB + 1], double* dq, i
 }
 __device__ __forceinline__ void block_inverse32_sel(const double (*Ls)[NB + 1], double (*Wv)[NB + 1], double (*Tm)[17], int tid) {
     block_inverse32_mfma(Ls, Wv, Tm, tid);
+}
+
+// A factored diagonal block travels between launches in a `dscr` slot of NB x NB doubles: column-major, stride NB, the
+// pivots d on the diagonal and W = L^{-1} strictly below it; the upper triangle is never touched.
+// Block 0 of a front's pivot chain, assembled in Dn (lower triangle, published by a barrier): factor it, invert the
+// factor, leave d / W in `slot`.  256 threads (mf_big_diag0 and the block-0 workgroup of mf_big_gather, mf_big_assemble.hpp;
+// mf_big_step keeps its own text of the same three phases and of the slot's decoding: profiles/gather_merge_isa.txt).
+__device__ __forceinline__ void block0_to_slot(double (*Dn)[NB + 1], double (*Wv)[NB + 1], double (*Tm)[17], double* dq, int nb,
+                                               int tid, int32_t* __restrict__ status, double* __restrict__ slot) {
+    block_ldlt32(Dn, dq, nb, tid, status);
+    block_inverse32_sel(Dn, Wv, Tm, tid);
+    for (int i = tid; i < NB * NB; i += 256) {
+        const int rr = i % NB, c = i / NB;
+        if (rr >= c && rr < nb) slot[rr + NB * c] = (rr == c) ? dq[rr] : Wv[rr][c];
+    }
 }
 
 // S = A W' for a 64-row slice held raw in P[c][rr] (LDS, overwritten in place); wave w owns rows
@@ -144,7 +159,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
         block_ldlt32(Dn, dq, nb, tid, is_la ? status : nullptr);
         block_inverse32_sel(Dn, Wv, Tm, tid);
     } else {
-        for (int i = tid; i < NB * NB; i += 256) {
+        for (int i = tid; i < NB * NB; i += 256) {        // the slot format of block0_to_slot, read back
             const int rr = i % NB, c = i / NB;
             const double v = (rr >= c && rr < nb) ? slot[rr + NB * c] : 0.0;
             Wv[rr][c] = (rr > c) ? v : (rr == c ? 1.0 : 0.0);
@@ -242,7 +257,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
         PROBE(5);
         block_inverse32_sel(Dn, Wv, Tm, tid);
         PROBE(6);
-        for (int i = tid; i < NB * NB; i += 256) {        // slot: diagonal d, strictly lower W (column-major)
+        for (int i = tid; i < NB * NB; i += 256) {        // block0_to_slot's store (its phases written out: the probe stamps each)
             const int rr = i % NB, c = i / NB;
             if (rr >= c && rr < nbn) nslot[rr + NB * c] = (rr == c) ? dq[rr] : Wv[rr][c];
         }
@@ -332,317 +347,7 @@ __global__ __launch_bounds__(256) void mf_big_diag0(const FrontDev* __restrict__
         Dn[rr][c] = (rr >= c && rr < nb) ? W[rr + (int64_t)c * m] : 0.0;
     }
     __syncthreads();
-    block_ldlt32(Dn, dq, nb, tid, status);
-    block_inverse32_sel(Dn, Wv, Tm, tid);
-    double* slot = dscr + (int64_t)blockIdx.x * 2 * (NB * NB);
-    for (int i = tid; i < NB * NB; i += 256) {
-        const int rr = i % NB, c = i / NB;
-        if (rr >= c && rr < nb) slot[rr + NB * c] = (rr == c) ? dq[rr] : Wv[rr][c];
-    }
-}
-
-// Gather form of the assembly for fronts with few children (every front of a nested-dissection tree above the
-// leaves has two to four).  The inverse of every child's relative index list -- for each front row its position in the
-// child's update block, or -1 -- and the children's update-block addresses are static gather maps, laid out once by
-// analyze() (build_gather_maps, mf_launch_plan.hpp): a workgroup copies the rows it needs into LDS, coalesced, where it
-// used to rebuild the whole table there behind a chain of four dependent loads, a fill pass and two barriers (reading the
-// maps from global memory inside the row loop instead was slower than that: DESIGN.md section 4).  `ct` destination
-// columns per workgroup: big_gather_ct.  Each destination entry is formed ONCE
-// in a register -- the children's entries that land on it, added in child order, all their loads in flight together --
-// and stored once.  No zero pass, no read-modify-write of the arena, and the dependent-load chains of the children run
-// side by side instead of one child after the other.
-__global__ __launch_bounds__(256) void mf_big_gather(const FrontDev* __restrict__ fr, int32_t first,
-                                                     const GatherRec* __restrict__ grec, const int32_t* __restrict__ gmap,
-                                                     const int32_t* __restrict__ a_src,
-                                                     const int32_t* __restrict__ a_dst,
-                                                     const int32_t* __restrict__ a_colptr,
-                                                     const double* __restrict__ Hval, double* __restrict__ arena,
-                                                     double* __restrict__ dscr, int32_t* __restrict__ status, int with_diag,
-                                                     int ct /* destination columns per workgroup */) {
-    const FrontDev F = fr[first + blockIdx.y];
-    const GatherRec G = grec[blockIdx.y];          // grec: the record of the launch's first front
-    const int m = F.m;
-    const int32_t* mp = gmap + G.map_off;          // [nchild][m]
-    if (with_diag && blockIdx.x == gridDim.x - 1) {
-        // One extra workgroup per front forms ONLY the first 32 x 32 diagonal block (same gather, same order as
-        // the column workgroups, which write it to the arena), factors and inverts it and leaves W_0 / d_0 in slot 0:
-        // step 0 of the factorization finds its diagonal block ready, as every later step does from the look-ahead
-        // workgroup.  Its time hides under the column workgroups of the same launch (was: a launch of its own for
-        // batches of many fronts, a redundant factorization inside every tile of step 0 for the others).
-        __shared__ double Wv[NB][NB + 1];
-        __shared__ double Dn[NB][NB + 1];
-        __shared__ double Tm[16][17];
-        __shared__ double dq[NB];
-        __shared__ int32_t inv0[GATHER_MAX_CHILD][NB];      // the maps' first 32 rows
-        const int tid = threadIdx.x, nch = F.nchild, nb = min(NB, F.k);
-        // the first batch of A entries of the block (cp -> a_dst / a_src -> Hval: three dependent loads) is requested
-        // beside the maps
-        int a_d0 = -1;
-        double a_v0 = 0.0;
-        const int a_end = (a_colptr + F.acol_off)[nb];
-        if (tid < a_end) {
-            a_d0 = a_dst[F.a_off + tid];
-            a_v0 = Hval[a_src[F.a_off + tid]];
-        }
-        {
-            const int ch = tid / NB, g = tid % NB;          // GATHER_MAX_CHILD * NB = 256 threads
-            inv0[ch][g] = (ch < nch && g < m) ? mp[(int64_t)ch * m + g] : -1;
-        }
-        __syncthreads();
-        for (int i = tid; i < NB * NB; i += 256) {
-            const int rr = i % NB, c = i / NB;
-            double v = 0.0;
-            if (rr >= c && rr < nb) {
-#pragma unroll
-                for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {        // child order: the summation order of the extend-add
-                    if (ch < nch) {
-                        const int jc = inv0[ch][c], ir = inv0[ch][rr];
-                        if (jc >= 0 && ir >= 0) v += arena[G.base[ch] + (int64_t)jc * G.ld[ch] + ir];
-                    }
-                }
-            }
-            Dn[rr][c] = v;
-        }
-        __syncthreads();
-        {
-            const int32_t* ad = a_dst + F.a_off;
-            if (a_d0 >= 0) {
-                const int lu = a_d0 % m, lv = a_d0 / m;
-                if (lu < nb) Dn[lu][lv] += a_v0;
-            }
-            for (int t = tid + 256; t < a_end; t += 256) {
-                const int d = ad[t], lu = d % m, lv = d / m;
-                if (lu < nb) Dn[lu][lv] += Hval[a_src[F.a_off + t]];
-            }
-        }
-        __syncthreads();
-        block_ldlt32(Dn, dq, nb, tid, status);
-        block_inverse32_sel(Dn, Wv, Tm, tid);
-        double* slot = dscr + (int64_t)blockIdx.y * 2 * (NB * NB);
-        for (int i = tid; i < NB * NB; i += 256) {
-            const int rr = i % NB, c = i / NB;
-            if (rr >= c && rr < nb) slot[rr + NB * c] = (rr == c) ? dq[rr] : Wv[rr][c];
-        }
-        return;
-    }
-    const int c0 = blockIdx.x * ct;
-    if (c0 >= m) return;
-    const int c1 = min(c0 + ct, m);
-    double* W = arena + F.F_off;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;     // one wave per destination column, lanes on the rows
-    const int nch = F.nchild;
-    // A entries are grouped by pivot column: the per-column offsets give the range of [c0, c1).  Its first batch is
-    // requested now (cp -> a_dst / a_src -> Hval) and runs under the children's loads; it is added after their sums.
-    const int32_t* cp = a_colptr + F.acol_off;
-    const int32_t* ad = a_dst + F.a_off;
-    const int a_beg = cp[min(c0, F.k)], a_end = cp[min(c1, F.k)];
-    int a_d0 = -1;
-    double a_v0 = 0.0;
-    if (a_beg + tid < a_end) {
-        a_d0 = ad[a_beg + tid];
-        a_v0 = Hval[a_src[F.a_off + a_beg + tid]];
-    }
-    // rows c0 .. m - 1 of every child's map (the lower triangle below column c0 needs no others), one coalesced copy,
-    // the children's loads in flight together
-    extern __shared__ int32_t inv[];               // [nchild][m - c0]
-    const int istride = m - c0;
-    for (int r = tid; r < istride; r += 256) {
-        int32_t t[GATHER_MAX_CHILD];
-#pragma unroll
-        for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) t[ch] = ch < nch ? mp[(int64_t)ch * m + c0 + r] : -1;
-#pragma unroll
-        for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch)
-            if (ch < nch) inv[ch * istride + r] = t[ch];
-    }
-    __syncthreads();
-    for (int c = c0 + wave; c < c1; c += 4) {
-        double* Wc = W + (int64_t)c * m;
-        int64_t colbase[GATHER_MAX_CHILD];         // child column offset, -1 when the child does not reach column c
-#pragma unroll
-        for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {
-            const int jc = ch < nch ? inv[ch * istride + c - c0] : -1;
-            colbase[ch] = jc >= 0 ? G.base[ch] + (int64_t)jc * G.ld[ch] : -1;
-        }
-        for (int r = c + lane; r < m; r += 128) {  // two rows per lane in flight (four: 2 % slower end to end, measured in round 4)
-            const int r1 = r + 64;
-            double u0[GATHER_MAX_CHILD], u1[GATHER_MAX_CHILD];
-#pragma unroll
-            for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {
-                u0[ch] = 0.0;
-                u1[ch] = 0.0;
-                if (colbase[ch] >= 0) {
-                    const int i0 = inv[ch * istride + r - c0];
-                    const int i1 = r1 < m ? inv[ch * istride + r1 - c0] : -1;
-                    if (i0 >= 0) u0[ch] = arena[colbase[ch] + i0];
-                    if (i1 >= 0) u1[ch] = arena[colbase[ch] + i1];
-                }
-            }
-            double v0 = 0.0, v1 = 0.0;
-#pragma unroll
-            for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {      // child order: the summation order of the extend-add
-                v0 += u0[ch];
-                v1 += u1[ch];
-            }
-            Wc[r] = v0;
-            if (r1 < m) Wc[r1] = v1;
-        }
-    }
-    __syncthreads();
-    if (a_d0 >= 0) W[a_d0] += a_v0;
-    for (int t = a_beg + tid + 256; t < a_end; t += 256) W[ad[t]] += Hval[a_src[F.a_off + t]];
-}
-
-// The same assembly with the index tables rebuilt in LDS by every workgroup of every launch, as before the static gather
-// maps (MGBHIP_GATHER_LDS_MAPS=1): the A/B lever of the maps and the bitwise reference of tests/test_gpu_gather_maps.py.
-__global__ __launch_bounds__(256) void mf_big_gather_lds(const FrontDev* __restrict__ fr, int32_t first,
-                                                     const int32_t* __restrict__ children,
-                                                     const int32_t* __restrict__ rel,
-                                                     const int32_t* __restrict__ a_src,
-                                                     const int32_t* __restrict__ a_dst,
-                                                     const int32_t* __restrict__ a_colptr,
-                                                     const double* __restrict__ Hval, double* __restrict__ arena, int mstride,
-                                                     double* __restrict__ dscr, int32_t* __restrict__ status, int with_diag,
-                                                     int ct /* destination columns per workgroup */) {
-    extern __shared__ int32_t inv[];               // [nchild][mstride]: position in the child's update block or -1
-    __shared__ int64_t cU[GATHER_MAX_CHILD];
-    __shared__ int64_t cR[GATHER_MAX_CHILD];
-    __shared__ int32_t cM[GATHER_MAX_CHILD], cB[GATHER_MAX_CHILD];
-    const FrontDev F = fr[first + blockIdx.y];
-    const int m = F.m;
-    if (with_diag && blockIdx.x == gridDim.x - 1) {
-        // One extra workgroup per front forms ONLY the first 32 x 32 diagonal block (same gather, same order as
-        // the column workgroups, which write it to the arena), factors and inverts it and leaves W_0 / d_0 in slot 0:
-        // step 0 of the factorization finds its diagonal block ready, as every later step does from the look-ahead
-        // workgroup.  Its time hides under the column workgroups of the same launch (was: a launch of its own for
-        // batches of many fronts, a redundant factorization inside every tile of step 0 for the others).
-        __shared__ double Wv[NB][NB + 1];
-        __shared__ double Dn[NB][NB + 1];
-        __shared__ double Tm[16][17];
-        __shared__ double dq[NB];
-            __shared__ int32_t inv0[GATHER_MAX_CHILD][NB];
-        const int tid = threadIdx.x, nch = F.nchild, nb = min(NB, F.k);
-        // the first batch of A entries of the block (cp -> a_dst / a_src -> Hval: three dependent loads) is requested before
-        // the children's chain (children -> descriptor -> rel -> arena: four more) instead of after it
-        int a_d0 = -1;
-        double a_v0 = 0.0;
-        const int a_end = (a_colptr + F.acol_off)[nb];
-        if (tid < a_end) {
-            a_d0 = a_dst[F.a_off + tid];
-            a_v0 = Hval[a_src[F.a_off + tid]];
-        }
-        if (tid < nch) {
-            const FrontDev C = fr[children[F.child_off + tid]];
-            cU[tid] = C.F_off + (int64_t)C.k * C.m + C.k;
-            cR[tid] = C.rel_off;
-            cM[tid] = C.m;
-            cB[tid] = C.m - C.k;
-        }
-        for (int i = tid; i < GATHER_MAX_CHILD * NB; i += 256) inv0[i / NB][i % NB] = -1;
-        __syncthreads();
-        for (int ch = 0; ch < nch; ++ch) {               // rel is increasing: only its first entries can be < 32
-            const int32_t* rl = rel + cR[ch];
-            const int lim = min(cB[ch], NB);
-            if (tid < lim) {
-                const int g = rl[tid];
-                if (g < NB) inv0[ch][g] = tid;
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < NB * NB; i += 256) {
-            const int rr = i % NB, c = i / NB;
-            double v = 0.0;
-            if (rr >= c && rr < nb) {
-                for (int ch = 0; ch < nch; ++ch) {        // child order: the summation order of the extend-add
-                    const int jc = inv0[ch][c], ir = inv0[ch][rr];
-                    if (jc >= 0 && ir >= 0) v += arena[cU[ch] + (int64_t)jc * cM[ch] + ir];
-                }
-            }
-            Dn[rr][c] = v;
-        }
-        __syncthreads();
-        {
-            const int32_t* ad = a_dst + F.a_off;
-            if (a_d0 >= 0) {
-                const int lu = a_d0 % m, lv = a_d0 / m;
-                if (lu < nb) Dn[lu][lv] += a_v0;
-            }
-            for (int t = tid + 256; t < a_end; t += 256) {
-                const int d = ad[t], lu = d % m, lv = d / m;
-                if (lu < nb) Dn[lu][lv] += Hval[a_src[F.a_off + t]];
-            }
-        }
-        __syncthreads();
-        block_ldlt32(Dn, dq, nb, tid, status);
-        block_inverse32_sel(Dn, Wv, Tm, tid);
-        double* slot = dscr + (int64_t)blockIdx.y * 2 * (NB * NB);
-        for (int i = tid; i < NB * NB; i += 256) {
-            const int rr = i % NB, c = i / NB;
-            if (rr >= c && rr < nb) slot[rr + NB * c] = (rr == c) ? dq[rr] : Wv[rr][c];
-        }
-        return;
-    }
-    const int c0 = blockIdx.x * ct;
-    if (c0 >= m) return;
-    const int c1 = min(c0 + ct, m);
-    double* W = arena + F.F_off;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;     // one wave per destination column, lanes on the rows
-    const int nch = F.nchild;
-    if (tid < nch) {
-        const FrontDev C = fr[children[F.child_off + tid]];
-        cU[tid] = C.F_off + (int64_t)C.k * C.m + C.k;
-        cR[tid] = C.rel_off;
-        cM[tid] = C.m;
-        cB[tid] = C.m - C.k;
-    }
-    for (int i = tid; i < nch * mstride; i += 256) inv[i] = -1;
-    __syncthreads();
-    for (int ch = 0; ch < nch; ++ch) {
-        const int32_t* rl = rel + cR[ch];
-        const int b = cB[ch];
-        for (int j = tid; j < b; j += 256) inv[ch * mstride + rl[j]] = j;
-    }
-    __syncthreads();
-    for (int c = c0 + wave; c < c1; c += 4) {
-        double* Wc = W + (int64_t)c * m;
-        int64_t colbase[GATHER_MAX_CHILD];         // child column offset, -1 when the child does not reach column c
-#pragma unroll
-        for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {
-            const int jc = ch < nch ? inv[ch * mstride + c] : -1;
-            colbase[ch] = jc >= 0 ? cU[ch] + (int64_t)jc * cM[ch] : -1;
-        }
-        for (int r = c + lane; r < m; r += 128) {  // two rows per lane in flight (four: 2 % slower end to end, measured in round 4)
-            const int r1 = r + 64;
-            double u0[GATHER_MAX_CHILD], u1[GATHER_MAX_CHILD];
-#pragma unroll
-            for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {
-                u0[ch] = 0.0;
-                u1[ch] = 0.0;
-                if (colbase[ch] >= 0) {
-                    const int i0 = inv[ch * mstride + r];
-                    const int i1 = r1 < m ? inv[ch * mstride + r1] : -1;
-                    if (i0 >= 0) u0[ch] = arena[colbase[ch] + i0];
-                    if (i1 >= 0) u1[ch] = arena[colbase[ch] + i1];
-                }
-            }
-            double v0 = 0.0, v1 = 0.0;
-#pragma unroll
-            for (int ch = 0; ch < GATHER_MAX_CHILD; ++ch) {      // child order: the summation order of the extend-add
-                v0 += u0[ch];
-                v1 += u1[ch];
-            }
-            Wc[r] = v0;
-            if (r1 < m) Wc[r1] = v1;
-        }
-    }
-    __syncthreads();
-    {   // A entries are grouped by pivot column: the per-column offsets give the range of [c0, c1)
-        const int32_t* cp = a_colptr + F.acol_off;
-        const int beg = cp[min(c0, F.k)], end = cp[min(c1, F.k)];
-        const int32_t* ad = a_dst + F.a_off;
-        for (int t = beg + tid; t < end; t += 256) W[ad[t]] += Hval[a_src[F.a_off + t]];
-    }
+    block0_to_slot(Dn, Wv, Tm, dq, nb, tid, status, dscr + (int64_t)blockIdx.x * 2 * (NB * NB));
 }
 
 // ---- triangular solves on the inverse-based layout: one workgroup per front --------------------
@@ -1027,29 +732,6 @@ __global__ __launch_bounds__(BIGI_THREADS) void mf_bwd_inv_split(const FrontDev*
 }
 
 // ---- host launchers ------------------------------------------------------------------------------------------
-// Assembly of the fronts of a large-front launch: the gathering kernel when it applies (big_assembly_kind,
-// mf_launch_plan.hpp), the column-tiled one otherwise.  with_diag asks the gather launch for an extra workgroup per
-// front that factors block 0 (big_block0_kind says MF_B0_GATHER only when the gathering kernel applies).
-inline void launch_big_assemble(const FactorArgs& a, const MfLaunch& L, bool with_diag) {
-    if (big_assembly_kind(L) != MF_ASM_GATHER) {
-        launch_big_assemble_cols(a, L);
-        return;
-    }
-    if (a.grec) {                      // static gather maps (analyze()); a.grec == nullptr: MGBHIP_GATHER_LDS_MAPS=1
-        const int ct = big_gather_ct(L, a.gather_ct);
-        const dim3 ga((L.max_m + ct - 1) / ct + (with_diag ? 1 : 0), L.count);      // + the diagonal-block workgroup
-        // LDS: rows c0 .. m - 1 of the maps of one front
-        hipLaunchKernelGGL(mf_big_gather, ga, dim3(256), big_gather_lds(L), a.st, a.fr, L.first, a.grec + L.grec_first, a.gmap,
-                           a.a_src, a.a_dst, a.a_colptr, a.values, a.arena, a.dscr, a.status, with_diag ? 1 : 0, ct);
-        return;
-    }
-    dim3 ga = big_assemble_grid(L);
-    const int ct = CT;                 // (one column per wave on levels with few fronts, ct = 4: no gain, measured in round 4)
-    if (with_diag) ga.x += 1;          // the diagonal-block workgroup
-    hipLaunchKernelGGL(mf_big_gather_lds, ga, dim3(256), big_gather_lds(L), a.st, a.fr, L.first, a.children, a.rel, a.a_src, a.a_dst,
-                       a.a_colptr, a.values, a.arena, L.max_m, a.dscr, a.status, with_diag ? 1 : 0, ct);
-}
-
 inline void launch_big_diag0(const FactorArgs& a, const MfLaunch& L, int nfronts) {
     hipLaunchKernelGGL(mf_big_diag0, dim3(nfronts), dim3(256), 0, a.st, a.fr, L.first, a.arena, a.dscr, a.status);
 }

@@ -1,5 +1,6 @@
 // mf_big_subst.hpp -- large fronts (m > lds_cap), substitution generation: a batch of multi-workgroup kernels per tree
-// level (grid.y = front within the batch).  Column-tiled assembly, then per 32-column panel a (redundant diagonal
+// level (grid.y = front within the batch).  After the assembly (mf_big_assemble.hpp, shared with the inverse-based
+// generation), per 32-column panel a (redundant diagonal
 // LDL' + row-tile triangular solve) kernel and a 64x64-tiled symmetric rank-32 update kernel; triangular solves
 // either one launch per 32-column block step or, while the work vector fits in LDS, one workgroup per front (big1).
 // This is the path of fronts beyond BIG_INV_MAX_M, of MGBHIP_OLD_BIG=1 and of MfSolver::robust.
@@ -8,80 +9,6 @@
 
 namespace mgbhip {
 namespace {
-
-// Assembly of destination columns [c0, c0 + CT): zero, scatter A, extend-add the children.
-__global__ __launch_bounds__(256) void mf_big_assemble(const FrontDev* __restrict__ fr, int32_t first,
-                                                       const int32_t* __restrict__ children,
-                                                       const int32_t* __restrict__ rel,
-                                                       const int32_t* __restrict__ a_src,
-                                                       const int32_t* __restrict__ a_dst,
-                                                       const int32_t* __restrict__ a_colptr,
-                                                       const double* __restrict__ Hval, double* __restrict__ arena) {
-    __shared__ int32_t rls[ASM_REL_LDS];
-    const FrontDev F = fr[first + blockIdx.y];
-    const int m = F.m;
-    const int c0 = blockIdx.x * CT;
-    if (c0 >= m) return;
-    const int c1 = min(c0 + CT, m);
-    double* W = arena + F.F_off;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;     // one wave per destination column, lanes on the rows
-    for (int c = c0 + wave; c < c1; c += 4) {
-        double* Wc = W + (int64_t)c * m;
-        for (int r = c + lane; r < m; r += 64) Wc[r] = 0.0;
-    }
-    __syncthreads();
-    {   // A entries are grouped by pivot column: the per-column offsets give the range of [c0, c1)
-        const int32_t* cp = a_colptr + F.acol_off;
-        const int beg = cp[min(c0, F.k)], end = cp[min(c1, F.k)];
-        const int32_t* ad = a_dst + F.a_off;
-        for (int t = beg + tid; t < end; t += 256) W[ad[t]] = Hval[a_src[F.a_off + t]];
-    }
-    __syncthreads();
-    for (int c = 0; c < F.nchild; ++c) {
-        const FrontDev C = fr[children[F.child_off + c]];
-        const double* U = arena + C.F_off;
-        const int mc = C.m, kc = C.k, b = mc - kc;
-        const int32_t* rlg = rel + C.rel_off;
-        // relative indices of this child in LDS: the two searches and the scatter below read them
-        // from there instead of chasing ~2 log2(b) dependent global loads
-        const bool in_lds = b <= ASM_REL_LDS;
-        if (in_lds)
-            for (int j = tid; j < b; j += 256) rls[j] = rlg[j];
-        __syncthreads();
-        const int32_t* rl = in_lds ? rls : rlg;
-        // child columns whose destination lies in [c0, c1): rel is increasing
-        int lo = 0, hi = b;
-        while (lo < hi) { int mid = (lo + hi) >> 1; if (rl[mid] < c0) lo = mid + 1; else hi = mid; }
-        const int jb = lo;
-        hi = b;
-        while (lo < hi) { int mid = (lo + hi) >> 1; if (rl[mid] < c1) lo = mid + 1; else hi = mid; }
-        const int je = lo;
-        for (int j = jb + wave; j < je; j += 4) {
-            double* Wc = W + (int64_t)rl[j] * m;
-            const double* Uc = U + (int64_t)(kc + j) * mc + kc;
-            // the read-modify-write chain rl -> W is latency bound and W may alias U for the
-            // compiler: stage four independent rows per lane so their loads are in flight together
-            for (int r = j + lane; r < b; r += 256) {
-                const int r1 = r + 64, r2 = r + 128, r3 = r + 192;
-                const int i0 = rl[r];
-                const int i1 = r1 < b ? rl[r1] : i0;
-                const int i2 = r2 < b ? rl[r2] : i0;
-                const int i3 = r3 < b ? rl[r3] : i0;
-                const double u0 = Uc[r];
-                const double u1 = r1 < b ? Uc[r1] : 0.0;
-                const double u2 = r2 < b ? Uc[r2] : 0.0;
-                const double u3 = r3 < b ? Uc[r3] : 0.0;
-                const double w0 = Wc[i0], w1 = Wc[i1], w2 = Wc[i2], w3 = Wc[i3];
-                Wc[i0] = w0 + u0;
-                if (r1 < b) Wc[i1] = w1 + u1;
-                if (r2 < b) Wc[i2] = w2 + u2;
-                if (r3 < b) Wc[i3] = w3 + u3;
-            }
-        }
-        __syncthreads();
-    }
-}
 
 // Panel step.  Every workgroup of a front loads the (fully updated, still unfactored)
 // diagonal block, wave 0 factors it redundantly in LDS, then the workgroup solves its TR
@@ -595,12 +522,6 @@ __global__ __launch_bounds__(BIG1_THREADS) void mf_bwd_big1(const FrontDev* __re
 }
 
 // ---- host launchers ------------------------------------------------------------------------------------------
-inline dim3 big_assemble_grid(const MfLaunch& L) { return dim3((L.max_m + CT - 1) / CT, L.count); }
-inline void launch_big_assemble_cols(const FactorArgs& a, const MfLaunch& L) {
-    hipLaunchKernelGGL(mf_big_assemble, big_assemble_grid(L), dim3(256), 0, a.st, a.fr, L.first, a.children, a.rel, a.a_src,
-                       a.a_dst, a.a_colptr, a.values, a.arena);
-}
-
 // The pivot chain of `nfronts` assembled fronts: per 32-column step the panel solve (which factors the diagonal block
 // of step 0 itself) and the trailing update with its look-ahead workgroup.
 inline void launch_subst_steps(const FactorArgs& a, const MfLaunch& L, int nfronts) {

@@ -7,7 +7,7 @@
 // lower triangle is the update matrix the parent reads.  Every extend-add runs child by child in a
 // fixed order on disjoint destination columns: no atomics, bitwise reproducible factors.
 //
-// mf_device.hpp, mf_small.hpp, mf_big_subst.hpp and mf_big_inv.hpp are included by mf_numeric.hip alone and form ONE
+// mf_device.hpp, mf_small.hpp, mf_big_subst.hpp, mf_big_inv.hpp and mf_big_assemble.hpp are included by mf_numeric.hip alone and form ONE
 // translation unit on purpose: the probe build (-DMGB_STEP_PROBE, tools/gpu_probe*.py) shares one __device__ g_probe
 // between the families, and the library is built without relocatable device code.  Each family header keeps the host
 // launchers of its kernels beside them; a kernel with dynamic LDS has ONE size function (*_lds) that its launch and

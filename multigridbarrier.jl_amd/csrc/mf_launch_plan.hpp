@@ -4,7 +4,8 @@
 // the kernel a hand-built pattern must get (tests/solver_gate_cases.py).
 //
 // The shape predicates of the launchers live here too (assembly kind, block-0 kind, backward variant): the launch code in
-// mf_small.hpp / mf_big_inv.hpp / mf_numeric.hip and the read-only report launch_rows() call the same functions.
+// mf_small.hpp / mf_big_inv.hpp / mf_big_assemble.hpp / mf_numeric.hip and the read-only report launch_rows() call the same
+// functions.
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -10,7 +10,8 @@
 //
 // The kernels and their host launchers live in the family headers, all part of this one translation unit
 // (mf_device.hpp says why): mf_small.hpp (fronts factored out of LDS, m <= lds_cap), mf_big_subst.hpp and
-// mf_big_inv.hpp (the two generations of multi-workgroup kernels for larger fronts).  Here: analyze() turns the
+// mf_big_inv.hpp (the two generations of multi-workgroup kernels for larger fronts), mf_big_assemble.hpp (the assembly
+// of those fronts, shared by both generations).  Here: analyze() turns the
 // symbolic plan into per-level launch lists (the classification itself is host-only code in mf_launch_plan.hpp, shared with
 // the CPU checker build), factor() / forward_pass() / backward_pass() walk them.
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 #include "mf_small.hpp"
 #include "mf_big_subst.hpp"
 #include "mf_big_inv.hpp"
+#include "mf_big_assemble.hpp"
 
 namespace mgbhip {
 

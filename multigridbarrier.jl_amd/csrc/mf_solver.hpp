@@ -23,7 +23,7 @@ struct FrontDev {
 };
 
 // Device arrays of the factorization in progress / of one triangular sweep, as the launchers beside the kernels
-// (mf_small.hpp, mf_big_subst.hpp, mf_big_inv.hpp) hand them on.
+// (mf_small.hpp, mf_big_subst.hpp, mf_big_inv.hpp, mf_big_assemble.hpp) hand them on.
 struct FactorArgs {
     const FrontDev* fr;
     const int32_t *children, *rel, *a_src, *a_dst, *a_colptr;
