@@ -445,6 +445,46 @@ int mgbhip_quadrature_plan(int32_t d, int32_t e, int32_t p, int32_t Q, int64_t N
 int mgbhip_quadrature_times(const mgbhip_quadrature* quad, double* ms2);
 int mgbhip_quadrature_destroy(mgbhip_quadrature* quad); /* NULL is a no-op */
 
+/* ---- residual: the element-interior residual of the p-Laplace equation ---------------------------------------------
+ * The half of the residual a-posteriori estimator that the face jumps below leave out: with the sign convention of the
+ * ENERGY kind above [-div a(grad u) = f, a(g) = |g|^(pexp-2) g] the strong residual r = f + div a(grad u) at the points
+ * of a rule and, per element, h_K^2 times the integral of r^2.  N elements of p nodes in d = e = 2 or 3 coordinates
+ * [x: (p N) x d, element-major] and a rule of Q points per element with positive weights wref [Q], given with the
+ * element basis at its points: phi [Q x p], dphi [Q x p x d] and d2phi [Q x p x d(d+1)/2, the second derivatives in
+ * reference coordinates in the order (0,0), (0,1), (1,1) for d = 2 and (0,0), (0,1), (0,2), (1,1), (1,2), (2,2) for
+ * d = 3].  Nothing else tells the library the element family.  At point q of an element with nodes x_i and values z_i
+ *     J = sum_i x_i dphi[q][i]^T,   measure_q = wref[q] det J,   g = grad u = J^-T sum_i dphi[q][i] z_i,
+ *     H_xi(v) = sum_i v_i d2phi[q][i],   H = J^-T [H_xi(z) - sum_a g_a H_xi(x_a)] J^-1   [the Hessian of u in x; exact on
+ *     curved elements],   div a = |g|^(pexp-2) [tr H + (pexp - 2) g^T H g / |g|^2];   pexp = 2: tr H;   g = 0: 0.
+ * Everything is copied.  A handle belongs to the context it was created from and must be destroyed before it.
+ *  - create: MGBHIP_ERR_INVALID if det J is not positive and finite at a point of the rule.
+ *  - geometry [any pointer may be NULL]: points [N x Q x d], weights [N x Q, the measures], sizes [N: h_K = |K|^(1/d),
+ *    |K| the sum of an element's measures in point order].
+ *  - source: f as p N nodal values carried to the points by phi [at_points = 0] or as N x Q values at the points
+ *    [at_points = 1]; one source serves every column.  z [(p N) x ncol]; pexp finite and >= 1.
+ *  - pointwise: r [N x Q x ncol], no reduction.
+ *  - integrate: per column and element h_K^2 times the sum over its points of measure_q r_q^2, into per_element
+ *    [N x ncol] or NULL, and their sum into totals [ncol].  An element's value is the sum of its Q terms in an order
+ *    fixed by Q alone, the totals are compensated sums over the elements in a fixed order: results are reproducible bit
+ *    for bit, do not depend on per_element, and a column's do not depend on the other columns.
+ *  - plan [no handle, no device]: the ten slots of mgbhip_quadrature_plan for that shape; S, G and the LDS base are those
+ *    of a quadrature of the same shape, the tables have 1 + d + d(d+1)/2 rows per node.
+ *  - times: device milliseconds of the last pointwise or integrate call, taken with events on the context's stream:
+ *    ms2 = { the element kernel, the reduction over the elements [0 after pointwise] }; invalid before the first call. */
+typedef struct mgbhip_residual mgbhip_residual;
+int mgbhip_residual_create(mgbhip_ctx* ctx, int32_t d, int32_t p, int64_t N, const double* x, int32_t Q, const double* wref,
+                           const double* phi, const double* dphi, const double* d2phi, mgbhip_residual** out);
+int mgbhip_residual_geometry(mgbhip_residual* res, double* points /* N x Q x d */, double* weights /* N x Q */,
+                             double* sizes /* N */);
+int mgbhip_residual_pointwise(mgbhip_residual* res, double pexp, int32_t ncol, const double* z /* (p*N) x ncol */,
+                              const double* source /* p*N, or N x Q */, int32_t at_points, double* r /* N x Q x ncol */);
+int mgbhip_residual_integrate(mgbhip_residual* res, double pexp, int32_t ncol, const double* z /* (p*N) x ncol */,
+                              const double* source /* p*N, or N x Q */, int32_t at_points,
+                              double* per_element /* N x ncol, or NULL */, double* totals /* ncol */);
+int mgbhip_residual_plan(int32_t d, int32_t p, int32_t Q, int64_t N, int32_t* out16);
+int mgbhip_residual_times(const mgbhip_residual* res, double* ms2);
+int mgbhip_residual_destroy(mgbhip_residual* res); /* NULL is a no-op */
+
 /* ---- faces: the facets of a mesh, fluxes through its boundary and jumps across its interior faces ------------------
  * N elements of p nodes in d = e = 2 or 3 coordinates [x: (p N) x d, element-major; t: N x p global node ids in
  * [0, 2^31)], F local faces per element with 2^(d-1) corner nodes each [corners: F x 2^(d-1) local node indices] and a

@@ -29,6 +29,7 @@ try:  # the device layer needs the built shared library; importing the setup lay
     from .closest import closest_point, ClosestPointLocator
     from .integrate import Quadrature, integrate, norm
     from .faces import Faces, boundary_flux, jump_indicator
+    from .estimate import ResidualEstimator, residual_estimator, strong_residual
     from .contour import isocontour, Contour, tessellate, Tessellation
     from .raycast import RayCaster, camera_rays, render_volume
     from .surface import TriangleCaster, Hits, render_surfaces, render_figure

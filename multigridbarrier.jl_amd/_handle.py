@@ -1,5 +1,5 @@
 """The lifecycle every post-processing class shares (`PointLocator`, `RayCaster`, `TriangleCaster`, `SegmentCaster`,
-`StreamTracer`, `FigureRenderer`, `Quadrature`, `Faces`): one context of its own, one handle of the C ABI in it, `close()`, the context-manager
+`StreamTracer`, `FigureRenderer`, `Quadrature`, `Faces`, `ResidualEstimator`): one context of its own, one handle of the C ABI in it, `close()`, the context-manager
 protocol and `__del__`.  The device layer is imported only when a handle is created, so an object that needs no device
 (no points, no rays, an empty soup) needs no library either."""
 from __future__ import annotations

@@ -17,6 +17,7 @@
 #include "polyline.hpp"
 #include "problem.hpp"
 #include "quadrature.hpp"
+#include "residual.hpp"
 #include "raycast.hpp"
 #include "stream.hpp"
 #include "surface.hpp"
@@ -66,6 +67,7 @@ struct mgbhip_locator : Handle<Locator> {};            // a point locator (inter
 struct mgbhip_closest : Handle<Closest> {};            // a closest-point locator (closest.hpp)
 struct mgbhip_quadrature : Handle<Quadrature> {};      // a quadrature rule on a mesh (quadrature.hpp)
 struct mgbhip_faces : Handle<Faces> {};                // the facets of a mesh (faces.hpp)
+struct mgbhip_residual : Handle<Residual> {};          // a rule with second derivatives on a flat mesh (residual.hpp)
 struct mgbhip_contour : Handle<Contour> {};            // a simplex soup (contour.hpp)
 struct mgbhip_tessellation : Handle<Tessellation> {};  // the lattice triangles of a 2-D mesh (contour.hpp)
 struct mgbhip_weld : Handle<Weld> {};                  // the index of a welded soup (weld.hpp)
@@ -1077,7 +1079,7 @@ int mgbhip_quadrature_plan(int32_t d, int32_t e, int32_t p, int32_t Q, int64_t N
     MGB_REQUIRE(out != nullptr, "null argument");
     MGB_REQUIRE(quad_dims_ok(d, e) && p >= 1 && Q >= 1 && N >= 1, "quadrature: bad sizes");
     const QuadPlan plan = quad_decide(d, e, p, Q, N);
-    quad_plan_out(plan, (int32_t)plan.lds, quad_lds_tables(d, p, Q), out);
+    quad_plan_out(plan, (int32_t)plan.lds, quad_lds_tables(1 + d, p, Q), out);
     return MGBHIP_OK;
     MGB_API_END
 }
@@ -1092,6 +1094,91 @@ int mgbhip_quadrature_times(const mgbhip_quadrature* h, double* ms) {
 }
 
 int mgbhip_quadrature_destroy(mgbhip_quadrature* h) { return destroy_handle(h); }
+
+int mgbhip_residual_create(mgbhip_ctx* ctx, int32_t d, int32_t p, int64_t N, const double* x, int32_t Q, const double* wref,
+                           const double* phi, const double* dphi, const double* d2phi, mgbhip_residual** out) {
+    MGB_API_BEGIN_ON(ctx)
+    MGB_REQUIRE(ctx != nullptr, "null context");
+    MGB_REQUIRE(out != nullptr, "null output pointer");
+    MGB_REQUIRE(d == 2 || d == 3, "residual: d must be 2 or 3");
+    MGB_REQUIRE(N > 0, "residual: no elements (N = 0)");
+    MGB_REQUIRE(p >= 1 && Q >= 1, "residual: bad sizes");
+    MGB_REQUIRE(x != nullptr && wref != nullptr && phi != nullptr && dphi != nullptr && d2phi != nullptr, "null argument");
+    const int32_t M = d * (d + 1) / 2;
+    MGB_REQUIRE((int64_t)residual_rows(d) * Q * p < (int64_t)INT32_MAX && (int64_t)p * N * d < (int64_t)INT32_MAX &&
+                    N * Q * (d + 1) < (int64_t)INT32_MAX,
+                "residual: sizes exceed 32-bit indexing");
+    MGB_REQUIRE(residual_decide(d, p, Q, N).G >= 1, "residual: an element's nodes do not fit in LDS");
+    for (int64_t i = 0; i < (int64_t)p * N * d; ++i) MGB_REQUIRE(std::isfinite(x[i]), "residual: the mesh has non-finite node coordinates");
+    for (int32_t q = 0; q < Q; ++q) MGB_REQUIRE(std::isfinite(wref[q]) && wref[q] > 0.0, "residual: the rule's weights must be positive and finite");
+    for (int64_t i = 0; i < (int64_t)Q * p; ++i) MGB_REQUIRE(std::isfinite(phi[i]), "residual: the basis tables must be finite");
+    for (int64_t i = 0; i < (int64_t)Q * p * d; ++i) MGB_REQUIRE(std::isfinite(dphi[i]), "residual: the basis tables must be finite");
+    for (int64_t i = 0; i < (int64_t)Q * p * M; ++i) MGB_REQUIRE(std::isfinite(d2phi[i]), "residual: the basis tables must be finite");
+    create_handle(ctx, out, [&](Residual& Rd) { residual_build(Rd, d, p, N, x, Q, wref, phi, dphi, d2phi, ctx->stream); });
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_residual_geometry(mgbhip_residual* h, double* points, double* weights, double* sizes) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null residual");
+    residual_geometry(h->obj, points, weights, sizes, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+// the checks pointwise and integrate share
+static void residual_check_call(const Residual& Rd, double pexp, int32_t ncol, const double* z, const double* source, int32_t at_points) {
+    MGB_REQUIRE(ncol >= 1, "residual: bad sizes");
+    MGB_REQUIRE(z != nullptr && source != nullptr, "null argument");
+    MGB_REQUIRE(at_points == 0 || at_points == 1, "residual: at_points must be 0 (p N nodal values) or 1 (N x Q values at the points)");
+    MGB_REQUIRE(std::isfinite(pexp) && pexp >= 1.0, "residual: p must be finite and >= 1");
+    MGB_REQUIRE((int64_t)Rd.p * Rd.N * ncol < (int64_t)INT32_MAX && Rd.N * Rd.Q * ncol < (int64_t)INT32_MAX,
+                "residual: sizes exceed 32-bit indexing");
+}
+
+int mgbhip_residual_pointwise(mgbhip_residual* h, double pexp, int32_t ncol, const double* z, const double* source, int32_t at_points,
+                              double* r) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null residual");
+    residual_check_call(h->obj, pexp, ncol, z, source, at_points);
+    MGB_REQUIRE(r != nullptr, "null argument");
+    residual_pointwise(h->obj, pexp, ncol, z, source, at_points == 1, r, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_residual_integrate(mgbhip_residual* h, double pexp, int32_t ncol, const double* z, const double* source, int32_t at_points,
+                              double* per_element, double* totals) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null residual");
+    residual_check_call(h->obj, pexp, ncol, z, source, at_points);
+    MGB_REQUIRE(totals != nullptr, "null argument");
+    residual_integrate(h->obj, pexp, ncol, z, source, at_points == 1, per_element, totals, h->ctx->stream);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_residual_plan(int32_t d, int32_t p, int32_t Q, int64_t N, int32_t* out) {
+    MGB_API_BEGIN
+    MGB_REQUIRE(out != nullptr, "null argument");
+    MGB_REQUIRE((d == 2 || d == 3) && p >= 1 && Q >= 1 && N >= 1, "residual: bad sizes");
+    const QuadPlan plan = residual_decide(d, p, Q, N);
+    quad_plan_out(plan, (int32_t)plan.lds, quad_lds_tables(residual_rows(d), p, Q), out);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_residual_times(const mgbhip_residual* h, double* ms) {
+    MGB_API_BEGIN_ON(h)
+    MGB_REQUIRE(h != nullptr, "null residual");
+    MGB_REQUIRE(ms != nullptr, "null argument");
+    residual_times(h->obj, ms);
+    return MGBHIP_OK;
+    MGB_API_END
+}
+
+int mgbhip_residual_destroy(mgbhip_residual* h) { return destroy_handle(h); }
 
 static_assert(MGBHIP_FACE_VALUE == FACE_VALUE && MGBHIP_FACE_FLUX == FACE_FLUX, "mgbhip.h mirrors FaceKind");
 

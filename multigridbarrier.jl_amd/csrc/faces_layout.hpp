@@ -12,7 +12,7 @@ constexpr int FACE_MAX_QF = 100;              // points per face, at most: 10 pe
 // the offsets the face kernel carves LDS with: xs at 0, zs = xs + face_lds_xs, red = zs + face_lds_zs, tab = red + quad_lds_red
 constexpr size_t face_lds_xs(int G, int sides, int p, int d) { return quad_even((size_t)G * sides * p * d); }
 constexpr size_t face_lds_zs(int G, int sides, int p) { return quad_even((size_t)G * sides * p * QUAD_CHUNK); }
-constexpr size_t face_lds_tables(int d, int p, int Qf, int F) { return (size_t)F * quad_lds_tables(d, p, Qf); }
+constexpr size_t face_lds_tables(int d, int p, int Qf, int F) { return (size_t)F * quad_lds_tables(1 + d, p, Qf); }
 
 // nfaces faces of Qf points, one lane each; sides = 1 for a boundary face (its element), 2 for an interior face (the L
 // element, then the R element), each of p nodes in d coordinates; the tables of all F local faces are staged together.

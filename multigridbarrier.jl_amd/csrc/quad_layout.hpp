@@ -26,6 +26,7 @@ constexpr size_t QUAD_LDS_MAX = 160 * 1024;       // launch cap (the element ker
 //   red [CHUNK][256]   one partial sum per lane and column
 //   tab           phi and dphi at the rule's points, point fastest -- only while everything stays under the cap
 //                 element: [p][1 + d][Q]             face: [F][p][1 + d][Qf], one table per local face
+//                 element residual (residual.hip): [p][1 + d + d (d + 1) / 2][Q], the second derivatives behind dphi
 constexpr size_t quad_even(size_t n) { return (n + 1) & ~(size_t)1; }
 constexpr size_t quad_lds_region(int G, size_t per_item) { return quad_even((size_t)G * per_item); }
 // the offsets the element kernel carves LDS with: xs at 0, zs = xs + quad_lds_xs, fs = zs + quad_lds_zs, red = fs + quad_lds_fs,
@@ -38,7 +39,8 @@ constexpr size_t quad_lds_red() { return (size_t)QUAD_CHUNK * QUAD_THREADS; }
 constexpr size_t quad_lds_base(int G, size_t xs_item, size_t zs_item, size_t fs_item) {
     return (quad_lds_region(G, xs_item) + quad_lds_region(G, zs_item) + quad_lds_region(G, fs_item) + quad_lds_red()) * sizeof(double);
 }
-constexpr size_t quad_lds_tables(int d, int p, int Q) { return (size_t)(1 + d) * Q * p * sizeof(double); }
+// rows: the table rows of a node, 1 + d for phi and dphi
+constexpr size_t quad_lds_tables(int rows, int p, int Q) { return (size_t)rows * Q * p * sizeof(double); }
 
 struct QuadPlan {
     int threads;         // QUAD_THREADS
@@ -73,7 +75,7 @@ constexpr QuadPlan quad_decide_lanes(int S, size_t xs_item, size_t zs_item, size
 // N elements of p nodes in e coordinates, Q points each: S = min(Q, 256) lanes per element
 constexpr QuadPlan quad_decide(int d, int e, int p, int Q, long long N) {
     return quad_decide_lanes(Q < QUAD_THREADS ? Q : QUAD_THREADS, (size_t)p * e, (size_t)p * QUAD_CHUNK, (size_t)p,
-                             quad_lds_tables(d, p, Q), N);
+                             quad_lds_tables(1 + d, p, Q), N);
 }
 
 }  // namespace mgbhip

@@ -120,6 +120,8 @@ EXPORTS = [
     "mgbhip_closest_create", "mgbhip_closest_fetch", "mgbhip_closest_evaluate", "mgbhip_closest_destroy",
     "mgbhip_quadrature_create", "mgbhip_quadrature_points", "mgbhip_quadrature_weights", "mgbhip_quadrature_integrate",
     "mgbhip_quadrature_max", "mgbhip_quadrature_plan", "mgbhip_quadrature_times", "mgbhip_quadrature_destroy",
+    "mgbhip_residual_create", "mgbhip_residual_geometry", "mgbhip_residual_pointwise", "mgbhip_residual_integrate",
+    "mgbhip_residual_plan", "mgbhip_residual_times", "mgbhip_residual_destroy",
     "mgbhip_faces_create", "mgbhip_faces_topology", "mgbhip_faces_geometry", "mgbhip_faces_sizes", "mgbhip_faces_integrate",
     "mgbhip_faces_jumps", "mgbhip_faces_indicator", "mgbhip_faces_plan", "mgbhip_faces_times", "mgbhip_faces_destroy",
     "mgbhip_contour_create", "mgbhip_contour_fetch", "mgbhip_contour_destroy", "mgbhip_contour_create_embedded",
@@ -232,6 +234,14 @@ def load_library():
     lib.mgbhip_quadrature_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _ip]
     lib.mgbhip_quadrature_times.argtypes = [vp, _dp]
     lib.mgbhip_quadrature_destroy.argtypes = [vp]
+    lib.mgbhip_residual_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp,
+                                           C.POINTER(C.c_void_p)]
+    lib.mgbhip_residual_geometry.argtypes = [vp, _dp, _dp, _dp]
+    lib.mgbhip_residual_pointwise.argtypes = [vp, C.c_double, C.c_int32, _dp, _dp, C.c_int32, _dp]
+    lib.mgbhip_residual_integrate.argtypes = [vp, C.c_double, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp]
+    lib.mgbhip_residual_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _ip]
+    lib.mgbhip_residual_times.argtypes = [vp, _dp]
+    lib.mgbhip_residual_destroy.argtypes = [vp]
     lib.mgbhip_faces_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, _dp, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
                                         _dp, _ip, C.c_int32, _ip, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.mgbhip_faces_topology.argtypes = [vp, _ip, _ip, _ip, _ip]
