@@ -108,12 +108,17 @@ __global__ __launch_bounds__(256) void mf_big_gather(const FrontDev* __restrict_
                                                      double* __restrict__ dscr, int32_t* __restrict__ status, int with_diag,
                                                      int ct /* destination columns per workgroup */,
                                                      const int32_t* __restrict__ children,
-                                                     const int32_t* __restrict__ rel, int mstride) {
+                                                     const int32_t* __restrict__ rel, int mstride,
+                                                     int roles /* BlockRoles: the grid's layout (with_diag) */) {
     extern __shared__ int32_t inv[];               // [nchild][stride]: rows row0 .. of the tables (column workgroups)
     __shared__ int64_t cU[GATHER_MAX_CHILD];       // LDS_MAPS only: the children's update blocks, relative lists,
     __shared__ int64_t cR[GATHER_MAX_CHILD];       // leading dimensions and sizes
     __shared__ int32_t cM[GATHER_MAX_CHILD], cB[GATHER_MAX_CHILD];
-    const FrontDev F = fr[first + blockIdx.y];
+    // with_diag: the block-0 workgroup is the front's chain workgroup, the column groups its tiles (mf_block_roles.hpp);
+    // a launch without one is the plain grid (column groups, fronts)
+    const BlockRole BR = with_diag ? role_of_block(roles, blockIdx.x, blockIdx.y, gridDim.x)
+                                   : tile_of_block(blockIdx.x, blockIdx.y);
+    const FrontDev F = fr[first + BR.front];
     const int m = F.m, tid = threadIdx.x, nch = F.nchild;
     GatherRec G;                                   // grec: the record of the launch's first front
     const int64_t* base;                           // per child: start of its update block in the arena ...
@@ -129,13 +134,13 @@ __global__ __launch_bounds__(256) void mf_big_gather(const FrontDev* __restrict_
         base = cU;
         ld = cM;
     } else {
-        G = grec[blockIdx.y];
+        G = grec[BR.front];
         base = G.base;
         ld = G.ld;
     }
     const int32_t* mp = LDS_MAPS ? nullptr : gmap + G.map_off;         // static maps: [nchild][m]
     const int32_t* ad = a_dst + F.a_off;
-    if (with_diag && blockIdx.x == gridDim.x - 1) {
+    if (BR.chain()) {
         // One extra workgroup per front forms ONLY the first 32 x 32 diagonal block (same gather, same order as
         // the column workgroups, which write it to the arena), factors and inverts it and leaves W_0 / d_0 in slot 0:
         // step 0 of the factorization finds its diagonal block ready, as every later step does from the look-ahead
@@ -196,10 +201,10 @@ __global__ __launch_bounds__(256) void mf_big_gather(const FrontDev* __restrict_
             if (lu < nb) Dn[lu][lv] += Hval[a_src[F.a_off + t]];
         }
         __syncthreads();
-        block0_to_slot(Dn, Wv, Tm, dq, nb, tid, status, dscr + (int64_t)blockIdx.y * 2 * (NB * NB));
+        block0_to_slot(Dn, Wv, Tm, dq, nb, tid, status, dscr + (int64_t)BR.front * 2 * (NB * NB));
         return;
     }
-    const int c0 = blockIdx.x * ct;
+    const int c0 = BR.tile() * ct;
     if (c0 >= m) return;
     const int c1 = min(c0 + ct, m);
     double* W = arena + F.F_off;
@@ -291,12 +296,14 @@ inline void launch_big_assemble(const FactorArgs& a, const MfLaunch& L, bool wit
     const bool lds_maps = !a.grec;     // no static gather maps (analyze()): MGBHIP_GATHER_LDS_MAPS=1
     // (one column per wave on levels with few fronts, ct = 4: no gain, measured in round 4)
     const int ct = lds_maps ? CT : big_gather_ct(L, a.gather_ct);
-    const dim3 ga((L.max_m + ct - 1) / ct + (with_diag ? 1 : 0), L.count);      // + the diagonal-block workgroup
+    const int ncol = (L.max_m + ct - 1) / ct;
+    // the column groups of every front + its diagonal-block workgroup, or the column groups alone
+    const RolesGrid ga = with_diag ? roles_grid(a.gather_roles, L.count, ncol) : tiles_only_grid(L.count, ncol);
     const auto gather = lds_maps ? mf_big_gather<true> : mf_big_gather<false>;
     // LDS: rows c0 .. m - 1 of the maps of one front, or its whole tables
-    hipLaunchKernelGGL(gather, ga, dim3(256), big_gather_lds(L), a.st, a.fr, L.first, lds_maps ? nullptr : a.grec + L.grec_first,
+    hipLaunchKernelGGL(gather, dim3(ga.x, ga.y), dim3(256), big_gather_lds(L), a.st, a.fr, L.first, lds_maps ? nullptr : a.grec + L.grec_first,
                        a.gmap, a.a_src, a.a_dst, a.a_colptr, a.values, a.arena, a.dscr, a.status, with_diag ? 1 : 0, ct,
-                       a.children, a.rel, L.max_m);
+                       a.children, a.rel, L.max_m, a.gather_roles);
 }
 
 }  // namespace

@@ -16,6 +16,7 @@
 // diagonal block: strictly UPPER triangle = off-diagonal of M_j, its diagonal lives in `dvec`;
 // the lower triangle keeps the unfactored block (sibling workgroups of step 0 still read it).
 #pragma once
+#include "mf_block_roles.hpp"
 #include "mf_device.hpp"
 
 namespace mgbhip {
@@ -78,7 +79,8 @@ __device__ __forceinline__ void slice_transform(double (*P)[ST + 1], double (*Po
 }
 
 #ifdef MGB_STEP_PROBE      // development probe build only (tools/gpu_probe.py): per-phase timestamps of one step
-#define PROBE(i) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) g_probe[i] = wall_clock64(); if (!is_la && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) g_probe[16 + i] = wall_clock64(); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define PROBE_NFRONTS (roles == ROLES_CHAIN_FIRST ? gridDim.x : gridDim.y)      // of the launch (roles_grid)
+#define PROBE(i) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) g_probe[i] = wall_clock64(); if (!is_la && BR.first_tile() && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) g_probe[16 + i] = wall_clock64(); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define PROBE(i) do { } while (0)
 #endif
@@ -86,14 +88,15 @@ __device__ __forceinline__ void slice_transform(double (*P)[ST + 1], double (*Po
 __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict__ fr, int32_t first, int j0,
                                                    double* __restrict__ arena, double* __restrict__ dscr,
                                                    double* __restrict__ dvec, int32_t* __restrict__ status,
-                                                   int do_diag) {
+                                                   int do_diag, int roles /* BlockRoles: the grid's layout */) {
     __shared__ double Wv[NB][NB + 1];
     __shared__ double Dn[NB][NB + 1];
     __shared__ double Tm[16][17];
     __shared__ double dq[NB], rdq[NB];
     __shared__ double Pa[NB][ST + 1];
     __shared__ double Pb[NB][ST + 1];
-    const FrontDev F = fr[first + blockIdx.y];      // (as kernel arguments for launches of few fronts: the kernel sits at its
+    const BlockRole BR = role_of_block(roles, blockIdx.x, blockIdx.y, gridDim.x);      // mf_block_roles.hpp
+    const FrontDev F = fr[first + BR.front];        // (as kernel arguments for launches of few fronts: the kernel sits at its
                                                       // 168-register cap and spilled, 6 % slower end to end: measured in round 4)
     const int m = F.m, k = F.k;
     if (j0 >= k) return;
@@ -102,11 +105,11 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
     const int T = (m - j1 + ST - 1) / ST;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double* W = arena + F.F_off;
-    double* slot = dscr + ((int64_t)blockIdx.y * 2 + ((j0 / NB) & 1)) * (NB * NB);
-    const bool is_la = blockIdx.x == gridDim.x - 1;
+    double* slot = dscr + ((int64_t)BR.front * 2 + ((j0 / NB) & 1)) * (NB * NB);
+    const bool is_la = BR.chain();
     int ti = 0, tj = 0;
     if (!is_la) {
-        const int lin = blockIdx.x;
+        const int lin = BR.tile();
         ti = (int)((sqrt(8.0 * lin + 1.0) - 1.0) * 0.5);
         while ((ti + 1) * (ti + 2) / 2 <= lin) ++ti;
         while (ti * (ti + 1) / 2 > lin) --ti;
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
     const int rbase = is_la ? j1 : j1 + ti * ST, cbase = j1 + tj * ST;
     PROBE(0);
 #ifdef MGB_STEP_PROBE
-    if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) g_probe[34] = clock64();
+    if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) g_probe[34] = clock64();
 #endif
     const int fr16 = lane & 15, fk = lane >> 4;
 
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
     // matrix cores, straight from the accumulators (the tile above the diagonal is the mirror image: skipped).
     // Written by tile workgroup 0 (done at 6 us, every workgroup has W_j staged) rather than by the look-ahead
     // workgroup, whose 1.7 us for it sat on the critical path of the pivot chain; steps without tiles keep it there.
-    if (is_la ? T == 0 : blockIdx.x == 0) {          // T is this front's own tile count (a batch is launched for its largest front)
+    if (is_la ? T == 0 : BR.first_tile()) {          // T is this front's own tile count (a batch is launched for its largest front)
         {
             const int rt = wave & 1, ct = wave >> 1;
             if (ct <= rt) {
@@ -228,7 +231,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
             Dn[rr][c] = (rr >= c && rr < nbn) ? cw[0][t] + Dn[rr][c] : 0.0;
         }
         __syncthreads();
-        double* nslot = dscr + ((int64_t)blockIdx.y * 2 + ((j1 / NB) & 1)) * (NB * NB);
+        double* nslot = dscr + ((int64_t)BR.front * 2 + ((j1 / NB) & 1)) * (NB * NB);
         PROBE(4);
 #ifdef MGB_STEP_PROBE
         // cold / warm experiment: the same factorization twice (Dn saved and restored in between)
@@ -236,22 +239,22 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
         for (int t = 0; t < 4; ++t) { const int i = tid + 256 * t; sv[t] = Dn[i % NB][i / NB]; }
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
-        if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) { g_probe[32] = clock64(); g_probe[36] = wall_clock64(); }
+        if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) { g_probe[32] = clock64(); g_probe[36] = wall_clock64(); }
         __builtin_amdgcn_sched_barrier(0);
         block_ldlt32(Dn, dq, nbn, tid, nullptr);
         __builtin_amdgcn_sched_barrier(0);
-        if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) { g_probe[33] = clock64(); g_probe[37] = wall_clock64(); }
+        if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) { g_probe[33] = clock64(); g_probe[37] = wall_clock64(); }
         __builtin_amdgcn_sched_barrier(0);
         for (int t = 0; t < 4; ++t) { const int i = tid + 256 * t; Dn[i % NB][i / NB] = sv[t]; }
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
-        if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) { g_probe[38] = clock64(); g_probe[44] = wall_clock64(); }
+        if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) { g_probe[38] = clock64(); g_probe[44] = wall_clock64(); }
         __builtin_amdgcn_sched_barrier(0);
 #endif
         block_ldlt32(Dn, dq, nbn, tid, status);
 #ifdef MGB_STEP_PROBE
         __builtin_amdgcn_sched_barrier(0);
-        if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) { g_probe[39] = clock64(); g_probe[45] = wall_clock64(); }
+        if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) { g_probe[39] = clock64(); g_probe[45] = wall_clock64(); }
         __builtin_amdgcn_sched_barrier(0);
 #endif
         PROBE(5);
@@ -263,7 +266,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
         }
         PROBE(7);
 #ifdef MGB_STEP_PROBE
-        if (is_la && blockIdx.y == 0 && tid == 0 && j0 == 64 && gridDim.y == 1 && F.k > 400) g_probe[35] = clock64();
+        if (is_la && BR.front == 0 && tid == 0 && j0 == 64 && PROBE_NFRONTS == 1 && F.k > 400) g_probe[35] = clock64();
 #endif
         return;
     }
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(256, 3) void mf_big_step(const FrontDev* __restrict
             acc[tb] = __builtin_amdgcn_mfma_f64_16x16x4f64(Pb[4 * kk + fk][16 * tb + fr16], s, acc[tb], 0, 0, 0);
         }
     }
-    const int nskip = (blockIdx.x == 0 && look) ? nbn : 0;               // corner owned by the look-ahead workgroup
+    const int nskip = (BR.first_tile() && look) ? nbn : 0;               // corner owned by the look-ahead workgroup
 #pragma unroll
     for (int tb = 0; tb < 4; ++tb)
 #pragma unroll
@@ -741,9 +744,9 @@ inline void launch_inv_steps(const FactorArgs& a, const MfLaunch& L, int nfronts
     for (int j0 = 0; j0 < L.max_k; j0 += NB) {
         const int rem = L.max_m - j0;
         const int T = std::max(0, (rem - 1 + ST - 1) / ST);
-        const dim3 gs(T * (T + 1) / 2 + 1, nfronts);         // trailing tiles + the look-ahead workgroup
-        hipLaunchKernelGGL(mf_big_step, gs, dim3(256), 0, a.st, a.fr, L.first, j0, a.arena, a.dscr, a.dvec, a.status,
-                           (j0 == 0 && diag_in_step0) ? 1 : 0);
+        const RolesGrid g = roles_grid(a.step_roles, nfronts, T * (T + 1) / 2);     // the look-ahead workgroup + the trailing tiles
+        hipLaunchKernelGGL(mf_big_step, dim3(g.x, g.y), dim3(256), 0, a.st, a.fr, L.first, j0, a.arena, a.dscr, a.dvec, a.status,
+                           (j0 == 0 && diag_in_step0) ? 1 : 0, a.step_roles);
     }
 }
 

@@ -10,9 +10,11 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "host_util.hpp"     // env_on
+#include "mf_block_roles.hpp"
 #include "mf_analysis.hpp"
 
 namespace mgbhip {
@@ -60,12 +62,21 @@ struct MfSwitches {
                             // class > 32 (default 0: factor_small_threads chooses per launch; tests/test_gpu_small_threads.py)
     bool border_launches;   // MGBHIP_BORDER_LAUNCHES=1: a carried factorization and its sweep launch the 1 x 1 border front too
                             // (MfSolver::skips_border; the reference of tests/test_gpu_border_skip.py)
+    int step_roles;         // MGBHIP_CHAIN_ORDER=legacy: the grids of mf_big_step and mf_big_gather in the layout ROLES_LEGACY (the chain
+    int gather_roles;       // workgroup of a front dispatched after its tiles) instead of ROLES_CHAIN_FIRST (mf_block_roles.hpp); `step`
+                            // / `gather`: chain-first in that kernel only (the per-kernel A/B of profiles/chain_order_ab.txt); unset or
+                            // any other value: chain-first in both, the shipped configuration.  The same
+                            // kernels and arithmetic either way; the reference of tests/test_gpu_chain_order.py
     static MfSwitches from_env() {
         auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
+        const char* co = getenv("MGBHIP_CHAIN_ORDER");
+        const std::string order = co ? co : "";
+        const int step = (order == "legacy" || order == "gather") ? ROLES_LEGACY : ROLES_CHAIN_FIRST;
+        const int gather = (order == "legacy" || order == "step") ? ROLES_LEGACY : ROLES_CHAIN_FIRST;
         return {env_on("MGBHIP_NO_GEO"), env_on("MGBHIP_OLD_BIG"), !env_on("MGBHIP_NO_MERGE_GROUPS"), !env_on("MGBHIP_NO_PACKED_LEAVES"),
                 !env_on("MGBHIP_NO_WAVE_SMALL"), num("MGBHIP_INV_MIN_N", 1024), num("MGBHIP_WAVE_MIN_N", 0),
                 env_on("MGBHIP_GATHER_LDS_MAPS"), (int)num("MGBHIP_GATHER_CT", 0), num("MGBHIP_BWD_SPLIT", 1) != 0,
-                (int)num("MGBHIP_SMALL_THREADS", 0), env_on("MGBHIP_BORDER_LAUNCHES")};
+                (int)num("MGBHIP_SMALL_THREADS", 0), env_on("MGBHIP_BORDER_LAUNCHES"), step, gather};
     }
 };
 

@@ -232,6 +232,8 @@ void MfSolver::analyze(int64_t n, const int32_t* rowptr, const int32_t* colidx, 
         compute_units = std::max(cus, 1);
     }
     border_launches = sw.border_launches;
+    step_roles = sw.step_roles;
+    gather_roles = sw.gather_roles;
     {   // the border unknown's own root front (mf_analyze: above every other root, so alone on the last level)
         const int32_t nlev = (int32_t)plan.level_ptr.size() - 1;
         border_alone = false;
@@ -279,7 +281,7 @@ void MfSolver::factor(const double* d_values, hipStream_t st, StageTimers* timer
     const FactorArgs a{condensed ? d_fronts_c.p : d_fronts.p, d_children.p, d_rel.p,
                        condensed ? d_a_src_c.p : (direct ? d_a_src_direct.p : d_a_src.p), condensed ? d_a_dst_c.p : d_a_dst.p,
                        condensed ? d_a_colptr_c.p : d_a_colptr.p, d_values, d_arena.p, d_dscr.p, d_dvec.p, d_status.p, st,
-                       d_grec.n ? d_grec.p : nullptr, d_gmap.p, gather_ct, small_threads, compute_units};
+                       d_grec.n ? d_grec.p : nullptr, d_gmap.p, gather_ct, small_threads, compute_units, step_roles, gather_roles};
     if (timers) timers->begin("factor");
     factored_inv = !robust;
     // The border front's pivot -1 - lambda^2 is read by nobody on the carried path (the Newton loop forms lambda^2 = <g, n>

@@ -36,6 +36,7 @@ struct FactorArgs {
     int gather_ct;              // MGBHIP_GATHER_CT (0: big_gather_ct chooses)
     int small_threads;          // MGBHIP_SMALL_THREADS (0: factor_small_threads chooses)
     int compute_units;          // of the device, for factor_small_threads
+    int step_roles, gather_roles;   // BlockRoles (mf_block_roles.hpp) of the mf_big_step / mf_big_gather grids: MGBHIP_CHAIN_ORDER
 };
 struct SolveArgs {
     const FrontDev* fr;
@@ -162,6 +163,7 @@ class MfSolver {
     int gather_ct = 0;              // MfSwitches::gather_ct of the last analyze()
     int small_threads = 0;          // MfSwitches::small_threads of the last analyze()
     int compute_units = 1;          // of the current device, queried by analyze()
+    int step_roles = ROLES_CHAIN_FIRST, gather_roles = ROLES_CHAIN_FIRST;   // MfSwitches::step_roles / gather_roles of the last analyze()
     bool border_launches = false;   // MfSwitches::border_launches of the last analyze()
     bool border_alone = false;      // the plan's last level is the 1 x 1 border front and nothing else
     bool border_skipped = false;    // the current factors were formed without the border front's launch ...
